@@ -70,9 +70,15 @@ def parse():
                     help="gradient all-reduce message type (parallel.GradReducer comm_dtype; bf16 halves the bytes on xGMI)")
     ap.add_argument("--ddp-no-overlap", action="store_true", help="A/B: issue every gradient collective after backward (GradReducer overlap=False)")
     ap.add_argument("--ddp-no-measure", action="store_true", help="A/B: no event brackets around the collectives (GradReducer measure=False)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (its losses, and a fixed seeded sample of "
+                         "each network's parameters and buffers after the update) as DIR/<name>.npy for output-for-output comparisons")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)   # child process of the default run
     ap.add_argument("--spawn-selftest", default=None, help=argparse.SUPPRESS)             # tests: rendezvous of the spawned ranks over gloo, no GPU
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_opt(args, device):
@@ -110,6 +116,35 @@ def synthetic_batch(n, size, seed, label_nc=6):
     for i in range(n):
         labels[i, 1 + i % (label_nc - 1)] = 1
     return bg, labels, df
+
+
+DUMP_ELEMS = 14 * 2 ** 20       # float32 elements of network state written by --dump-outputs, all networks together (56 MiB)
+
+
+def dump_outputs(tr, out_dir):
+    """What a caller of tr.step() receives from its last call: the step's losses (float64 scalars, one file each) and the
+    networks' state after the update -- parameters and buffers of each network's state_dict, in its order, flattened and
+    concatenated as float32.  A network with more elements than its share of DUMP_ELEMS is written as a sample at sorted
+    indices drawn by a generator seeded with 0, so the same arguments always select the same elements.
+    Writes DIR/loss_<kind>_<name>.npy and DIR/<net>_state.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if hasattr(tr, "flush_losses"):
+        tr.flush_losses()
+    for kind, named in tr.losses.items():
+        for name, vals in named.items():
+            if vals:
+                np.save(os.path.join(out_dir, f"loss_{kind}_{name}.npy"), np.array(vals[-1], dtype=np.float64))
+    nets = tr.model.networks
+    share = DUMP_ELEMS // max(len(nets), 1)
+    for net_name, net in nets.items():
+        with torch.no_grad():
+            flat = torch.cat([v.detach().flatten().float() for v in net.state_dict().values()])
+            if flat.numel() > share:
+                idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+                flat = flat[idx.to(flat.device)]
+            np.save(os.path.join(out_dir, f"{net_name}_state.npy"), flat.cpu().numpy())
 
 
 def cpu_baseline():
@@ -334,6 +369,8 @@ def main():
     host_enqueue = time.perf_counter() - t0         # the host's share: every launch of the timed steps is enqueued, nothing awaited
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:             # before the roofline's extra steps below move the weights again
+        dump_outputs(tr, args.dump_outputs)
     ddp = red.overlap_report() if red is not None else None
     red_stats = dict(red.stats) if red is not None else None      # before the extra steps below add to them
     fam, fam_extra, extra_steps = {}, {}, 0
