@@ -119,6 +119,10 @@ SIGNATURES = {
     "dei2i_label_gb_wgrad": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "dei2i_adam_step": (c_int, [_P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, _P]),
     "dei2i_sgd_rmsprop_step": (c_int, [_P, c_int, c_int64, c_int, c_float, c_float, c_float, c_float, _P]),
+    "dei2i_adam_step_l2": (c_int, [_P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, _P]),
+    "dei2i_ema_lerp": (c_int, [_P, c_int, c_int64, c_float, _P]),
+    "dei2i_diffaug_partial_floats": (c_size_t, [c_int]),
+    "dei2i_diffaug": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dei2i_prof_enable": (c_int, [c_int, c_int]),
     "dei2i_prof_collect": (c_int, [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
     "dei2i_prof_collect_timed": (c_int, [c_int, POINTER(c_int64), POINTER(c_double)]),

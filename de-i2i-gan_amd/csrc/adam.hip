@@ -2,6 +2,7 @@
 // torch.optim.Adam single-tensor semantics (no amsgrad), reference call site trainers/base_trainer.py:75-89
 // (Adam betas (0.5, 0.999); AdamW betas (0.9, 0.95) with torch's default decoupled weight decay 1e-2 for the MAE stage):
 //   p *= 1 - lr*wd  (AdamW only: keep = 1 - lr*wd, 1 for Adam)
+//   g = g*grad_scale + wd*p  (COUPLED: torch.optim.Adam's weight_decay, stargan-v2 core/solver.py:52-56; p.grad is not written)
 //   m += (1-b1)(g-m); v = b2 v + (1-b2) g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
 #include <hip/hip_runtime.h>
 
@@ -10,9 +11,10 @@
 
 namespace dei2i {
 
+template <bool COUPLED>
 __global__ __launch_bounds__(256) void adam_kernel(const dei2i_adam_rec* __restrict__ table, float lr, float beta1,
                                                    float beta2, float eps, float bias_c1, float bias_c2_sqrt,
-                                                   float grad_scale, float keep) {
+                                                   float grad_scale, float keep, float wd) {
   const dei2i_adam_rec rec = table[blockIdx.y];
   const float step_size = lr / bias_c1;
   const float inv_c2 = 1.f / bias_c2_sqrt;
@@ -28,7 +30,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const dei2i_adam_rec* __restr
     float* pp = &p.x; const float* gp = &g.x; float* mp = &m.x; float* vp = &v.x;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float gv = gp[e] * grad_scale;
+      const float gv = COUPLED ? gp[e] * grad_scale + wd * pp[e] : gp[e] * grad_scale;
       mp[e] = mp[e] + (1.f - beta1) * (gv - mp[e]);
       vp[e] = beta2 * vp[e] + (1.f - beta2) * gv * gv;
       const float denom = sqrtf(vp[e]) * inv_c2 + eps;
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const dei2i_adam_rec* __restr
     reinterpret_cast<float4*>(rec.v)[i] = v;
   }
   for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gv = rec.g[i] * grad_scale;
+    const float gv = COUPLED ? rec.g[i] * grad_scale + wd * rec.p[i] : rec.g[i] * grad_scale;
     const float m = rec.m[i] + (1.f - beta1) * (gv - rec.m[i]);
     const float v = beta2 * rec.v[i] + (1.f - beta2) * gv * gv;
     rec.m[i] = m;
@@ -68,6 +70,19 @@ __global__ __launch_bounds__(256) void sgd_rmsprop_kernel(const dei2i_adam_rec* 
   }
 }
 
+// stargan-v2's EMA (core/solver.py:549-551: param_test = torch.lerp(param, param_test, beta)) over every tensor of a network in
+// place: rec.p = param_test (lerp end), rec.g = param (lerp start).  torch.lerp's formula: start + w (end - start) for |w| < 0.5,
+// end - (end - start)(1 - w) otherwise.
+__global__ __launch_bounds__(256) void ema_lerp_kernel(const dei2i_adam_rec* __restrict__ table, float w) {
+  const dei2i_adam_rec rec = table[blockIdx.y];
+  const int64_t n = rec.n, stride = (int64_t)gridDim.x * blockDim.x;
+  const bool hi = fabsf(w) >= 0.5f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float start = rec.g[i], end = rec.p[i], diff = end - start;
+    rec.p[i] = hi ? end - diff * (1.f - w) : start + w * diff;
+  }
+}
+
 }  // namespace dei2i
 
 using namespace dei2i;
@@ -90,7 +105,27 @@ extern "C" int dei2i_adam_step(const dei2i_adam_rec* table_dev, int count, int64
   int64_t bx = (max_n / 4 + 255) / 256;
   if (bx < 1) bx = 1;
   if (bx > 512) bx = 512;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, lr, beta1, beta2,
-                     eps, bias_c1, bias_c2_sqrt, grad_scale, 1.f - lr * decoupled_decay);
+  hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, lr, beta1,
+                     beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, 1.f - lr * decoupled_decay, 0.f);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dei2i_adam_step_l2(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2,
+                                  float eps, float bias_c1, float bias_c2_sqrt, float grad_scale, float weight_decay, dei2i_stream s) {
+  if (!table_dev || count <= 0 || max_n <= 0) return DEI2I_ERR_BAD_ARG;
+  int64_t bx = (max_n / 4 + 255) / 256;
+  if (bx < 1) bx = 1;
+  if (bx > 512) bx = 512;
+  hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, lr, beta1,
+                     beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, 1.f, weight_decay);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dei2i_ema_lerp(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float weight, dei2i_stream s) {
+  if (!table_dev || count <= 0 || max_n <= 0) return DEI2I_ERR_BAD_ARG;
+  int64_t bx = (max_n + 255) / 256;
+  if (bx < 1) bx = 1;
+  if (bx > 1024) bx = 1024;
+  hipLaunchKernelGGL(ema_lerp_kernel, dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, weight);
   return (int)hipGetLastError();
 }

@@ -1956,6 +1956,70 @@ def upsample2(x):
 
 
 # --------------------------------------------------------------------------------------------------------------
+# DiffAugment (utils/diffaug.py) as fused HIP kernels (csrc/diffaug.hip): one affine operator per sample and canonical-order policy
+# run; its input gradient is the adjoint, whose own gradient is the forward's linear part -- differentiable to any order (the R1
+# penalty of stargan-v2 differentiates D(DiffAugment(x)) with respect to x with create_graph=True).  No image is saved: the
+# per-sample parameter table and the run's flags are all either direction needs.
+# --------------------------------------------------------------------------------------------------------------
+def _diffaug_run(x, tab, run, mode: int):
+    color, ch, cw = run
+    x = x.contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    n, c, h, w = x.shape
+    out = torch.empty_like(x)
+    lib = _lib_for(x)
+    partial = torch.empty(lib.dei2i_diffaug_partial_floats(n), dtype=torch.float32, device=x.device) if color else None
+    L.check(lib.dei2i_diffaug(mode, n, c, h, w, ch, cw, int(color), _p(x), _p(tab), _p(partial), _p(out), _stream()), "diffaug")
+    return out
+
+
+class _DiffAug(torch.autograd.Function):
+    """mode 0: y = Cut Trans (L x + beta); mode 1: its linear part (beta = 0)"""
+
+    @staticmethod
+    def forward(ctx, x, tab, run, mode, host):
+        ctx.tab, ctx.run, ctx.host = tab, run, host       # (host: the pinned source of tab's upload, alive while the graph is)
+        return _diffaug_run(x, tab, run, mode)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _DiffAugAdjoint.apply(g, ctx.tab, ctx.run), None, None, None, None
+
+
+class _DiffAugAdjoint(torch.autograd.Function):
+    """the input gradient L Trans^T Cut g; linear in g, its transpose is the forward's linear part"""
+
+    @staticmethod
+    def forward(ctx, g, tab, run):
+        ctx.tab, ctx.run = tab, run
+        return _diffaug_run(g, tab, run, 2)
+
+    @staticmethod
+    def backward(ctx, gg):
+        return _DiffAug.apply(gg, ctx.tab, ctx.run, 1, None), None, None
+
+
+def diff_augment(x, policy=""):
+    """DiffAugment(x, policy) of utils/diffaug.py on an NCHW fp32 GPU image batch: the same draws from the global CPU RNG, one upload
+    of the parameter table per call, one or two launches per canonical-order policy run.  ``policy == ""`` returns ``x`` itself."""
+    if not policy:
+        return x
+    from .utils.diffaug import draw_params
+    _require_gpu(x, "diff_augment")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise TypeError("diff_augment expects an NCHW fp32 image batch")
+    n, _, h, w = x.shape
+    rec, runs = draw_params(policy, n, h, w)
+    host = torch.empty(rec.shape, dtype=torch.int32, pin_memory=True)
+    host.copy_(torch.from_numpy(rec))
+    tab = host.to(x.device, non_blocking=True)
+    for i, run in enumerate(runs):
+        x = _DiffAug.apply(x, tab[i], run, 0, host)
+    return x
+
+
+# --------------------------------------------------------------------------------------------------------------
 # generator heads: tanh / sigmoid / compose  (generator.py:268-270), NaN guard (generator.py:266-267)
 # --------------------------------------------------------------------------------------------------------------
 class _Compose(torch.autograd.Function):

@@ -3,7 +3,8 @@
 A ``torch.optim.Optimizer`` subclass, so ``lr_scheduler``s, ``param_groups`` / ``add_param_group`` and
 ``torch.amp.GradScaler`` keep working the way the reference's trainers use them (trainers/base_trainer.py:68-126,
 mae_trainer.py:28,139-158).  Semantics = torch.optim.Adam (no amsgrad), or torch.optim.AdamW with ``weight_decay > 0``
-(decoupled: p *= 1 - lr*wd before the update): parameters whose ``grad`` is None are skipped and get no state."""
+(decoupled: p *= 1 - lr*wd before the update): parameters whose ``grad`` is None are skipped and get no state.
+``ema_lerp_`` is stargan-v2's parameter EMA on the same pointer table (csrc/adam.hip)."""
 import ctypes
 import math
 
@@ -47,14 +48,11 @@ class FusedAdam(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             wd = float(group.get("weight_decay", 0.0))
             for t, plist in by_step.items():
-                if wd > 0.0 and not self.decoupled:          # coupled L2 decay: one multi-tensor launch on the gradients, then plain Adam
-                    if self.grad_scale != 1.0:
-                        raise NotImplementedError("coupled weight decay with a gradient scale")
-                    torch._foreach_add_([p.grad for p in plist], [p.data for p in plist], alpha=wd)
-                self._launch(plist, t, float(group["lr"]), b1, b2, group["eps"], wd if self.decoupled else 0.0)
+                # coupled L2 decay (g*grad_scale + wd*p) inside the kernel: p.grad is left as the caller's
+                self._launch(plist, t, float(group["lr"]), b1, b2, group["eps"], wd, coupled=wd > 0.0 and not self.decoupled)
         return loss
 
-    def _launch(self, plist, t, lr, b1, b2, eps, weight_decay=0.0):
+    def _launch(self, plist, t, lr, b1, b2, eps, weight_decay=0.0, coupled=False):
         dev = plist[0].device
         lib = ops._lib_for(plist[0])
         n = len(plist)
@@ -80,11 +78,45 @@ class FusedAdam(torch.optim.Optimizer):
             table.copy_(torch.tensor(rows, dtype=torch.int64))
             table_dev = table.to(dev, non_blocking=True)
             cache[key] = (rows, table_dev)
-        L.check(lib.dei2i_adam_step(ctypes.c_void_p(table_dev.data_ptr()), n, max_n, lr, b1, b2, eps, 1.0 - b1 ** t,
-                                    math.sqrt(1.0 - b2 ** t), self.grad_scale, weight_decay, ops._stream()), "adam_step")
+        step = lib.dei2i_adam_step_l2 if coupled else lib.dei2i_adam_step
+        L.check(step(ctypes.c_void_p(table_dev.data_ptr()), n, max_n, lr, b1, b2, eps, 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t),
+                     self.grad_scale, weight_decay, ops._stream()), "adam_step")
         for p in plist:
             p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1      # raw-pointer update: invalidate packed copies
             p._dei2i_keep = None
+
+
+def ema_lerp_(ema_params, params, weight):
+    """``e.copy_(torch.lerp(p, e, weight))`` for every pair, in place, one launch (stargan-v2 moving_average, core/solver.py:549-551).
+    Every updated tensor's ``_dei2i_epoch`` is bumped: the packed-weight caches of the EMA network are keyed on it."""
+    ema_params, params = list(ema_params), list(params)
+    if len(ema_params) != len(params):
+        raise ValueError("ema_lerp_: parameter lists differ in length")
+    if not params:
+        return
+    rows, max_n = [], 0
+    for e, p in zip(ema_params, params):
+        ops._require_gpu(e, "ema_lerp_")
+        if e.dtype != torch.float32 or p.dtype != torch.float32 or e.shape != p.shape or not e.is_contiguous() or not p.is_contiguous():
+            raise TypeError("ema_lerp_ expects pairs of contiguous fp32 tensors of one shape")
+        if e.device != p.device:
+            raise ValueError("ema_lerp_: the EMA copy and the parameter are on different devices")
+        rows.append((e.data_ptr(), p.data_ptr(), 0, 0, p.numel()))
+        max_n = max(max_n, p.numel())
+    dev = ema_params[0].device
+    hit = _ema_tables.get((dev, rows[0][0], len(rows)))
+    if hit is not None and hit[0] == rows:
+        table_dev = hit[1]
+    else:
+        table_dev = torch.tensor(rows, dtype=torch.int64).to(dev)
+        _ema_tables[(dev, rows[0][0], len(rows))] = (rows, table_dev)
+    lib = ops._lib_for(ema_params[0])
+    L.check(lib.dei2i_ema_lerp(ctypes.c_void_p(table_dev.data_ptr()), len(rows), max_n, float(weight), ops._stream()), "ema_lerp")
+    for e in ema_params:
+        e._dei2i_epoch = getattr(e, "_dei2i_epoch", 0) + 1      # raw-pointer update: invalidate packed copies
+
+
+_ema_tables = {}
 
 
 class _FusedPlain(torch.optim.Optimizer):

@@ -1,18 +1,32 @@
 """The reference's stargan-v2 loss functions and train iteration (stargan-v2/core/solver.py) on the product's networks: same function
 names, argument meaning and return values (loss tensor + a namespace of floats); ``Solver.train_iteration`` is one pass of the body of
-``Solver.train`` (solver.py:262-296) for ``norm_type adain``."""
+``Solver.train`` (solver.py:262-296) for ``norm_type adain``, ``w_hpf 0``:
+
+  * DiffAugment(., args.DiffAugment) on what the discriminator sees -- x_real and x_fake of the D loss, x_fake of the G loss
+    (solver.py:472,481,510), drawn from the global CPU RNG in the reference's order; the R1 penalty is taken with respect to the
+    un-augmented x_real, through the augmentation (ops.diff_augment is differentiable twice);
+  * lambda_ds decayed linearly to 0 over args.ds_iter iterations (solver.py:311-313), after the EMA;
+  * Adam with coupled weight decay per network, EMA (beta 0.999) of the generator-side networks.
+
+Not the reference's iteration: ``generator.update_stats()`` is not called (open item), and the w_hpf > 0 / SEAN paths
+(heat-map masks, their downloaded weights) are not built."""
 from types import SimpleNamespace
 
 import torch
-import torch.nn.functional as F
 
-from ..optim import FusedAdam
+from .. import ops
+from ..optim import FusedAdam, ema_lerp_
+
+
+def _floats(*losses):
+    """the values of 0-dim loss tensors, in one device-to-host read"""
+    return torch.stack([t.detach().float() for t in losses]).tolist()
 
 
 def adv_loss(logits, target):
     """solver.py:566-570"""
     assert target in [1, 0]
-    return F.binary_cross_entropy_with_logits(logits, torch.full_like(logits, fill_value=float(target)))
+    return ops.bce_logits(logits, float(target))
 
 
 def r1_reg(d_out, x_in):
@@ -34,17 +48,19 @@ def get_style_code(nets, norm_type, num_embeds, y_trg, x_ref, z_trg):
 def compute_d_loss(nets, args, x_real, y_org, y_trg, z_trg=None, x_ref=None, masks=None):
     """solver.py:467-491"""
     assert (z_trg is None) != (x_ref is None)
+    policy = getattr(args, "DiffAugment", "")
     x_real.requires_grad_()
-    out = nets.discriminator(x_real, y_org)
+    out = nets.discriminator(ops.diff_augment(x_real, policy), y_org)
     loss_real = adv_loss(out, 1)
     loss_reg = r1_reg(out, x_real)
     with torch.no_grad():
         s_trg = get_style_code(nets, args.norm_type, 1, y_trg, x_ref, z_trg)
         x_fake = nets.generator(x_real, s_trg, labels=y_trg, masks=masks)
-    out = nets.discriminator(x_fake, y_trg)
+    out = nets.discriminator(ops.diff_augment(x_fake, policy), y_trg)
     loss_fake = adv_loss(out, 0)
     loss = loss_real + loss_fake + args.lambda_reg * loss_reg
-    return loss, SimpleNamespace(real=loss_real.item(), fake=loss_fake.item(), reg=loss_reg.item())
+    real, fake, reg = _floats(loss_real, loss_fake, loss_reg)
+    return loss, SimpleNamespace(real=real, fake=fake, reg=reg)
 
 
 def compute_g_loss(nets, args, x_real, y_org, y_trg, z_trgs=None, x_refs=None, masks=None):
@@ -54,33 +70,35 @@ def compute_g_loss(nets, args, x_real, y_org, y_trg, z_trgs=None, x_refs=None, m
     x_ref, x_ref2 = x_refs if x_refs is not None else (None, None)
     s_trg = get_style_code(nets, args.norm_type, args.num_embeds, y_trg, x_ref, z_trg)
     x_fake = nets.generator(x_real, s_trg, labels=y_trg, masks=masks)
-    out = nets.discriminator(x_fake, y_trg)
+    out = nets.discriminator(ops.diff_augment(x_fake, getattr(args, "DiffAugment", "")), y_trg)
     loss_adv = adv_loss(out, 1)
     s_pred = get_style_code(nets, args.norm_type, args.num_embeds, y_trg, x_fake, z_trg=None)
-    loss_sty = torch.mean(torch.abs(s_pred - s_trg))
+    loss_sty = ops.l1(s_pred, s_trg)
     s_trg2 = get_style_code(nets, args.norm_type, args.num_embeds, y_trg, x_ref2, z_trg=z_trg2)
     x_fake2 = nets.generator(x_real, s_trg2, labels=y_trg, masks=masks).detach()
-    loss_ds = torch.mean(torch.abs(x_fake - x_fake2))
+    loss_ds = ops.l1(x_fake, x_fake2)
     s_org = get_style_code(nets, args.norm_type, args.num_embeds, y_org, x_real, z_trg=None)
     x_rec = nets.generator(x_fake, s_org, labels=y_org, masks=None)
-    loss_cyc = torch.mean(torch.abs(x_rec - x_real))
+    loss_cyc = ops.l1(x_rec, x_real)
     loss = loss_adv + args.lambda_sty * loss_sty - args.lambda_ds * loss_ds + args.lambda_cyc * loss_cyc
-    return loss, SimpleNamespace(adv=loss_adv.item(), sty=loss_sty.item(), ds=loss_ds.item(), cyc=loss_cyc.item())
+    adv, sty, ds, cyc = _floats(loss_adv, loss_sty, loss_ds, loss_cyc)
+    return loss, SimpleNamespace(adv=adv, sty=sty, ds=ds, cyc=cyc)
 
 
 def moving_average(model, model_test, beta=0.999):
-    """solver.py:549-551"""
+    """solver.py:549-551: param_test = lerp(param, param_test, beta), every tensor of the network in one launch, in place"""
     with torch.no_grad():
-        for param, param_test in zip(model.parameters(), model_test.parameters()):
-            param_test.data = torch.lerp(param.data, param_test.data, beta)
+        ema_lerp_(model_test.parameters(), model.parameters(), beta)
 
 
 class Solver:
     """solver.py:33-56 (networks, EMA copies, one Adam per network: lr / f_lr for the mapping network, betas, coupled weight decay)
-    + one iteration of ``train`` (solver.py:262-296, norm_type adain).  The optimizers are the product's fused multi-tensor Adam."""
+    + one iteration of ``train`` (solver.py:262-296 and the lambda_ds decay of 311-313, norm_type adain).  The optimizers are the
+    product's fused multi-tensor Adam, the EMA one multi-tensor launch per network."""
 
     def __init__(self, args, nets, nets_ema, device="cuda:0"):
         self.args, self.nets, self.nets_ema, self.device = args, nets, nets_ema, torch.device(device)
+        self.initial_lambda_ds = args.lambda_ds          # the lambda_ds decay step is initial / ds_iter (solver.py:311-313)
         for ns in (nets, nets_ema):
             for m in vars(ns).values():
                 m.to(self.device)
@@ -117,4 +135,6 @@ class Solver:
         optims.generator.step()
         for name in ("generator", "mapping_network", "style_encoder"):
             moving_average(getattr(nets, name), getattr(self.nets_ema, name), beta=0.999)
+        if args.lambda_ds > 0:
+            args.lambda_ds -= self.initial_lambda_ds / getattr(args, "ds_iter", 100000)
         return out

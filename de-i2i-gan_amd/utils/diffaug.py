@@ -3,9 +3,12 @@ to the images the discriminator sees (utils/diffaug.py:9-76; call sites defectga
 'color' (brightness, saturation, contrast), 'translation' (random shift by up to 1/8 of the side, zero fill) and 'cutout'
 (a random half-size square set to zero), all differentiable w.r.t. the image.
 
-NCHW fp32 images, plain torch ops (3-channel images in front of the discriminator: plumbing, not a hot kernel).  The
-per-sample random numbers are drawn with the global torch RNG ON THE HOST in the reference's order -- a run seeded like
-the reference's CPU path sees the reference's augmentations -- and uploaded (a few values per sample)."""
+NCHW fp32 images.  The policy functions below are plain torch ops and define the semantics (the defectGAN model calls
+them); ``ops.diff_augment`` is the same map as fused HIP kernels (csrc/diffaug.hip), differentiable to any order, whose
+host half is ``draw_params``.  The per-sample random numbers are drawn with the global torch RNG ON THE HOST in the
+reference's order -- a run seeded like the reference's CPU path sees the reference's augmentations -- and uploaded (a few
+values per sample)."""
+import numpy as np
 import torch
 
 
@@ -71,3 +74,58 @@ def diff_augment(x, policy=""):
         for fn in POLICIES[name]:
             x = fn(x)
     return x.contiguous()
+
+
+# ---- host half of the fused HIP op (ops.diff_augment, csrc/diffaug.hip) ----------------------------------------------------------
+CANONICAL = ("color", "translation", "cutout")
+REC_FIELDS = 8          # struct dei2i_diffaug_rec: a, b, k, beta (fp32), ty, tx, top, left (int32)
+
+
+def policy_runs(policy):
+    """the policy list split into maximal runs in canonical order (color -> translation -> cutout), each launched as one operator;
+    an unknown name raises KeyError before anything is drawn"""
+    names = policy.split(",") if policy else []
+    for name in names:
+        if name not in POLICIES:
+            raise KeyError(f"DiffAugment policy [{name}] is not defined (color | translation | cutout)")
+    runs = []
+    for name in names:
+        if runs and CANONICAL.index(name) > CANONICAL.index(runs[-1][-1]):
+            runs[-1].append(name)
+        else:
+            runs.append([name])
+    return runs
+
+
+def draw_params(policy, n, h, w):
+    """Draw the per-sample parameters of ``policy`` for an (n, *, h, w) batch from the global CPU torch RNG, in the order and shapes
+    of the policy functions above (one (n,1,1,1) float draw per color function, two (n,1,1) integer draws per translation / cutout).
+    Returns (records, runs): records an int32 (len(runs), n, 8) array of struct dei2i_diffaug_rec (the four floats stored bitwise),
+    runs a list of (has_color, cut_h, cut_w) -- cut_h = cut_w = 0 when the run has no cutout."""
+    runs = policy_runs(policy)
+    rec = np.zeros((len(runs), n, REC_FIELDS), dtype=np.int32)
+    f = rec.view(np.float32)
+    meta = []
+    for r, names in enumerate(runs):
+        f[r, :, 0] = 1.0
+        ch = cw = 0
+        for name in names:
+            if name == "color":
+                rb, rs, rc = (torch.rand(n, 1, 1, 1).view(n) for _ in range(3))
+                ks, kc = rs * 2, rc + 0.5
+                f[r, :, 0] = (kc * ks).numpy()
+                f[r, :, 1] = (kc * (1 - ks)).numpy()
+                f[r, :, 2] = (1 - kc).numpy()
+                f[r, :, 3] = (rb - 0.5).numpy()
+            elif name == "translation":
+                max_y, max_x = int(h * 0.125 + 0.5), int(w * 0.125 + 0.5)
+                rec[r, :, 4] = torch.randint(-max_y, max_y + 1, size=[n, 1, 1]).view(n).numpy()
+                rec[r, :, 5] = torch.randint(-max_x, max_x + 1, size=[n, 1, 1]).view(n).numpy()
+            else:
+                ch, cw = int(h * 0.5 + 0.5), int(w * 0.5 + 0.5)
+                cy = torch.randint(0, h + (1 - ch % 2), size=[n, 1, 1]).view(n)
+                cx = torch.randint(0, w + (1 - cw % 2), size=[n, 1, 1]).view(n)
+                rec[r, :, 6] = (cy - ch // 2).numpy()
+                rec[r, :, 7] = (cx - cw // 2).numpy()
+        meta.append(("color" in names, ch, cw))
+    return rec, meta

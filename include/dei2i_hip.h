@@ -221,6 +221,28 @@ int dei2i_adam_step(const dei2i_adam_rec* table_dev, int count, int64_t max_n, f
 int dei2i_sgd_rmsprop_step(const dei2i_adam_rec* table_dev, int count, int64_t max_n, int kind, float lr, float alpha, float eps,
                            float grad_scale, dei2i_stream s);
 
+/* torch.optim.Adam's coupled weight decay inside the Adam update: the gradient is g * grad_scale + weight_decay * p (p.grad is not
+ * written); otherwise dei2i_adam_step with decoupled_decay 0 */
+int dei2i_adam_step_l2(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2, float eps,
+                       float bias_c1, float bias_c2_sqrt, float grad_scale, float weight_decay, dei2i_stream s);
+/* EMA of a network's parameters in place, one launch (stargan-v2 moving_average, core/solver.py:549-551): rec.p = the EMA copy,
+ * rec.g = the trained parameter, rec.m / rec.v unused; p = torch.lerp(g, p, weight) with torch.lerp's two-sided formula */
+int dei2i_ema_lerp(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float weight, dei2i_stream s);
+
+/* ---- DiffAugment (utils/diffaug.py) on fp32 NCHW images: one canonical-order policy run (color -> translation -> cutout) as
+ * y = Cut . Trans . (L x + beta) per sample, L(x)[c] = a x[c] + b mean_c(x) + k mean_chw(x) (csrc/diffaug.hip).
+ * tab: device array of N records; a = 1, b = k = beta = 0 without color, ty = tx = 0 without translation, ch = cw = 0 without
+ * cutout (the cut window is rows [top, top + ch) x cols [left, left + cw)).  mode 0: forward; 1: forward without beta (linear part);
+ * 2: adjoint (input gradient of src = the output gradient).  partial: dei2i_diffaug_partial_floats(N) floats when color != 0.
+ * Deterministic (fixed-order reductions, no atomics). */
+typedef struct dei2i_diffaug_rec {
+  float a, b, k, beta;
+  int ty, tx, top, left;
+} dei2i_diffaug_rec;
+size_t dei2i_diffaug_partial_floats(int N);
+int dei2i_diffaug(int mode, int N, int C, int H, int W, int ch, int cw, int color, const float* src, const dei2i_diffaug_rec* tab,
+                  float* partial, float* dst, dei2i_stream s);
+
 /* ---- spectral normalisation of a conv weight (--use_spectral; torch.nn.utils.spectral_norm semantics, one power
  * iteration per training-mode forward) ----  W = weight_orig as a (Cout, K) fp32 matrix, u (Cout) / v (K) the module's
  * buffers (updated in place when iterate != 0); u_used / v_used receive the vectors sigma was computed with (the backward
