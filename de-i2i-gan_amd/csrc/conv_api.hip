@@ -10,7 +10,7 @@ int g_use_wgrad_v2 = 1;
 int g_use_wgrad_halo = 1;
 int g_use_wgrad_thin = 1;
 int g_dgrad_s2_ring = 1;          // option "dgrad_s2_ring": stride-2 reflect dgrads decomposed (interior into dx + ring rectangles)
-extern int g_halo_bn, g_halo_stages, g_halo16, g_halo16_stages, g_halo16_fold;
+extern int g_halo16, g_halo16_fold;
 
 static ConvShape to_shape(const dei2i_conv* c) {
   ConvShape s;
@@ -518,7 +518,7 @@ int dei2i_conv2d_dgrad_input(const dei2i_conv* c, const void* dy, const void* wd
 
 /* ---- input gradient + the backward reductions of the norm layer in front of the conv, one launch (conv_halo16.hip EPIN) ---- */
 static bool dgrad_norm_shape_ok(const dei2i_conv* c) {
-  if (!g_halo16 || !g_halo16_fold || g_halo16_stages != 8 || g_halo_bn != 0 || g_halo_stages != 0) return false;   // A/B options
+  if (!g_halo16 || !g_halo16_fold) return false;   // A/B options
   if (!valid_conv(c) || c->dtype != DT_BF16 || c->up) return false;
   if (c->kh != 3 || c->kw != 3 || c->stride != 1 || c->pad != 1 || c->pad_mode != PAD_REFLECT) return false;
   if (c->H % 16 != 0 || c->W % 32 != 0 || c->H < 32 || c->W < 64 || c->CinS < 64 || c->CinS % 8 != 0 || c->CoutS % 32 != 0) return false;
@@ -536,7 +536,7 @@ int dei2i_conv2d_dgrad_input_norm(const dei2i_conv* c, const void* dy, const voi
                                   dei2i_stream s) {
   if (!dy || !wd_packed || !dx || !en || !dgrad_norm_shape_ok(c)) return DEI2I_ERR_BAD_ARG;
   if (!en->x || !en->mean || !en->rstd || !en->partial || en->up < 0 || en->up > 1) return DEI2I_ERR_BAD_ARG;
-  const int kind = en->kind & 0xff;            // (bits 8+: timing-only switches of tools/diag_epin.py)
+  const int kind = en->kind;
   if (kind == 1 ? !en->gb : (kind != 2 || !en->a || !en->b || en->up)) return DEI2I_ERR_BAD_ARG;
   if (en->group_images < 0 || (en->group_images > 0 && c->N % en->group_images != 0)) return DEI2I_ERR_BAD_ARG;
   ConvShape sh = to_shape(c);

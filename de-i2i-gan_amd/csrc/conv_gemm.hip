@@ -251,15 +251,8 @@ __global__ __launch_bounds__(256) void gather_gemm_kernel(const DescPack pack, c
     const f32x4 q = *reinterpret_cast<const f32x4*>(stg + row * SROW + (n - n0));
     if (ws != nullptr) {         // split-K: this slice's fp32 slab, rows indexed by (class base + m); plain stores
       const size_t wrow = (size_t)(pack.m_base[blockIdx.y] + m);
-      if (pack.ws_atomic) {
-        const float qq[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (n + e < wrows) atomicAdd(ws + wrow * ldc + n + e, qq[e]);
-      } else {
-        // columns >= wrows are never read by the finalize kernel: the full vector is stored
-        *reinterpret_cast<f32x4*>(ws + ((size_t)blockIdx.z * slab_rows + wrow) * ldc + n) = q;
-      }
+      // columns >= wrows are never read by the finalize kernel: the full vector is stored
+      *reinterpret_cast<f32x4*>(ws + ((size_t)blockIdx.z * slab_rows + wrow) * ldc + n) = q;
       continue;
     }
     size_t opix;
@@ -556,8 +549,6 @@ static int g_use_halo = 1;
 void set_use_halo(int on) { g_use_halo = on; }
 static int g_use_thin = 1;
 void set_use_thin(int on) { g_use_thin = on; }
-static int g_splitk_atomic = 0;
-void set_splitk_atomic(int on) { g_splitk_atomic = on; }
 
 template <typename T, int BM, int BN, int WM, int WN>
 static hipError_t launch_gg(const DescPack& pack, const void* src, const void* wgt, int wrows, const float* bias,
@@ -632,10 +623,6 @@ static hipError_t gather_gemm_t(const DescPack& pack, const void* src, const voi
     hipError_t e0 = hipMemsetAsync(out, 0, (size_t)g0.N * g0.OH * g0.OW * ldc * sizeof(T), st);
     if (e0 != hipSuccess) return e0;
   }
-  if (splits > 1 && pack.ws_atomic) {
-    hipError_t e0 = hipMemsetAsync(ws, 0, slab_elems * sizeof(float), st);
-    if (e0 != hipSuccess) return e0;
-  }
   hipError_t e;
   int zs = 1;
   if (BN == 128) e = launch_gg<T, 128, 128, 2, 2>(pack, src, wgt, wrows, bias, out, ws, ldc, act, splits, slab_rows, &zs, st);
@@ -648,8 +635,7 @@ static hipError_t gather_gemm_t(const DescPack& pack, const void* src, const voi
     if (blocks > 4096) blocks = 4096;
     count_launch(K_SPLITK_FINALIZE);
     hipLaunchKernelGGL(splitk_finalize_kernel<T>, dim3((unsigned)blocks), dim3(threads), 0, st, pack, (const float*)ws,
-                       pack.ws_atomic ? 1 : zs, slab_elems,
-                       bias, (T*)out, ldc, wrows, act);
+                       zs, slab_elems, bias, (T*)out, ldc, wrows, act);
     e = hipGetLastError();
   }
   return e;
@@ -662,7 +648,6 @@ hipError_t gather_gemm_multi(int dtype, const GatherDesc* descs, const long long
   DescPack pack;
   pack.n = 0;
   pack.ws_compact = compact_ws ? 1 : 0;
-  pack.ws_atomic = g_splitk_atomic;
   pack.skip_dead_taps = compact_ws ? 1 : 0;      // the reflect-ring launches are the compact ones
   for (int i = 0; i < n; ++i) {
     if (descs[i].M <= 0) continue;           // empty parity class

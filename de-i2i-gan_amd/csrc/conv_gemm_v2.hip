@@ -44,8 +44,7 @@ __global__ __launch_bounds__(512) void gather_gemm_v2_kernel(const DescPack pack
                                                              const bf16_t* __restrict__ wgt_base, const int wrows,
                                                              const float* __restrict__ bias, bf16_t* __restrict__ out,
                                                              float* __restrict__ ws, const int ldc, const int act,
-                                                             const int tiles_n, const int ksteps_per_split, const int ablate,
-                                                             unsigned long long* __restrict__ dbg) {
+                                                             const int tiles_n, const int ksteps_per_split) {
   constexpr int STAGE_BYTES = (BM + BN) * 128;
   static_assert(BM % 64 == 0 && (BM / WM) % 32 == 0, "tile rows");
   constexpr int WTM = BM / WM, WTN = BN / WN;
@@ -55,7 +54,6 @@ __global__ __launch_bounds__(512) void gather_gemm_v2_kernel(const DescPack pack
   static_assert(TM >= 1 && TN >= 1, "wave tile must hold at least one 32x32 block");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const unsigned long long t0 = ablate == 5 ? __builtin_amdgcn_s_memtime() : 0ull;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -198,7 +196,6 @@ __global__ __launch_bounds__(512) void gather_gemm_v2_kernel(const DescPack pack
   constexpr int AHEAD = STAGES - 1;
   issue(0, 0);
   if (AHEAD > 1 && nk > 1) issue(1, 1);
-  const unsigned long long t1 = ablate == 5 ? __builtin_amdgcn_s_memtime() : 0ull;
   for (int it = 0; it < nk; ++it) {
     if (AHEAD > 1 && it + 1 < nk) {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LA + LB) : "memory");
@@ -206,11 +203,9 @@ __global__ __launch_bounds__(512) void gather_gemm_v2_kernel(const DescPack pack
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
-    if (it + AHEAD < nk && ablate != 1 && ablate != 3) issue((it + AHEAD) % STAGES, it + AHEAD);
-    if (ablate != 2 && ablate != 3) compute(it % STAGES);
+    if (it + AHEAD < nk) issue((it + AHEAD) % STAGES, it + AHEAD);
+    compute(it % STAGES);
   }
-  const unsigned long long t2 = ablate == 5 ? __builtin_amdgcn_s_memtime() : 0ull;
-  if (ablate == 4) return;
   // ---- epilogue ----
   // D row = channel 4*kg + e of its 16-block, col = pixel l16.  The tile is staged through the (now idle)
   // LDS ring as bf16 [pixel][BN (+8 pad)] with 8-byte writes (row stride 16*odd bytes: 2-way instead of 32-way bank
@@ -254,16 +249,7 @@ __global__ __launch_bounds__(512) void gather_gemm_v2_kernel(const DescPack pack
       *reinterpret_cast<u32x4*>(out + opix * ldc + ncol) = *reinterpret_cast<const u32x4*>(ctile + row * CROW + chunk * 16);
     }
   }
-  if (ablate == 5 && dbg != nullptr && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-    unsigned long long* d = dbg + (size_t)(blockIdx.x + gridDim.x * blockIdx.y) * 4;
-    d[0] = t0; d[1] = t1; d[2] = t2; d[3] = t3;
-  }
 }
-
-int g_v2_ablate = 0;
-unsigned long long* g_v2_dbg = nullptr;
 
 template <int BM, int BN, int WM, int WN, int STAGES>
 static hipError_t launch_v2(const DescPack& pack, const void* src, const void* wgt, int wrows, const float* bias, void* out,
@@ -291,7 +277,7 @@ static hipError_t launch_v2(const DescPack& pack, const void* src, const void* w
   count_launch(K_GATHER_V2);
   prof_begin(PROF_GATHER_GEMM, flops, st);
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, pack.n, zs), dim3(512), lds, st, pack, (const bf16_t*)src,
-                     (const bf16_t*)wgt, wrows, bias, (bf16_t*)out, zs > 1 ? ws : (float*)nullptr, ldc, act, tiles_n, kps, g_v2_ablate, g_v2_dbg);
+                     (const bf16_t*)wgt, wrows, bias, (bf16_t*)out, zs > 1 ? ws : (float*)nullptr, ldc, act, tiles_n, kps);
   prof_end(PROF_GATHER_GEMM, st);
   return hipGetLastError();
 }

@@ -26,10 +26,6 @@
 namespace dei2i {
 
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page_halo[256];
-extern int g_v2_ablate;
-extern unsigned long long* g_v2_dbg;
-int g_halo_mfma32 = 0;
-int g_halo_bn = 0, g_halo_stages = 0;      // tile-size sweep options (0 = the shipped choice)
 
 typedef __attribute__((address_space(3))) void lds_void_h;
 typedef __attribute__((address_space(1))) const void gbl_void_h;
@@ -48,6 +44,7 @@ constexpr int HALO_TH = 8, HALO_TW = 32;
 constexpr int HALO_GROUPS = 43;                       // 8-pixel LDS-DMA groups per halo slice (344 >= 10*34 pixels)
 constexpr int HALO_BYTES = HALO_GROUPS * 8 * 128;     // 44,032
 constexpr int HALO_HL = 6;                            // halo LDS-DMA instructions per wave per slice (48 >= 43 groups)
+constexpr int HALO_STAGES = 4;                        // weight-ring depth
 
 template <int N> DEI2I_D void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -62,28 +59,26 @@ template <int N> DEI2I_D void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"
 // stats != nullptr: the epilogue also writes this tile's per-channel sum / sum of squares of the STORED (rounded) outputs,
 // record (n * tiles_per_image + tile) of a (N, tiles, 2, ldc) fp32 tensor -- the layout of moments_partial (reduce.hip),
 // so the BatchNorm / InstanceNorm finalize kernels read it unchanged and the separate statistics pass is gone.
-template <int BN, int STAGES, bool DIAG, bool M16, bool FP8 = false, bool PRO = false>
+template <int BN, bool FP8 = false, bool PRO = false>
 __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, const bf16_t* __restrict__ src,
                                                         const bf16_t* __restrict__ wgt, const int wrows,
                                                         const float* __restrict__ bias, bf16_t* __restrict__ out,
-                                                        const int ldc, const int act, const int tiles_n, const int ablate,
-                                                        unsigned long long* __restrict__ dbg,
+                                                        const int ldc, const int act, const int tiles_n,
                                                         const float* __restrict__ dequant, const ConvPro pro,
                                                         float* __restrict__ stats) {
-  static_assert(!FP8 || M16, "the fp8 variant uses the 16x16x32 shape");
-  static_assert(!PRO || (!FP8 && !DIAG), "operand-path normalisation: bf16 production variant only");
+  static_assert(!PRO || !FP8, "operand-path normalisation: bf16 variant only");
   constexpr int BM = HALO_TH * HALO_TW;             // 256 output pixels
-  constexpr int WN = 2, WTN = BN / WN, TM = 2, TN = WTN / 32;
+  constexpr int STAGES = HALO_STAGES;
+  constexpr int WN = 2, WTN = BN / WN, TM = 2;
   constexpr int LB = BN / 64;                       // weight LDS-DMA instructions per wave per stage
   constexpr int B_STAGE = BN * 128;
   constexpr int AHEAD = STAGES - 1;
   // A 3-deep ring was tried in the tile sweep: it ran 3 % faster and produced WRONG results in a fraction of the launches
-  // (tests/diag_ring_depth.py) -- with two wave groups in anti-phase a stage is re-issued while the trailing group can still
-  // be reading it.  4 is the minimum the schedule below is correct for.
-  static_assert(TN >= 1 && STAGES >= 4, "tile shape");
+  // -- with two wave groups in anti-phase a stage is re-issued while the trailing group can still be reading it.  4 is the
+  // minimum the schedule below is correct for.
+  static_assert((BN == 128 || BN == 64) && STAGES >= 4, "tile shape");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const unsigned long long kt0 = ablate == 5 ? __builtin_amdgcn_s_memtime() : 0ull;
   unsigned char* const halo = smem;
   unsigned char* const ring = smem + 2 * HALO_BYTES;
   int* const htab = reinterpret_cast<int*>(ring + STAGES * B_STAGE);
@@ -207,23 +202,22 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
     if (++is_tap == ntaps) { is_tap = 0; ++is_slice; }
   };
 
-  // MFMA shape: 32x32x16 (M16 = false) or 16x16x32 (M16 = true; same cycles per FLOP, but the chip holds a higher clock
-  // under it -- mfma_peak.hip: 2.26 vs 1.94 PF, 2.2 vs 1.9 GHz).  Both run the transposed product (A = weights,
-  // B = pixels): D[channel][pixel] leaves four consecutive channels of one pixel in consecutive registers.
-  constexpr int PB = M16 ? TM * 2 : TM;              // pixel blocks per wave (16 or 32 pixels each)
-  constexpr int CB = M16 ? WTN / 16 : TN;            // channel blocks per wave
-  constexpr int NKS = M16 ? 2 : 4;                   // MFMA k-blocks per 64-channel k-step
-  typedef __attribute__((ext_vector_type(M16 ? 4 : 16))) float acc_t;
+  // MFMA shape 16x16x32 (32x32x16 has the same cycles per FLOP, but the chip holds a higher clock under 16x16x32 --
+  // mfma_peak.hip: 2.26 vs 1.94 PF, 2.2 vs 1.9 GHz), transposed product (A = weights, B = pixels): D[channel][pixel]
+  // leaves four consecutive channels of one pixel in consecutive registers.
+  constexpr int PB = TM * 2;                         // 16-pixel blocks per wave
+  constexpr int CB = WTN / 16;                       // 16-channel blocks per wave
+  constexpr int NKS = 2;                             // MFMA k-blocks per 64-channel k-step
+  typedef __attribute__((ext_vector_type(4))) float acc_t;
   acc_t acc[PB][CB];
 #pragma unroll
   for (int i = 0; i < PB; ++i)
 #pragma unroll
     for (int j = 0; j < CB; ++j)
 #pragma unroll
-      for (int e = 0; e < (M16 ? 4 : 16); ++e) acc[i][j][e] = 0.f;
+      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
 
-  const int lr = lane & 31, lh = lane >> 5;          // 32x32x16 lane roles: row / k-half
-  const int l16 = lane & 15, kg = lane >> 4;         // 16x16x32 lane roles: row / k-group (8 channels each)
+  const int l16 = lane & 15, kg = lane >> 4;         // lane roles: row / k-group (8 channels each)
 
   // ---- fragment reads: ALL k-blocks of a k-step live in registers (Frags); the reads of k-step j are issued in this
   //      wave's M phase, its MFMAs in the C phase ----
@@ -231,11 +225,11 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
   int a_pix0[PB];                                    // halo pixel of this lane's pixel row for tap offset 0
 #pragma unroll
   for (int i = 0; i < PB; ++i)
-    a_pix0[i] = M16 ? (wm * TM + (i >> 1)) * hwd + (i & 1) * 16 + l16 : (wm * TM + i) * hwd + lr;
+    a_pix0[i] = (wm * TM + (i >> 1)) * hwd + (i & 1) * 16 + l16;
   int b_lane[CB], b_rsw[CB];
 #pragma unroll
   for (int j = 0; j < CB; ++j) {
-    const int row = M16 ? wn * WTN + j * 16 + l16 : wn * WTN + j * 32 + lr;
+    const int row = wn * WTN + j * 16 + l16;
     b_lane[j] = row * 128;
     b_rsw[j] = (row >> 1) & 7;
   }
@@ -269,7 +263,7 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
     if (++ld_stage == STAGES) ld_stage = 0;
   };
   auto read_frags = [&](Frags& f, int ks) {
-    const int chunk = M16 ? ks * 4 + kg : ks * 2 + lh;          // this lane's 16-byte chunk of the 128-byte k-row
+    const int chunk = ks * 4 + kg;                              // this lane's 16-byte chunk of the 128-byte k-row
 #pragma unroll
     for (int i = 0; i < PB; ++i) f.a[ks][i] = *reinterpret_cast<const u32x4*>(la_base[i] + ((chunk ^ la_swz[i]) << 4));
 #pragma unroll
@@ -286,12 +280,10 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
           const long a0 = (long)(((unsigned long long)aq.y << 32) | aq.x), a1 = (long)(((unsigned long long)aq.w << 32) | aq.z);
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b0, a0, acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b1, a1, acc[i][j], 0, 0, 0);
-        } else if constexpr (M16)
+        } else {
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f.b[ks][j]),
                                                                __builtin_bit_cast(bf16x8, f.a[ks][i]), acc[i][j], 0, 0, 0);
-        else
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.b[ks][j]),
-                                                               __builtin_bit_cast(bf16x8, f.a[ks][i]), acc[i][j], 0, 0, 0);
+        }
       }
   };
 
@@ -319,15 +311,7 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
   const int grp = wave >> 2;
   int tap = 0, slice = 0;                             // k-step of this wave's current M / C phase
   Frags f0, f1;
-  unsigned long long dg[6] = {0, 0, 0, 0, 0, 0};      // DIAG: cycles in [issue | reads issued | vmcnt | lgkmcnt | barrier M | C+barrier]
-  auto now = [&]() -> unsigned long long {
-    if (!DIAG) return 0ull;
-    const unsigned long long t = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    return t;
-  };
   auto phase_m = [&](Frags& f, int j) {
-    const unsigned long long q0 = now();
     prep_load();
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) read_frags(f, ks);
@@ -339,27 +323,19 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
       if (slice + 1 < nslices && tap >= 4 && tap <= 6) transform(slice + 1, (tap - 4) * 2, (tap - 4) * 2 + 2);
     }
     __builtin_amdgcn_sched_barrier(0);
-    const unsigned long long q2 = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
     // my share of weights(j+1) [issued in C(j-2)] must have landed; younger: weights(j+2) [C(j-1)] and the halo slice
     // C(j-1) issued at tap 1 (this k-step is then tap 2)
     const bool halo_young = tap == 2 && slice + 1 < nslices;
     if (j + 1 >= nk) wait_vm<0>();
     else if (j + 2 < nk) { if (halo_young) wait_vm<LB + HALO_HL>(); else wait_vm<LB>(); }
     else { if (halo_young) wait_vm<HALO_HL>(); else wait_vm<0>(); }
-    const unsigned long long q3 = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const unsigned long long q4 = now();
     __builtin_amdgcn_s_barrier();
-    if (DIAG) {
-      const unsigned long long q5 = now();
-      dg[1] += q2 - q0; dg[2] += q3 - q2; dg[3] += q4 - q3; dg[4] += q5 - q4;
-    }
   };
   // C(j): the 16 MFMAs, with this wave's LDS-DMA issue in the gaps (an MFMA holds the vector issue 8 of its 32 cycles;
   // a 16-byte-per-lane load instruction occupies the CU's address path ~64 cycles, the hard floor of this kernel:
   // 20.8 KB per k-step = 1 300 cycles)
   auto phase_c = [&](const Frags& f, int j) {
-    const unsigned long long q0 = now();
     mfma_group(f, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (j - 1 + STAGES < nk) issue_b((j + STAGES - 1) % STAGES);
@@ -370,12 +346,9 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
     for (int ks = 1; ks < NKS; ++ks) mfma_group(f, ks);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
-    if (DIAG) dg[5] += now() - q0;
     if (++tap == ntaps) { tap = 0; ++slice; }
   };
 
-  const unsigned long long st0 = ablate == 5 ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long sr0 = ablate == 5 ? __builtin_amdgcn_s_memrealtime() : 0ull;
   // prologue: halo slice 0 and weights(0 .. STAGES-2); weights(STAGES-1) is issued by C(0)
   issue_halo(0);
   for (int s2 = 0; s2 < STAGES - 1; ++s2)
@@ -402,19 +375,8 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
     phase_c(f1, j + 1);
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();            // pairs with group 1's last phase
-  if (ablate == 5 && dbg != nullptr && lane == 0) {      // diagnostic: loop cycles and the clock held
-    unsigned long long* d = dbg + ((size_t)blockIdx.x * 8 + wave) * 4;
-    d[0] = __builtin_amdgcn_s_memtime() - st0;
-    d[1] = __builtin_amdgcn_s_memrealtime() - sr0;
-    d[2] = (unsigned long long)nk;
-    d[3] = st0;
-    if (DIAG) {
-      unsigned long long* e = dbg + (size_t)gridDim.x * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 6;
-      for (int q = 0; q < 6; ++q) e[q] = dg[q];
-    }
-  }
 
-  // ---- epilogue: D row = channel (e&3) + 8(e>>2) + 4lh of the 32-block, col = pixel lr.  Stage the tile through LDS
+  // ---- epilogue: stage the tile through LDS
   //      as bf16 [pixel][BN (+8 pad)] with 8-byte writes (row stride 16*odd bytes: 2-way instead of 32-way conflicts),
   //      write back with 16-byte stores ----
   __syncthreads();
@@ -425,37 +387,19 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
   // per-element `act` switch this replaces was 60 % of the kernel's code, and a dispatch walks its code cold.
   const float slope = act_slope(act);
   const float dq = FP8 ? dequant[0] : 1.f;
-  if constexpr (M16) {
-    // D row = channel 4*kg + e of its 16-block, col = pixel l16
+  // D row = channel 4*kg + e of its 16-block, col = pixel l16
 #pragma unroll
-    for (int j = 0; j < CB; ++j) {
-      const int col0 = wn * WTN + j * 16 + 4 * kg;
-      float bq[4];
-      uint32_t m01, m23;
-      epi_col_consts(bias, n0 + col0, wrows, bq, m01, m23);
+  for (int j = 0; j < CB; ++j) {
+    const int col0 = wn * WTN + j * 16 + 4 * kg;
+    float bq[4];
+    uint32_t m01, m23;
+    epi_col_consts(bias, n0 + col0, wrows, bq, m01, m23);
 #pragma unroll
-      for (int i = 0; i < PB; ++i) {
-        const int row = (wm * TM + (i >> 1)) * 32 + (i & 1) * 16 + l16;
-        *reinterpret_cast<u32x2*>(ctile + row * CROW + col0 * 2) =
-            epi_finish4(acc[i][j][0] * dq, acc[i][j][1] * dq, acc[i][j][2] * dq, acc[i][j][3] * dq, bq, slope, m01, m23);
-      }
+    for (int i = 0; i < PB; ++i) {
+      const int row = (wm * TM + (i >> 1)) * 32 + (i & 1) * 16 + l16;
+      *reinterpret_cast<u32x2*>(ctile + row * CROW + col0 * 2) =
+          epi_finish4(acc[i][j][0] * dq, acc[i][j][1] * dq, acc[i][j][2] * dq, acc[i][j][3] * dq, bq, slope, m01, m23);
     }
-  } else {
-#pragma unroll
-    for (int j = 0; j < CB; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int col0 = wn * WTN + j * 32 + 8 * q + 4 * lh;             // first of this lane's four channels
-        float bq[4];
-        uint32_t m01, m23;
-        epi_col_consts(bias, n0 + col0, wrows, bq, m01, m23);
-#pragma unroll
-        for (int i = 0; i < PB; ++i) {
-          const int row = (wm * TM + i) * 32 + lr;
-          *reinterpret_cast<u32x2*>(ctile + row * CROW + col0 * 2) =
-              epi_finish4(acc[i][j][q * 4], acc[i][j][q * 4 + 1], acc[i][j][q * 4 + 2], acc[i][j][q * 4 + 3], bq, slope, m01, m23);
-        }
-      }
   }
   __syncthreads();
   constexpr int CPR = BN / 8;             // 16-byte chunks per tile row
@@ -499,33 +443,20 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
       if (c < ldc) stats[((size_t)tile_m * 2 + (k >> 3)) * ldc + c] = sum;
     }
   }
-  if (ablate == 5 && dbg != nullptr && lane == 0) {      // diagnostic: cycles from kernel entry to the last store issued
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    dbg[(size_t)gridDim.x * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 6] = __builtin_amdgcn_s_memtime() - kt0;
-  }
 }
 
-template <int BN, int STAGES, bool FULL = true>      // FULL = false: a sweep instance (tile-size report), default variant only
+template <int BN>
 static hipError_t launch_halo(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out,
-                              int ldc, int act, const float* dequant, hipStream_t st, const ConvPro* pro = nullptr,
-                              float* stats = nullptr) {
+                              int ldc, int act, const float* dequant, hipStream_t st, const ConvPro* pro, float* stats) {
   const int tiles_m = g.N * (g.Ho / HALO_TH) * (g.Wo / HALO_TW);
   const int tiles_n = (ldc + BN - 1) / BN;
-  const size_t lds = 2 * (size_t)HALO_BYTES + (size_t)STAGES * BN * 128 + HALO_GROUPS * 8 * sizeof(int) +
+  const size_t lds = 2 * (size_t)HALO_BYTES + (size_t)HALO_STAGES * BN * 128 + HALO_GROUPS * 8 * sizeof(int) +
                      (pro != nullptr ? 2 * (size_t)g.Cs * sizeof(float) : 0);
   if (lds > 160 * 1024) return hipErrorNotSupported;
-  auto kern = halo_conv_kernel<BN, STAGES, false, true>;
-  if constexpr (FULL) {
-    if (g_halo_mfma32) kern = halo_conv_kernel<BN, STAGES, false, false>;     // A/B option: 32x32x16 MFMAs
-    if (g_v2_ablate == 6) kern = halo_conv_kernel<BN, STAGES, true, true>;   // diagnostic build: per-phase cycle stamps
-    if (dequant != nullptr) kern = halo_conv_kernel<BN, STAGES, false, true, true>;   // e4m3 operands
-    if (pro != nullptr) {
-      if (dequant != nullptr) return hipErrorNotSupported;
-      kern = halo_conv_kernel<BN, STAGES, false, true, false, true>;           // operand-path normalisation
-    }
-  } else if (pro != nullptr) {
-    return hipErrorNotSupported;
-  }
+  if (dequant != nullptr && pro != nullptr) return hipErrorNotSupported;
+  auto kern = dequant != nullptr ? halo_conv_kernel<BN, true, false>           // e4m3 operands
+            : pro != nullptr     ? halo_conv_kernel<BN, false, true>           // operand-path normalisation
+                                 : halo_conv_kernel<BN, false, false>;
   const ConvPro pv = pro != nullptr ? *pro : ConvPro{nullptr, nullptr, 0, 0.f, nullptr, 0};
   {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -535,7 +466,7 @@ static hipError_t launch_halo(const GatherDesc& g, const void* src, const void* 
   count_launch(dequant != nullptr ? K_HALO_CONV_FP8 : K_HALO_CONV);
   prof_begin(PROF_HALO_CONV, (dequant != nullptr ? 4.0 : 2.0) * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows, st);
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias,
-                     (bf16_t*)out, ldc, act, tiles_n, g_v2_ablate == 6 ? 5 : g_v2_ablate, g_v2_dbg, dequant, pv, stats);
+                     (bf16_t*)out, ldc, act, tiles_n, dequant, pv, stats);
   prof_end(PROF_HALO_CONV, st);
   return hipGetLastError();
 }
@@ -552,26 +483,12 @@ hipError_t halo_conv(const GatherDesc& g, const void* src, const void* wgt, int 
   if (ldc < 64 || ldc % 8 != 0) return hipErrorNotSupported;
   const int tiles_m = g.N * (g.Ho / HALO_TH) * (g.Wo / HALO_TW);
   if (pro != nullptr && (g.Cs > 512 || (pro->ring != nullptr && (g.Hl < 4 || g.Wl < 4)))) return hipErrorNotSupported;
-  if (dequant == nullptr && pro == nullptr && stats == nullptr && (g_halo_bn != 0 || g_halo_stages != 0)) {
-    // tile-size sweep (options halo_bn / halo_stages; profiles/sweep_tiles.py): output-channel tile width x weight-ring
-    // depth.  LDS = 88,064 B of halo + STAGES x BN x 128 B of ring (+ the offset table): 128x4 = 153.6 KB is the
-    // largest 128-wide one that fits the 160 KB, 64-wide tiles leave room for rings up to 8 deep.
-    const int bn = (g_halo_bn == 64 || ldc < 128) ? 64 : 128;
-    int stg = g_halo_stages != 0 ? g_halo_stages : 4;
-    if (bn == 128 && stg > 4) stg = 4;          // deeper rings do not fit beside a 128-wide tile
-    if (tiles_m * ((ldc + bn - 1) / bn) < num_cu / 2) return hipErrorNotSupported;
-    if (bn == 128 && stg == 4) return launch_halo<128, 4>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st);
-    if (bn == 64 && stg == 4) return launch_halo<64, 4>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st);
-    if (bn == 64 && stg == 6) return launch_halo<64, 6, false>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st);
-    if (bn == 64 && stg == 8) return launch_halo<64, 8, false>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st);
-    return hipErrorInvalidValue;
-  }
   if (ldc >= 128) {
     if (tiles_m * ((ldc + 127) / 128) < num_cu / 2) return hipErrorNotSupported;   // small grids: split-K v1 fills the chip better
-    return launch_halo<128, 4>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st, pro, stats);
+    return launch_halo<128>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st, pro, stats);
   }
   if (tiles_m < num_cu / 2) return hipErrorNotSupported;
-  return launch_halo<64, 4>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st, pro, stats);
+  return launch_halo<64>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st, pro, stats);
 }
 
 }  // namespace dei2i

@@ -54,10 +54,9 @@ constexpr int H16_HL = 5;                             // halo LDS-DMA instructio
 template <int N> DEI2I_D void wait_vm16() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 template <int N> DEI2I_D void lgkm_wait() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
 // LDS reads the compiler does not track (no automatic s_waitcnt: every use needs a hand-placed lgkm_wait)
-template <int OFF, bool SKIP = false> DEI2I_D u32x4 lds_read128_asm(int addr) {
+template <int OFF> DEI2I_D u32x4 lds_read128_asm(int addr) {
   u32x4 v;
-  if constexpr (SKIP) asm volatile("; no read %0 %1" : "=v"(v) : "v"(addr));        // (timing-only ablation)
-  else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
   return v;
 }
 DEI2I_D int lds_read32_asm(int addr) {
@@ -104,9 +103,6 @@ DEI2I_D void reduce_rows16(float (&v)[NV], float* __restrict__ scratch, int tid,
   }
 }
 
-// DIAG: a diagnostic build (option "v2_ablate" = 6) that accumulates s_memtime stamps per wave into `dbg`:
-//   [0] loop cycles  [1] loop s_memrealtime ticks  [2] k-steps  [3] whole-kernel cycles
-//   [4] M: fragment reads issued  [5] M: vmcnt wait  [6] M: lgkmcnt wait  [7] M: barrier  [8] C: MFMA + DMA issue  [9] C: barrier
 // FOLD: this launch is the input gradient of a REFLECT-padded conv (architecture.py:51-56: pad 1).  The zero-boundary dgrad
 // on the input grid misses what the padded frame's ring (row -1 / H, column -1 / W) reflects back onto rows 1 / H-2 and
 // columns 1 / W-2 -- conv_api.hip computes that ring as a second small GEMM + split-K finalize + border fold (three
@@ -116,9 +112,6 @@ DEI2I_D void reduce_rows16(float (&v)[NV], float* __restrict__ scratch, int tid,
 // (waves wm = 0, 1), ring column -1 / W over the tile's 16 rows as one extra block of 16 rows x 1 column (waves wm = 2 /
 // 3); each is 4 extra MFMAs per wave in 3 of the 9 taps, accumulated apart and added to rows 1 / 14 or columns 1 / 30 of
 // the LDS-staged tile before it is written; the four frame CORNERS (one pixel each) are dot products in the epilogue.
-// DIAG 2 / 3 / 4: stamps + a TIMING-ONLY ablation (results are wrong): 2 = no LDS-DMA inside the loop, 3 = no fragment reads,
-// 4 = no MFMAs (options v2_ablate = 7 / 8 / 9)
-// ABL (options v2_ablate = 10 + ABL, no stamps): the same as a bit mask -- 1 no LDS-DMA in the loop, 2 no fragment reads, 4 no MFMAs
 // PIPE: the software-pipelined main loop (see there) instead of the two-phase one
 // EPIN: the epilogue also takes the backward reductions of the normalisation layer in front of this conv (geom.h: EpiNorm) from
 // the finished dz tile -- FOLD launches only (every conv of the generator is reflect-padded)
@@ -129,25 +122,17 @@ DEI2I_D void reduce_rows16(float (&v)[NV], float* __restrict__ scratch, int tid,
 // padding is in the table), its 4 taps read tap-shifted fragments exactly like the 3x3 kernel -- so the input is fetched ONCE per
 // tile and channel tile (the gather GEMM streams every input pixel four times, once per tap that reads it: 48 KB per k-step
 // against 8 KB of weights + 9 KB of halo here).  HBM layout and the packed weights ([Cout][4x4][CinS]) are the generic ones.
-template <int BN, int STAGES, int DIAG = 0, bool FOLD = false, int ABL = 0, bool PIPE = false, bool EPIN = false, bool S2 = false>
+template <int BN, int STAGES, bool FOLD = false, bool PIPE = false, bool EPIN = false, bool S2 = false>
 __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, const bf16_t* __restrict__ src,
                                                           const bf16_t* __restrict__ wgt, const int wrows,
                                                           const float* __restrict__ bias, bf16_t* __restrict__ out,
                                                           const int ldc, const int act, const int tiles_n,
-                                                          float* __restrict__ stats, unsigned long long* __restrict__ dbg,
-                                                          const bf16_t* __restrict__ zring, const int ring_pix,
+                                                          float* __restrict__ stats, const bf16_t* __restrict__ zring,
+                                                          const int ring_pix,
                                                           const EpiNorm en) {
   // zring (optional): the input tensor is the SOURCE-resolution z of a SPADE -> upsample -> conv block whose 2-pixel frame
   // (at the logical, upsampled resolution) has per-pixel gamma / beta classes: those halo pixels come from the compact
   // ring tensor [N][ring_pix][Cs] (geom.h) instead of from src[y >> up][x >> up]
-  const unsigned long long kt0 = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
-  unsigned long long dg[6] = {0, 0, 0, 0, 0, 0};
-  auto now = [&]() -> unsigned long long {
-    if (!DIAG) return 0ull;
-    const unsigned long long t = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    return t;
-  };
   constexpr int WTN = BN / 2;                         // channels per wave (2 waves along N)
   constexpr int PB = 8, CB = WTN / 16;                // 16-pixel blocks / 16-channel blocks per wave
   constexpr int B_STAGE = BN * 64;
@@ -172,7 +157,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
   const int y0 = (trem / tiles_x) * H16_TH, x0 = (trem % tiles_x) * H16_TW;
   const int n0 = tile_n * BN;
 
-  static_assert(!S2 || (!FOLD && !PIPE && !EPIN && DIAG == 0 && ABL == 0 && STAGES == 4), "the stride-2 form runs the two-phase loop on a 4-stage ring");
+  static_assert(!S2 || (!FOLD && !PIPE && !EPIN && STAGES == 4), "the stride-2 form runs the two-phase loop on a 4-stage ring");
   const int lth = S2 ? 2 : g.th, ltw = S2 ? 2 : g.tw;  // taps of the loop (S2: per parity plane)
   const int hwd = H16_TW + ltw - 1;                   // halo width in pixels
   const int npix = (H16_TH + lth - 1) * hwd;
@@ -341,13 +326,11 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
     if (++ld_stage == STAGES) ld_stage = 0;
   };
 
-  unsigned long long* drec = nullptr;
-  unsigned long long st0 = 0;
   if constexpr (PIPE) {
     // ---- main loop, software-pipelined (option "halo16" = 1): every wave runs MFMAs all the time -----------------------------
     // The anti-phase loop below gives a wave EITHER its 12 fragment reads OR its 32 MFMAs per phase; a DMA piece among the
     // MFMAs stalls the in-order wave ~100-300 cycles behind the other waves' pieces and the SIMD's matrix pipe idles with it
-    // (its partner wave is in a read phase).  Timing-only ablations of that loop, res-block shape, kernel wall: full 71.7 us |
+    // (its partner wave is in a read phase).  Timing-only ablations of that loop (DESIGN.md 5), res-block shape, kernel wall: full 71.7 us |
     // MFMA only 51.3 | reads only 40.9 | DMA only 35.8 | empty loop 18.0 -- the three streams run one after the other much more
     // than beside each other.  Here a k-step (one tap x 32 channels) is two halves of 16 MFMAs:
     //   H0(j): issue the reads of pixel rows 2,3 of k-step j                      | MFMAs of rows 0,1
@@ -380,21 +363,21 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       for (int r = 0; r < 2; ++r) {
         const int t = a_base[r0 + r] + soff;
         const int addr = t ^ ((t >> 3) & 32);
-        dst[2 * r] = lds_read128_asm<0, (ABL & 2) != 0>(addr);
-        dst[2 * r + 1] = lds_read128_asm<1024, (ABL & 2) != 0>(addr);
+        dst[2 * r] = lds_read128_asm<0>(addr);
+        dst[2 * r + 1] = lds_read128_asm<1024>(addr);
       }
     };
     const int b_addr0 = b_addr[0] + 2 * H16_HBYTES;     // (block jj sits 16 rows = 1024 bytes after block jj-1, same slot)
     auto read_b1 = [&](int jj, int stage) -> u32x4 {
       const int a = b_addr0 + stage * B_STAGE;
-      return jj == 0 ? lds_read128_asm<0, (ABL & 2) != 0>(a) : jj == 1 ? lds_read128_asm<1024, (ABL & 2) != 0>(a) : jj == 2 ? lds_read128_asm<2048, (ABL & 2) != 0>(a) : lds_read128_asm<3072, (ABL & 2) != 0>(a);
+      return jj == 0 ? lds_read128_asm<0>(a) : jj == 1 ? lds_read128_asm<1024>(a) : jj == 2 ? lds_read128_asm<2048>(a) : lds_read128_asm<3072>(a);
     };
     auto read_ring = [&](int t, int par) {              // FOLD: the ring block's fragment of loop tap t (read whether or not it is live)
       if constexpr (FOLD) {
         const int ty = t / 3, tx = t % 3;
         ring_live = (ring_kind == 1 && ty == 0) || (ring_kind == 2 && ty == 2) || (ring_kind == 3 && tx == 0) || (ring_kind == 4 && tx == 2);
         const int pix = ring_live ? ring_pix0 + (tap_off(t) >> 6) : 0;
-        ring_frag = lds_read128_asm<0, (ABL & 2) != 0>(par + pix * 64 + ((kg ^ sw16(pix)) << 4));
+        ring_frag = lds_read128_asm<0>(par + pix * 64 + ((kg ^ sw16(pix)) << 4));
       }
     };
     // (the opaque asm statements below keep per-tap copies of loop-invariant addresses -- 9 weight pointers, 5 table
@@ -431,22 +414,13 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
     };
     // 4 MFMAs: pixel blocks a[0..3] (accumulators i0..i0+3) x channel block jj
     auto mfma4 = [&](const u32x4* a, int i0, int jj) {
-      if constexpr (!(ABL & 4)) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-          acc[i0 + i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bc[jj]), __builtin_bit_cast(bf16x8, a[i]),
-                                                                    acc[i0 + i][jj], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(a[i]));
-        asm volatile("" ::"v"(bc[jj]));
-      }
+      for (int i = 0; i < 4; ++i)
+        acc[i0 + i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bc[jj]), __builtin_bit_cast(bf16x8, a[i]),
+                                                                  acc[i0 + i][jj], 0, 0, 0);
     };
     constexpr int NF = FOLD ? 1 : 0;
 
-    // (cycle count of the loop for every build of this path, when a debug buffer is set: tools/diag_halo16_stamps.py)
-    st0 = dbg != nullptr ? __builtin_amdgcn_s_memtime() : 0ull;
-    const unsigned long long sr0p = dbg != nullptr ? __builtin_amdgcn_s_memrealtime() : 0ull;
     // prologue: halo slice 0 and weights(0..6); halo 0, weights(0) and weights(1) landed (waves 4-7 read stage 1 in H1(0))
     {
       int po[H16_HL];
@@ -470,7 +444,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
     auto read_a1 = [&](u32x4* dst, int r0, int q, int soff) {      // q = 2 * r + c
       const int t = a_base[r0 + (q >> 1)] + soff;
       const int addr = t ^ ((t >> 3) & 32);
-      dst[q] = (q & 1) ? lds_read128_asm<1024, (ABL & 2) != 0>(addr) : lds_read128_asm<0, (ABL & 2) != 0>(addr);
+      dst[q] = (q & 1) ? lds_read128_asm<1024>(addr) : lds_read128_asm<0>(addr);
     };
     auto kstep = [&](auto tap_c, int sl) {
       constexpr int T = decltype(tap_c)::value;
@@ -485,12 +459,10 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       // ---- H0(j): rows 0,1 multiply (groups by channel block jj), rows 2,3 of this k-step are fetched
       read_a1(ah, 2, 0, soff);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (!(ABL & 16)) lgkm_wait<2>();          // all of al', ring' and bc'[0..2] are in; bc'[3] and ah0 may be in flight
+      lgkm_wait<2>();                                     // all of al', ring' and bc'[0..2] are in; bc'[3] and ah0 may be in flight
 #pragma unroll
       for (int jj = 0; jj < CB; ++jj) {
-        if (jj == CB - 1) {
-          if constexpr (!(ABL & 16)) lgkm_wait<4>();      // bc'[3] is in (ah0..3 may be in flight)
-        }
+        if (jj == CB - 1) lgkm_wait<4>();                 // bc'[3] is in (ah0..3 may be in flight)
         __builtin_amdgcn_sched_barrier(0);
         mfma4(al, 0, jj);
         if constexpr (FOLD) {
@@ -503,15 +475,13 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
         __builtin_amdgcn_sched_barrier(0);
       }
       if (grp == 0) {
-        if constexpr (!(ABL & 1)) {
-          constexpr int NH = T == 7 ? 3 : 4 + (T == 0 ? 0 : T == 1 ? 1 : T == 2 ? 2 : T == 3 ? 3 : T == 4 ? 4 : T == 5 ? 4 : T == 6 ? 3 : 1);
-          if (j + STAGES - 2 >= nk) wait_vm16<0>();
-          else if (has_halo) wait_vm16<NH>();
-          else wait_vm16<4>();
-        }
+        constexpr int NH = T == 7 ? 3 : 4 + (T == 0 ? 0 : T == 1 ? 1 : T == 2 ? 2 : T == 3 ? 3 : T == 4 ? 4 : T == 5 ? 4 : T == 6 ? 3 : 1);
+        if (j + STAGES - 2 >= nk) wait_vm16<0>();
+        else if (has_halo) wait_vm16<NH>();
+        else wait_vm16<4>();
         // (tap 8: these were the last reads of this slice's halo buffer, which the DMA refills after the next barrier)
-        if constexpr (T == 8 && !(ABL & 16)) lgkm_wait<0>();
-        if constexpr (!(ABL & 8)) __builtin_amdgcn_s_barrier();
+        if constexpr (T == 8) lgkm_wait<0>();
+        __builtin_amdgcn_s_barrier();
       }
       __builtin_amdgcn_sched_barrier(0);
       // ---- H1(j): rows 2,3 multiply; rows 0,1 of k-step j+1 are fetched, and its weight block jj as soon as this k-step's
@@ -526,7 +496,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       read_a1(al, 0, 0, soff_n);
       read_a1(al, 0, 1, soff_n);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (!(ABL & 16)) lgkm_wait<NP + 2>();     // ah0..3 are in
+      lgkm_wait<NP + 2>();                                // ah0..3 are in
 #pragma unroll
       for (int jj = 0; jj < CB; ++jj) {
         __builtin_amdgcn_sched_barrier(0);
@@ -538,26 +508,22 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
         if (jj == 2) read_ring(TN, par_n);
         __builtin_amdgcn_sched_barrier(0);
         if (jj == 0) {
-          if constexpr (!(ABL & 1)) {
-            if constexpr (NP) {
-              if constexpr (!(ABL & 16)) lgkm_wait<4>();  // the piece offset (oldest of this half's reads) is in
-              if (has_halo) issue_halo_piece(sl + 1, T, piece_off);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            constexpr int TW = (T + STAGES - 1) % 9, DS = (T + STAGES - 1) / 9;
-            if (sl + DS < nslices) issue_w(TW, sl + DS, (j + STAGES - 1) & (STAGES - 1));
+          if constexpr (NP) {
+            lgkm_wait<4>();                               // the piece offset (oldest of this half's reads) is in
+            if (has_halo) issue_halo_piece(sl + 1, T, piece_off);
           }
+          __builtin_amdgcn_sched_barrier(0);
+          constexpr int TW = (T + STAGES - 1) % 9, DS = (T + STAGES - 1) / 9;
+          if (sl + DS < nslices) issue_w(TW, sl + DS, (j + STAGES - 1) & (STAGES - 1));
           __builtin_amdgcn_sched_barrier(0);
         }
       }
       if (grp == 1) {
-        if constexpr (!(ABL & 1)) {
-          constexpr int NH = T == 7 ? 4 : 5 + (T == 0 ? 1 : T == 1 ? 2 : T == 2 ? 3 : T == 3 ? 4 : T == 4 ? 5 : T == 5 ? 4 : T == 6 ? 3 : 1);
-          if (j + STAGES - 1 >= nk) wait_vm16<0>();
-          else if (has_halo) wait_vm16<NH>();
-          else wait_vm16<5>();
-        }
-        if constexpr (!(ABL & 8)) __builtin_amdgcn_s_barrier();
+        constexpr int NH = T == 7 ? 4 : 5 + (T == 0 ? 1 : T == 1 ? 2 : T == 2 ? 3 : T == 3 ? 4 : T == 4 ? 5 : T == 5 ? 4 : T == 6 ? 3 : 1);
+        if (j + STAGES - 1 >= nk) wait_vm16<0>();
+        else if (has_halo) wait_vm16<NH>();
+        else wait_vm16<5>();
+        __builtin_amdgcn_s_barrier();
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -579,12 +545,6 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       lgkm_wait<0>();
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (dbg != nullptr && lane == 0) {
-      unsigned long long* rec = dbg + ((size_t)blockIdx.x * 8 + wave) * 10;
-      rec[0] = __builtin_amdgcn_s_memtime() - st0;
-      rec[1] = __builtin_amdgcn_s_memrealtime() - sr0p;
-      rec[2] = (unsigned long long)nk;
-    }
   } else {
     // ---- main loop: two wave groups in anti-phase (see conv_halo.hip) ----
     //   M(j) reads its fragments, then issues weights(j-2+STAGES) into stage (j-2) % STAGES (last read by the trailing group's
@@ -597,10 +557,6 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
     const int grp = wave >> 2;
     int tap = 0, slice = 0;                              // k-step of this wave's current M / C phase
     Frags f;
-    if constexpr (DIAG == 3 || (ABL & 2)) {
-      read_frags(f);
-      ld_tx = 0; ld_ty = 0; ld_slice = 0; ld_stage = 0; ld_toff = toff_origin;
-    }
     // DMA slot of k-step jj: weights(jj-2+STAGES) and, when k-step jj is tap 2 of its slice, the next slice's halo.  It sits
     // after the first 8 MFMAs of C(jj-1).  Measured alternatives (same box, res-block shape, kernel wall 69.4-70.7 us as is):
     // the slot in M(jj) after the fragment reads 74.5-75.9 us, before them 77.0-77.5, weights in M / halo in C 72.9-73.3, half
@@ -613,58 +569,35 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       if (tap2 && slice + 1 < nslices) issue_halo(slice + 1);
     };
     auto phase_m = [&](int j) {
-      const unsigned long long q0 = now();
-      if constexpr (DIAG != 3 && !(ABL & 2)) read_frags(f);
+      read_frags(f);
       __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long q1 = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
       // the next slice's halo went out in C(tap 1): while it is younger than weights(j+1) it may stay in flight -- but not at the
       // slice's last tap, whose barrier is the last one before M(next slice, tap 0) reads it (short tap grids: S2)
       const bool halo_young = tap >= 2 && tap <= STAGES - 1 && tap <= ntaps - 2 && slice + 1 < nslices;
-      if constexpr (DIAG != 2 && !(ABL & 1)) {
-        if (j + STAGES - 2 >= nk) wait_vm16<0>();
-        else if (halo_young) wait_vm16<(STAGES - 3) * LB + H16_HL>();
-        else wait_vm16<(STAGES - 3) * LB>();
-      }
-      const unsigned long long q2 = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
+      if (j + STAGES - 2 >= nk) wait_vm16<0>();
+      else if (halo_young) wait_vm16<(STAGES - 3) * LB + H16_HL>();
+      else wait_vm16<(STAGES - 3) * LB>();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const unsigned long long q3 = now();
       __builtin_amdgcn_s_barrier();
-      if (DIAG) {
-        const unsigned long long q4 = now();
-        dg[0] += q1 - q0; dg[1] += q2 - q1; dg[2] += q3 - q2; dg[3] += q4 - q3;
-      }
     };
     auto phase_c = [&](int j) {
-      const unsigned long long q0 = now();
-      if constexpr (DIAG != 4 && !(ABL & 4)) {
   #pragma unroll
-        for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < 2; ++i)
   #pragma unroll
-          for (int jj = 0; jj < CB; ++jj)
-            acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f.b[jj]), __builtin_bit_cast(bf16x8, f.a[i]),
-                                                                 acc[i][jj], 0, 0, 0);
-      }
+        for (int jj = 0; jj < CB; ++jj)
+          acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f.b[jj]), __builtin_bit_cast(bf16x8, f.a[i]),
+                                                               acc[i][jj], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (DIAG != 2 && !(ABL & 1)) {
-        slot_w(j + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        slot_h(tap == 1);
-      }
+      slot_w(j + 1);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (DIAG != 4 && !(ABL & 4)) {
+      slot_h(tap == 1);
+      __builtin_amdgcn_sched_barrier(0);
   #pragma unroll
-        for (int i = 2; i < PB; ++i)
+      for (int i = 2; i < PB; ++i)
   #pragma unroll
-          for (int jj = 0; jj < CB; ++jj)
-            acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f.b[jj]), __builtin_bit_cast(bf16x8, f.a[i]),
-                                                                 acc[i][jj], 0, 0, 0);
-      } else {
-        // keep the fragments live so that the reads are not removed
-  #pragma unroll
-        for (int i = 0; i < PB; ++i) asm volatile("" ::"v"(f.a[i]));
-  #pragma unroll
-        for (int jj = 0; jj < CB; ++jj) asm volatile("" ::"v"(f.b[jj]));
-      }
+        for (int jj = 0; jj < CB; ++jj)
+          acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f.b[jj]), __builtin_bit_cast(bf16x8, f.a[i]),
+                                                               acc[i][jj], 0, 0, 0);
       if constexpr (FOLD) {
         if (ring_live) {
   #pragma unroll
@@ -674,17 +607,10 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long q1 = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
       __builtin_amdgcn_s_barrier();
-      if (DIAG) {
-        const unsigned long long q2 = now();
-        dg[4] += q1 - q0; dg[5] += q2 - q1;
-      }
       if (++tap == ntaps) { tap = 0; ++slice; }
     };
 
-    st0 = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
-    const unsigned long long sr0 = DIAG ? __builtin_amdgcn_s_memrealtime() : 0ull;
     // prologue: halo slice 0 and weights(0 .. STAGES-3); weights(STAGES-2) is issued by M(0).  nk >= 9 > STAGES-1.
     issue_halo(0);
     for (int s2 = 0; s2 < STAGES - 2; ++s2) issue_b(s2);
@@ -698,14 +624,6 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       phase_c(j);
     }
     if (grp == 0) __builtin_amdgcn_s_barrier();           // pairs with group 1's last phase
-    if (DIAG && dbg != nullptr && lane == 0) {
-      drec = dbg + ((size_t)blockIdx.x * 8 + wave) * 10;
-      drec[0] = __builtin_amdgcn_s_memtime() - st0;
-      drec[1] = __builtin_amdgcn_s_memrealtime() - sr0;
-      drec[2] = (unsigned long long)nk;
-      for (int q = 0; q < 6; ++q) drec[4 + q] = dg[q];
-    }
-
   }
 
   // ---- epilogue: the whole 16 x 32 tile is staged as bf16 [pixel][BN (+8 pad)] (8-byte writes: a lane holds 4 consecutive
@@ -737,7 +655,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
         const f32x4 lo = *reinterpret_cast<const f32x4*>(q), hi = *reinterpret_cast<const f32x4*>(q + 4);
         d[0] = f32x2{lo.x, lo.y}; d[1] = f32x2{lo.z, lo.w}; d[2] = f32x2{hi.x, hi.y}; d[3] = f32x2{hi.z, hi.w};
       };
-      if ((en.kind & 0xff) == 1) {
+      if (en.kind == 1) {
         ld8(en.mean + (size_t)img * ldc + ncol, nc[0]);
         ld8(en.rstd + (size_t)img * ldc + ncol, nc[1]);
         const bf16_t* gp = en.gb + ((size_t)(img * 5 + 2) * 5 + 2) * 2 * ldc + ncol;
@@ -866,11 +784,10 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
         }
         if constexpr (EPIN) {
           // v = dL/dz of 8 channels of pixel (py, px), as the streaming pass would read it back (bf16): the same per-element
-          // arithmetic as spade_bwd_partial_kernel / bn_bwd_partial_kernel (reduce.hip), on channel PAIRS (v_pk_*_f32)
+          // arithmetic as spade_bwd_partial_kernel / bn_bwd_partial_kernel (reduce.hip), on channel PAIRS (v_pk_*_f32).  The sums
+          // that add a product are written as FMAs: the contraction the compiler would pick for `+=` depends on the branches around it
           const uint32_t dw[4] = {v.x, v.y, v.z, v.w}, xw[4] = {xq[p].x, xq[p].y, xq[p].z, xq[p].w};
-          if (en.kind & 0x100) {                         // (timing only, tools/diag_epin.py: no arithmetic -- the loads stay live)
-            ep[0][0] += bf16x2_unpack(xw[0]) + bf16x2_unpack(dw[0]);
-          } else if ((en.kind & 0xff) == 1) {
+          if (en.kind == 1) {
             const int cy = border_class(py, g.Ho), cx = border_class(px, g.Wo);
             const bool interior = cy == 2 && cx == 2;
             u32x4 gq = gmi, bq2 = bti;                   // the interior class (kept in registers); the frame's pixels fetch theirs
@@ -890,19 +807,20 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
               const f32x2 z = __builtin_elementwise_fma(xh, g1, bf16x2_unpack(bw[e]));
               const f32x2 gg = {z.x > 0.f ? d2.x : 0.f, z.y > 0.f ? d2.y : 0.f};
               const f32x2 dxh = gg * g1;
-              ep[0][e] += dxh;
+              ep[0][e] = __builtin_elementwise_fma(gg, g1, ep[0][e]);
               ep[1][e] = __builtin_elementwise_fma(dxh, xh, ep[1][e]);
               const f32x2 gi = gg * inm2;
               ep[2][e] = __builtin_elementwise_fma(gi, xh, ep[2][e]);
-              ep[3][e] += gi;
+              ep[3][e] = __builtin_elementwise_fma(gg, inm2, ep[3][e]);
             }
           } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const f32x2 x2 = bf16x2_unpack(xw[e]);
               const f32x2 zz = __builtin_elementwise_fma(nc[0][e], x2, nc[1][e]);
-              const f32x2 gg = bf16x2_unpack(dw[e]) * f32x2{act_grad_from_out(zz.x, en.act), act_grad_from_out(zz.y, en.act)};
-              ep[0][e] += gg;
+              const f32x2 d2 = bf16x2_unpack(dw[e]), ag = {act_grad_from_out(zz.x, en.act), act_grad_from_out(zz.y, en.act)};
+              const f32x2 gg = d2 * ag;
+              ep[0][e] = __builtin_elementwise_fma(d2, ag, ep[0][e]);
               ep[1][e] = __builtin_elementwise_fma(gg, (x2 - nc[2][e]) * nc[3][e], ep[1][e]);
             }
           }
@@ -925,22 +843,16 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
     }
   }
   if constexpr (EPIN) {
-    const int nq = (en.kind & 0xff) == 1 ? 4 : 2;
-    if (!(en.kind & 0x200)) {                            // (0x200: timing only, no reduction)
-      float* const prow = en.partial + (size_t)(img * (tiles_y * tiles_x) + trem) * nq * ldc;
-      float flat[32];
+    const int nq = en.kind == 1 ? 4 : 2;
+    float* const prow = en.partial + (size_t)(img * (tiles_y * tiles_x) + trem) * nq * ldc;
+    float flat[32];
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
+    for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { flat[q * 8 + 2 * k] = ep[q][k].x; flat[q * 8 + 2 * k + 1] = ep[q][k].y; }
-      reduce_rows16<32, CPR>(flat, rscr, tid, [&](int q, int c, float sum) {
-        if (q < nq && n0 + c < ldc) prow[(size_t)q * ldc + n0 + c] = sum;
-      });
-    }
-  }
-  if (DIAG && drec != nullptr) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    drec[3] = (__builtin_amdgcn_s_memtime() - kt0) | ((st0 - kt0) << 32);     // whole kernel | prologue (cycles)
+      for (int k = 0; k < 4; ++k) { flat[q * 8 + 2 * k] = ep[q][k].x; flat[q * 8 + 2 * k + 1] = ep[q][k].y; }
+    reduce_rows16<32, CPR>(flat, rscr, tid, [&](int q, int c, float sum) {
+      if (q < nq && n0 + c < ldc) prow[(size_t)q * ldc + n0 + c] = sum;
+    });
   }
 }
 
@@ -948,117 +860,49 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
 //  built and measured in round 2: equal to or slower than the eight-wave two-phase loop (108 us on the res-block shape with the
 //  DMA pieces staggered per wave, ~equal without): one wave per SIMD has nobody to cover its stalls.  Removed)
 
-extern int g_v2_ablate;
-extern unsigned long long* g_v2_dbg;
-extern int g_halo_bn, g_halo_stages;
-int g_halo16 = 3;
-int g_halo16_fold = 1;         // A/B option "halo16_fold": 0 = ring GEMM + finalize + border fold as separate launches              // A/B option "halo16": 0 = always the 8 x 32 tile kernel (conv_halo.hip)
-int g_halo16_stages = 8;
+int g_halo16 = 1;              // A/B option "halo16": 0 = always the 8 x 32 tile kernel (conv_halo.hip)
+int g_halo16_fold = 1;         // A/B option "halo16_fold": 0 = ring GEMM + finalize + border fold as separate launches
 
-template <int BN, int STAGES>
-static hipError_t launch_halo16(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out,
-                                int ldc, int act, hipStream_t st, float* stats, const void* ring = nullptr, bool fold = false,
-                                const EpiNorm* en = nullptr, bool s2 = false) {
-  const int tiles_m = g.N * (g.Ho / H16_TH) * (g.Wo / H16_TW);
-  const int tiles_n = (ldc + BN - 1) / BN;
-  if (s2) {                                             // the 4x4 stride-2 form: two-phase loop, 4-stage weight ring
-    if constexpr (STAGES == 4) {
-      constexpr size_t lds2 = std::max(2 * (size_t)H16_HBYTES + 4 * (size_t)BN * 64 + 4 * H16_GROUPS * 16 * sizeof(int),
-                                       2 * 256 * (size_t)(BN * 2 + 16) + 4 * BN * sizeof(float) + 8 * (BN / 8) * 32 * sizeof(float));
-      auto k2 = halo16_conv_kernel<BN, 4, 0, false, 0, false, false, true>;
-      static bool attr2 = false;
-      if (!attr2) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        if (e != hipSuccess) return e;
-        attr2 = true;
-      }
-      count_launch(K_HALO16_S2);
-      prof_begin(PROF_GATHER_GEMM, 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows, st);
-      hipLaunchKernelGGL(k2, dim3(tiles_m * tiles_n), dim3(512), lds2, st, g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias,
-                         (bf16_t*)out, ldc, act, tiles_n, stats, (unsigned long long*)nullptr, (const bf16_t*)nullptr, 0, EpiNorm{});
-      prof_end(PROF_GATHER_GEMM, st);
-      return hipGetLastError();
-    }
-    return hipErrorNotSupported;
-  }
+// one instance of the kernel; its dynamic LDS limit is raised on its first launch
+template <int BN, int STAGES, bool FOLD, bool PIPE, bool EPIN, bool S2>
+static hipError_t launch_halo16_kernel(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out,
+                                       int ldc, int act, hipStream_t st, float* stats, const void* ring, const EpiNorm* en) {
   constexpr size_t loop_lds = 2 * (size_t)H16_HBYTES + (size_t)STAGES * BN * 64 + 4 * H16_GROUPS * 16 * sizeof(int);   // (4 tables: S2)
   constexpr size_t epi_lds = 2 * 256 * (size_t)(BN * 2 + 16) + 4 * BN * sizeof(float) + 8 * (BN / 8) * 32 * sizeof(float);   // tile | corners | reduce scratch
-  const size_t lds = std::max(loop_lds, epi_lds);
-  const bool diag = g_v2_ablate >= 6 && g_v2_ablate <= 9 && g_v2_dbg != nullptr && STAGES == 8 && !fold;
-  constexpr bool S8 = STAGES == 8 && BN == 128;   // the diagnostic builds exist for the shipped ring depth and the 128-channel tile only
-  auto kern = halo16_conv_kernel<BN, STAGES, 0>;
-  if (diag && S8) {
-    kern = g_v2_ablate == 6 ? halo16_conv_kernel<BN, STAGES, S8 ? 1 : 0> : g_v2_ablate == 7 ? halo16_conv_kernel<BN, STAGES, S8 ? 2 : 0>
-         : g_v2_ablate == 8 ? halo16_conv_kernel<BN, STAGES, S8 ? 3 : 0> : halo16_conv_kernel<BN, STAGES, S8 ? 4 : 0>;
-  }
-  // (the FOLD build of the pipelined loop needs 20 more registers -- ring accumulators and fragment -- than a wave has: it
-  //  spills inside the loop, and a scratch reload drains the LDS-DMA queue.  Those launches keep the two-phase loop.)
-  // (and its read schedule and wait counts are written for 4 channel blocks per wave: the 64-channel tile keeps the two-phase loop too)
-  const bool pipe = g_halo16 == 3 && STAGES == 8 && BN == 128 && !fold;
-  if (pipe) {
-    constexpr bool P8 = STAGES == 8 && BN == 128;
-    kern = halo16_conv_kernel<BN, STAGES, 0, false, 0, P8>;
-    if (!fold && BN == 128 && g_v2_ablate > 20 && g_v2_ablate <= 51) {
-      constexpr bool Q = P8 && BN == 128;
-      switch (g_v2_ablate - 20) {
-        case 8: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 8 : 0, Q>; break;
-        case 16: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 16 : 0, Q>; break;
-        case 24: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 24 : 0, Q>; break;
-        case 12: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 12 : 0, Q>; break;
-        case 9: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 9 : 0, Q>; break;
-        case 25: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 25 : 0, Q>; break;
-        case 27: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 27 : 0, Q>; break;
-        case 26: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 26 : 0, Q>; break;
-        case 2: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 2 : 0, Q>; break;
-        case 31: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 31 : 0, Q>; break;
-        case 1: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 1 : 0, Q>; break;
-        case 4: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 4 : 0, Q>; break;
-        case 5: kern = halo16_conv_kernel<BN, STAGES, 0, false, Q ? 5 : 0, Q>; break;
-        default: break;
-      }
-    }
-    static const void* attr_set[16] = {};               // (per template instance of this launcher: the kernels it has prepared)
-    bool seen = false;
-    for (const void* q : attr_set) seen = seen || q == reinterpret_cast<const void*>(kern);
-    if (!seen) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      for (const void*& q : attr_set)
-        if (q == nullptr) { q = reinterpret_cast<const void*>(kern); break; }
-    }
-  }
-  const bool abl = !pipe && g_v2_ablate > 10 && g_v2_ablate <= 17 && S8 && !fold;
-  if (abl) {
-    switch (g_v2_ablate - 10) {
-      case 1: kern = halo16_conv_kernel<BN, STAGES, 0, false, S8 ? 1 : 0>; break;
-      case 2: kern = halo16_conv_kernel<BN, STAGES, 0, false, S8 ? 2 : 0>; break;
-      case 3: kern = halo16_conv_kernel<BN, STAGES, 0, false, S8 ? 3 : 0>; break;
-      case 4: kern = halo16_conv_kernel<BN, STAGES, 0, false, S8 ? 4 : 0>; break;
-      case 5: kern = halo16_conv_kernel<BN, STAGES, 0, false, S8 ? 5 : 0>; break;
-      case 6: kern = halo16_conv_kernel<BN, STAGES, 0, false, S8 ? 6 : 0>; break;
-      default: kern = halo16_conv_kernel<BN, STAGES, 0, false, S8 ? 7 : 0>; break;
-    }
-  }
-  if (fold && !pipe) kern = halo16_conv_kernel<BN, STAGES, 0, STAGES == 8>;   // (instantiated for the shipped ring depth only)
-  if (fold && !pipe && en != nullptr) kern = halo16_conv_kernel<BN, STAGES, 0, STAGES == 8, 0, false, STAGES == 8>;
-  if ((fold && STAGES != 8) || (en != nullptr && !fold)) return hipErrorNotSupported;
-  static bool attr_done[16] = {};
-  const int which = fold ? (en != nullptr ? 15 : 2) : (abl ? 7 + (g_v2_ablate - 10) : (diag && S8 ? g_v2_ablate - 3 : 0));
-  if (!pipe && !attr_done[which]) {
+  constexpr size_t lds = std::max(loop_lds, epi_lds);
+  auto kern = halo16_conv_kernel<BN, STAGES, FOLD, PIPE, EPIN, S2>;
+  static bool attr_set = false;
+  if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    attr_done[which] = true;
+    attr_set = true;
   }
-  count_launch(K_HALO16_CONV);
+  count_launch(S2 ? K_HALO16_S2 : K_HALO16_CONV);
   // (profiling families: the pipelined forward instance is a kernel of its own -- bench.py's roofline line --, the FOLD launches
-  //  are another, the 64-channel tile counts with the other conv kernels)
-  const ProfFamily fam = fold ? PROF_HALO_FOLD : (pipe ? PROF_HALO_CONV : PROF_GATHER_GEMM);
+  //  are another, the 64-channel tile and the stride-2 form count with the other conv kernels)
+  const ProfFamily fam = FOLD ? PROF_HALO_FOLD : (PIPE ? PROF_HALO_CONV : PROF_GATHER_GEMM);
   prof_begin(fam, 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows, st);
+  const int tiles_m = g.N * (g.Ho / H16_TH) * (g.Wo / H16_TW);
+  const int tiles_n = (ldc + BN - 1) / BN;
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias,
-                     (bf16_t*)out, ldc, act, tiles_n, stats, g_v2_dbg, (const bf16_t*)ring,
+                     (bf16_t*)out, ldc, act, tiles_n, stats, (const bf16_t*)ring,
                      ring != nullptr ? ring_pixels(g.Hl, g.Wl) : 0, en != nullptr ? *en : EpiNorm{});
   prof_end(fam, st);
   return hipGetLastError();
+}
+
+// the 3x3 forms, all on the 8-deep weight ring: FOLD (+ EPIN) launches and the 64-channel tile run the two-phase loop, the
+// 128-channel forward and zero-boundary dgrad the pipelined one
+// (the FOLD build of the pipelined loop needs 20 more registers -- ring accumulators and fragment -- than a wave has: it
+//  spills inside the loop, and a scratch reload drains the LDS-DMA queue.  Those launches keep the two-phase loop.)
+// (and its read schedule and wait counts are written for 4 channel blocks per wave: the 64-channel tile keeps the two-phase loop too)
+template <int BN>
+static hipError_t launch_halo16(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out,
+                                int ldc, int act, hipStream_t st, float* stats, const void* ring, bool fold, const EpiNorm* en) {
+  if (fold && en != nullptr)
+    return launch_halo16_kernel<BN, 8, true, false, true, false>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, en);
+  if (fold) return launch_halo16_kernel<BN, 8, true, false, false, false>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, en);
+  return launch_halo16_kernel<BN, 8, false, BN == 128, false, false>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, en);
 }
 
 // returns hipErrorNotSupported when the shape does not qualify (the caller goes on to the 8 x 32 tile kernel)
@@ -1073,7 +917,7 @@ int g_halo16_s2 = 1;           // A/B option "halo16_s2": 0 = the 4x4 stride-2 c
 // moves 8 KB of weights + 9 KB of halo (a plane's halo serves 4 taps, the 3x3 kernel's 9), and the gather GEMM's 128-channel
 // k-steps are twice as efficient as its 64-channel ones -- so only the 64-channel inputs are taken.
 bool halo16_s2_shape_ok(const GatherDesc& g, int ldc, int num_cu) {
-  if (!g_halo16_s2 || !g_halo16 || g_halo_bn != 0 || g_halo_stages != 0) return false;
+  if (!g_halo16_s2 || !g_halo16) return false;
   if (g.sh != 2 || g.sw != 2 || g.th != 4 || g.tw != 4 || g.ys != 1 || g.xs != 1 || g.by0 != -1 || g.bx0 != -1 || g.up || g.wK != g.K || g.wtw != 4) return false;
   if (g.Cs != 64 && g_halo16_s2 != 2) return false;                                        // (option value 2: every channel count, for A/B)
   if (g.Cs % 32 != 0 || g.Cs < 64 || g.Ho % H16_TH != 0 || g.Wo % H16_TW != 0 || g.M != g.N * g.Ho * g.Wo || !g.out_identity) return false;
@@ -1087,18 +931,19 @@ bool halo16_s2_shape_ok(const GatherDesc& g, int ldc, int num_cu) {
 static hipError_t halo16_conv_s2(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out,
                                  int ldc, int act, int num_cu, hipStream_t st, float* stats) {
   if (!halo16_s2_shape_ok(g, ldc, num_cu)) return hipErrorNotSupported;
-  return launch_halo16<128, 4>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, nullptr, false, nullptr, true);
+  // the 4x4 stride-2 form: two-phase loop, 4-stage weight ring
+  return launch_halo16_kernel<128, 4, false, false, false, true>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, nullptr, nullptr);
 }
 
 hipError_t halo16_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
                        int act, int num_cu, hipStream_t st, float* stats, const void* ring, bool fold, const EpiNorm* en) {
   if (g.sh == 2 && g.sw == 2 && !fold && en == nullptr && ring == nullptr)
     return halo16_conv_s2(g, src, wgt, wrows, bias, out, ldc, act, num_cu, st, stats);
-  if (en != nullptr && (!fold || ((en->kind & 0xff) != 1 && (en->kind & 0xff) != 2))) return hipErrorNotSupported;
+  if (en != nullptr && (!fold || (en->kind != 1 && en->kind != 2))) return hipErrorNotSupported;
   if (fold && (!g_halo16_fold || g.ys >= 0 || g.xs >= 0 || g.pad_mode != PAD_ZERO || g.up || g.Ho < 2 * H16_TH || g.Wo < 2 * H16_TW ||
                bias != nullptr || act != ACT_NONE || stats != nullptr || ring != nullptr))
     return hipErrorNotSupported;
-  if (!g_halo16 || g_halo_bn != 0 || g_halo_stages != 0) return hipErrorNotSupported;   // (the tile sweep is the 8 x 32 kernel's)
+  if (!g_halo16) return hipErrorNotSupported;
   if (g.sh != 1 || g.sw != 1 || (g.ys != 1 && g.ys != -1) || (g.xs != 1 && g.xs != -1)) return hipErrorNotSupported;
   if (g.th != 3 || g.tw != 3 || g.wK != g.K || g.wtw != g.tw) return hipErrorNotSupported;
   if (g.Cs % 32 != 0 || g.Ho % H16_TH != 0 || g.Wo % H16_TW != 0 || g.M != g.N * g.Ho * g.Wo) return hipErrorNotSupported;
@@ -1109,14 +954,8 @@ hipError_t halo16_conv(const GatherDesc& g, const void* src, const void* wgt, in
   // the double-size tile needs a grid that still covers the chip: at least ~7/8 of a round (fewer: the 8 x 32 tiles spread better)
   if (tiles_m * tn < (num_cu * 7) / 8) return hipErrorNotSupported;
   if (ring != nullptr && (g.Hl < 4 || g.Wl < 4)) return hipErrorNotSupported;
-  if (fold && g_halo16_stages != 8) return hipErrorNotSupported;
-  if (ldc >= 128) {
-    if (g_halo16_stages == 4) return launch_halo16<128, 4>(g, src, wgt, wrows, bias, out, ldc, act, st, stats);
-    if (g_halo16_stages == 6) return launch_halo16<128, 6>(g, src, wgt, wrows, bias, out, ldc, act, st, stats);
-    return launch_halo16<128, 8>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, fold, en);
-  }
-  if (g_halo16_stages == 4) return launch_halo16<64, 4>(g, src, wgt, wrows, bias, out, ldc, act, st, stats);
-  return launch_halo16<64, 8>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, fold, en);
+  if (ldc >= 128) return launch_halo16<128>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, fold, en);
+  return launch_halo16<64>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, fold, en);
 }
 
 }  // namespace dei2i

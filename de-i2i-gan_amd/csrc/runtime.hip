@@ -9,17 +9,11 @@
 
 namespace dei2i {
 
-extern int g_v2_ablate;
 extern int g_use_wgrad_v2;
 extern int g_use_wgrad_halo;
-extern int g_wgrad_halo_cbw, g_wgrad_halo_abl;
 extern int g_use_wgrad_thin;
 extern int g_dgrad_s2_ring;
-extern int g_wt_splits_per_cu;
-extern int g_halo_mfma32;
-extern int g_halo_bn, g_halo_stages;
-extern int g_halo16, g_halo16_stages, g_halo16_fold, g_halo16_s2;
-extern unsigned long long* g_v2_dbg;
+extern int g_halo16, g_halo16_fold, g_halo16_s2;
 static int g_cus = 256;
 void set_num_cu_rt(int n) { g_cus = n > 0 ? n : 256; }
 int num_cu() { return g_cus; }
@@ -97,33 +91,14 @@ int dei2i_set_option(const char* name, int value) {
   if (std::string(name) == "wgrad_v2") { g_use_wgrad_v2 = value; return 0; }
   if (std::string(name) == "halo_conv") { set_use_halo(value); return 0; }
   if (std::string(name) == "thin_conv") { set_use_thin(value); return 0; }
-  if (std::string(name) == "halo_mfma32") { g_halo_mfma32 = value; return 0; }
-  if (std::string(name) == "halo_bn") { if (value != 0 && value != 64 && value != 128) return DEI2I_ERR_BAD_ARG; g_halo_bn = value; return 0; }
-  if (std::string(name) == "halo_stages") {
-    if (value != 0 && value != 4 && value != 6 && value != 8) return DEI2I_ERR_BAD_ARG;
-    g_halo_stages = value;
-    return 0;
-  }
   if (std::string(name) == "halo16") { g_halo16 = value; return 0; }
   if (std::string(name) == "halo16_fold") { g_halo16_fold = value; return 0; }
   if (std::string(name) == "halo16_s2") { g_halo16_s2 = value; return 0; }
-  if (std::string(name) == "halo16_stages") {
-    if (value != 4 && value != 6 && value != 8) return DEI2I_ERR_BAD_ARG;
-    g_halo16_stages = value;
-    return 0;
-  }
-  if (std::string(name) == "splitk_atomic") { set_splitk_atomic(value); return 0; }
   if (std::string(name) == "wgrad_halo") { g_use_wgrad_halo = value; return 0; }
-  if (std::string(name) == "wgrad_halo_abl") { g_wgrad_halo_abl = value; return 0; }
-  if (std::string(name) == "wgrad_halo_cbw") { g_wgrad_halo_cbw = value == 1 ? 1 : 2; return 0; }
   if (std::string(name) == "wgrad_thin") { g_use_wgrad_thin = value; return 0; }
   if (std::string(name) == "dgrad_s2_ring") { g_dgrad_s2_ring = value; return 0; }
-  if (std::string(name) == "wgrad_thin_splits") { g_wt_splits_per_cu = value; return 0; }
-  if (std::string(name) == "v2_ablate") { g_v2_ablate = value; return 0; }     // timing-only builds: 1 = no loads, 2 = no MFMA
   return DEI2I_ERR_BAD_ARG;
 }
-
-int dei2i_set_debug_buffer(void* p) { g_v2_dbg = (unsigned long long*)p; return 0; }
 
 int dei2i_launch_counts(int64_t* out, int n) {
   for (int i = 0; i < n && i < K_COUNT; ++i) out[i] = (int64_t)g_launches[i];

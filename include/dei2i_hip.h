@@ -47,10 +47,13 @@ typedef struct dei2i_conv {
 int dei2i_version(void);
 int dei2i_init(int device);                         /* queries the CU count; optional */
 const char* dei2i_error_string(int code);
-/* tuning / A-B switches: "gather_gemm_v2" / "wgrad_v2" = 0|1 (LDS-DMA kernels for the bf16 hot shapes) */
+/* A-B switches between shipped kernel families (1 = on, the default; 0 = off); any other name -> DEI2I_ERR_BAD_ARG:
+ *   "gather_gemm_v2", "wgrad_v2", "halo_conv", "thin_conv", "wgrad_thin", "dgrad_s2_ring" = 0|1
+ *   "wgrad_halo" = 0|1|2 (2: also on shapes too small to fill the chip)
+ *   "halo16" = 0 (the 8 x 32 halo kernel only) | nonzero (the 16 x 32 halo kernels where they qualify)
+ *   "halo16_fold" = 0|1 (reflect dgrads: ring folded inside the 16 x 32 kernel, or as separate launches)
+ *   "halo16_s2" = 0|1|2 (4x4 stride-2 forward convs on the 16 x 32 kernel; 2: every channel count, not only 64) */
 int dei2i_set_option(const char* name, int value);
-/* diagnostic builds only: device buffer receiving in-kernel s_memtime stamps (option "v2_ablate" = 5) */
-int dei2i_set_debug_buffer(void* device_ptr);
 
 /* ---- packed weight layouts (replaces nothing in the reference: layout prep for the kernels) ---- */
 size_t dei2i_packed_fwd_elems(const dei2i_conv* c);      /* Cout * kh*kw * CinS */

@@ -25,11 +25,11 @@ FAMILIES = (("thin_cin_conv", "thin_cin_conv_kernel"), ("thin_cout_conv", "thin_
 def family(name):
     # the two large instances of the 16 x 32-tile halo conv are kernels of their own: the pipelined forward instance (the
     # step's largest kernel, bench.py's roofline line) and the FOLD instance (reflect dgrads)
-    if "halo16_conv_kernel<128, 8, 0, false, 0, true" in name:
+    if "halo16_conv_kernel<128, 8, false, true" in name:
         return "halo16_conv_fwd"
-    if "halo16_conv_kernel<128, 8, 0, true" in name:
+    if "halo16_conv_kernel<128, 8, true" in name:
         return "halo16_conv_fold"
-    if "halo16_conv_kernel<128, 4, 0, false, 0, false, false, true" in name:
+    if "halo16_conv_kernel<128, 4, false, false, false, true" in name:
         return "halo16_conv_s2"         # the stride-2 4x4 form (parity planes in LDS)
     for fam, key in FAMILIES:
         if key + "<" in name or key + "(" in name:

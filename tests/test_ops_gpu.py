@@ -381,13 +381,13 @@ def test_noise_inject_op(ops, pname):
     assert wg.grad.shape == wt.shape and maxrel(wg.grad, wr.grad) < 2e-5
 
 
-def test_halo_conv_tile_variants_bit_identical(ops):
-    """The halo conv's tile options (output-channel width 64 | 128, weight ring 4 / 6 / 8 deep) change the LDS schedule,
-    not the arithmetic: forward and dgrad must come out bit-identical to the shipped tile, launch after launch.  (A
-    3-deep ring failed exactly this -- a race between the two wave groups -- and was removed.)"""
+def test_halo_conv_8x32_bit_identical_across_launches(ops):
+    """The 8 x 32 tile halo conv's two wave groups run in anti-phase over a shared weight ring: forward and dgrad must
+    come out bit-identical launch after launch.  (A 3-deep ring failed exactly this -- a race between the two wave
+    groups -- and was removed.)"""
     from de_i2i_gan_amd import _lib
     lib = _lib.load()
-    lib.dei2i_set_option(b"halo16", 0)          # the sweep options belong to the 8 x 32 tile kernel: keep the 16 x 32 one out
+    lib.dei2i_set_option(b"halo16", 0)          # the 8 x 32 tile kernel only: keep the 16 x 32 one out
     try:
         for cin, cout, hw, n, up in ((128, 64, 128, 8, False), (256, 128, 64, 16, False), (128, 128, 32, 16, True)):
             torch.manual_seed(11)
@@ -403,19 +403,12 @@ def test_halo_conv_tile_variants_bit_identical(ops):
                 (dx,) = torch.autograd.grad(y, xd, gy)
                 return y.detach().view(torch.int16).clone(), dx.detach().view(torch.int16).clone()
 
-            lib.dei2i_set_option(b"halo_bn", 0)
-            lib.dei2i_set_option(b"halo_stages", 0)
             y0, d0 = run()
-            for bn, stg in ((0, 0), (64, 4), (64, 6), (64, 8)):
-                lib.dei2i_set_option(b"halo_bn", bn)
-                lib.dei2i_set_option(b"halo_stages", stg)
-                for _ in range(3):
-                    y, d = run()
-                    assert torch.equal(y, y0) and torch.equal(d, d0), (cin, cout, hw, bn, stg)
+            for _ in range(12):
+                y, d = run()
+                assert torch.equal(y, y0) and torch.equal(d, d0), (cin, cout, hw)
     finally:
-        lib.dei2i_set_option(b"halo_bn", 0)
-        lib.dei2i_set_option(b"halo_stages", 0)
-        lib.dei2i_set_option(b"halo16", 3)      # (the shipped default: pipelined loop)
+        lib.dei2i_set_option(b"halo16", 1)      # (the shipped default)
 
 
 @pytest.mark.parametrize("pname", ["f32", "bf16"])

@@ -42,7 +42,7 @@ def main():
     only = sys.argv[2] if len(sys.argv) > 2 else None
     for kv in sys.argv[3:]:                      # library options for same-box A/B runs: name=int
         from de_i2i_gan_amd import _lib
-        name, val = kv.split("=") if "=" in kv else ("v2_ablate", kv)
+        name, val = kv.split("=")
         _lib.load().dei2i_set_option(name.encode(), int(val))
     for name, cin, cout, k, s, pad, refl, up, H, N in SHAPES:
         if only and only not in name:
