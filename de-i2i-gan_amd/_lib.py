@@ -60,14 +60,12 @@ SIGNATURES = {
     "dei2i_pack_weight_fwd": (c_int, [_CD, _P, _P, _P]),
     "dei2i_pack_weight_dgrad": (c_int, [_CD, _P, _P, _P]),
     "dei2i_pack_weight_both": (c_int, [_CD, _P, _P, _P, _P]),
-    "dei2i_unpack_wgrad": (c_int, [_CD, _P, _P, c_float, _P]),
     "dei2i_conv2d_out_shape": (None, [_CD, POINTER(c_int), POINTER(c_int)]),
     "dei2i_conv2d_dgrad_shape": (None, [_CD, POINTER(c_int), POINTER(c_int)]),
     "dei2i_conv2d_workspace_bytes": (c_size_t, [_CD]),
     "dei2i_conv2d_fwd": (c_int, [_CD, _P, _P, _P, c_int, _P, _P, c_size_t, _P]),
     "dei2i_conv2d_dgrad": (c_int, [_CD, _P, _P, _P, _P, c_size_t, _P]),
     "dei2i_conv2d_dgrad_input": (c_int, [_CD, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dei2i_conv2d_wgrad": (c_int, [_CD, _P, _P, _P, _P]),
     "dei2i_quantize_fp8": (c_int, [c_size_t, _P, c_float, _P, _P]),
     "dei2i_pack_weight_fwd_fp8": (c_int, [_CD, _P, _P, c_float, _P, _P, _P]),
     "dei2i_conv2d_fp8_supported": (c_int, [_CD]),
@@ -77,20 +75,19 @@ SIGNATURES = {
     "dei2i_nchw_to_nhwc": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "dei2i_nhwc_to_nchw": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "dei2i_nchw_to_nhwc_resize": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_cast_from_f32": (c_int, [c_int, c_size_t, _P, _P, _P]),
     "dei2i_moments_chunks": (c_int, [c_int]),
     "dei2i_moments_partial": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_bn_finalize_train": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P]),
+    "dei2i_bn_finalize_train": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P]),
     "dei2i_bn_finalize_eval": (c_int, [c_int, _P, _P, _P, _P, c_float, _P, _P, _P]),
-    "dei2i_in_finalize": (c_int, [c_int, c_int, c_int, _P, c_float, _P, _P, _P]),
-    "dei2i_affine_act_fwd": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P, c_int, _P, _P, c_float, _P]),
+    "dei2i_in_finalize": (c_int, [c_int, c_int, c_int, c_int, _P, c_float, _P, _P, _P]),
+    "dei2i_affine_act_fwd": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, c_int, _P, _P, c_float, _P]),
     "dei2i_spade_act_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, c_float, _P]),
     "dei2i_act_bwd": (c_int, [c_int, c_size_t, _P, _P, c_int, _P, _P]),
     "dei2i_colsum_blocks": (c_int, [c_size_t]),
     "dei2i_colsum": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P]),
     "dei2i_bn_bwd_chunks": (c_int, [c_size_t]),
-    "dei2i_bn_bwd_partial": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P]),
-    "dei2i_bn_bwd_apply": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P, _P]),
+    "dei2i_bn_bwd_partial": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P]),
+    "dei2i_bn_bwd_apply": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P]),
     "dei2i_spade_bwd_partial": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P]),
     "dei2i_spade_bwd_apply": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, c_int, _P, _P, _P, _P, _P]),
     "dei2i_compose_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
@@ -106,11 +103,6 @@ SIGNATURES = {
     "dei2i_spectral_fwd": (c_int, [c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P]),
     "dei2i_spectral_bwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
     "dei2i_fold_bn_weight": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P, _P]),
-    "dei2i_bn_finalize_train_groups": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P]),
-    "dei2i_affine_act_groups_fwd": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, c_int, _P, _P, c_float, _P]),
-    "dei2i_affine_act_stats_groups_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P]),
-    "dei2i_bn_bwd_partial_groups": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P]),
-    "dei2i_bn_bwd_apply_groups": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P]),
     "dei2i_label_gb_packed_elems": (c_size_t, [c_int, c_int]),
     "dei2i_label_gb_pack": (c_int, [_P, c_int, c_int, _P]),
     "dei2i_label_gb_fwd": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
@@ -146,9 +138,7 @@ SIGNATURES = {
     "dei2i_conv2d_fwd_ring": (c_int, [_CD, _P, _P, _P, _P, c_int, _P, _P, _P]),
     "dei2i_affine_act_img_fwd": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P]),
     "dei2i_spade_prep": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "dei2i_in_finalize_chunks": (c_int, [c_int, c_int, c_int, c_int, _P, c_float, _P, _P, _P]),
-    "dei2i_bn_finalize_train_chunks": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P]),
-    "dei2i_affine_act_stats_fwd": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P]),
+    "dei2i_affine_act_stats_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P]),
     "dei2i_launch_counts": (c_int, [POINTER(c_int64), c_int]),
     "dei2i_launch_counts_reset": (None, []),
     "dei2i_kernel_name": (c_char_p, [c_int]),

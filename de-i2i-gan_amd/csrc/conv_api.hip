@@ -149,19 +149,6 @@ __global__ __launch_bounds__(256) void pack_tiled_kernel(const float* __restrict
   }
 }
 
-__global__ void unpack_wgrad_kernel(const float* __restrict__ src, float* __restrict__ dst, int Cout, int Cin, int CinS,
-                                    int taps, float beta) {
-  const size_t total = (size_t)Cout * Cin * taps;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int t = (int)(i % taps);
-    const size_t r = i / taps;
-    const int ci = (int)(r % Cin);
-    const int co = (int)(r / Cin);
-    const float v = src[((size_t)co * taps + t) * CinS + ci];
-    dst[i] = beta != 0.f ? beta * dst[i] + v : v;
-  }
-}
-
 // ---- fold: gradient of reflect padding + nearest upsample ------------------------------------------
 // dx[n,hs,ws,:] = sum over logical (hl,wl) in the 2^up x 2^up cell of sum over padded positions that map to it.
 template <typename T>
@@ -346,14 +333,6 @@ int dei2i_pack_weight_both(const dei2i_conv* c, const float* w, void* packed_fwd
   else
     hipLaunchKernelGGL(pack_all_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, w, (float*)packed_fwd, (float*)packed_dgrad,
                        pa, c->Cout, c->Cin, c->CinS, c->CoutS, c->kh, c->kw, c->stride);
-  return (int)hipGetLastError();
-}
-
-int dei2i_unpack_wgrad(const dei2i_conv* c, const float* dw_packed, float* dw_oihw, float beta, dei2i_stream s) {
-  if (!valid_conv(c) || !dw_packed || !dw_oihw) return DEI2I_ERR_BAD_ARG;
-  const size_t total = (size_t)c->Cout * c->Cin * c->kh * c->kw;
-  hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)s, dw_packed, dw_oihw,
-                     c->Cout, c->Cin, c->CinS, c->kh * c->kw, beta);
   return (int)hipGetLastError();
 }
 
@@ -551,16 +530,9 @@ int dei2i_conv2d_dgrad_input_norm(const dei2i_conv* c, const void* dy, const voi
   return ef == hipErrorNotSupported ? DEI2I_ERR_BAD_ARG : (int)ef;
 }
 
-int dei2i_conv2d_wgrad(const dei2i_conv* c, const void* x, const void* dy, float* dw_packed, dei2i_stream s) {
-  if (!valid_conv(c) || !x || !dy || !dw_packed) return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  GatherDesc g = make_fwd_desc(to_shape(c), c->CinS);
-  return (int)wgrad_gemm(c->dtype, g, x, dy, c->Cout, c->CoutS, dw_packed, 0, nullptr, st);
-}
-
-/* wgrad straight to the OIHW fp32 gradient: the bf16 hot shapes take the LDS-DMA slab kernel + fused reduce/un-pack
- * (scratch >= dei2i_wgrad_slab_elems floats; more lets it split the pixel range further); other shapes take the v1 kernel
- * into scratch[0 : packed elems] and the un-pack kernel. */
+/* wgrad straight to the OIHW fp32 gradient: the bf16 hot shapes take the LDS-DMA slab kernels, other shapes the v1 kernel;
+ * every path ends in the fused reduce/un-pack (scratch >= dei2i_wgrad_slab_elems floats; more lets it split the pixel range
+ * further). */
 int dei2i_conv2d_wgrad_oihw(const dei2i_conv* c, const void* x, const void* dy, float* scratch, size_t scratch_elems,
                             float* dw_oihw, int accumulate, dei2i_stream s) {
   if (!valid_conv(c) || !x || !dy || !scratch || !dw_oihw) return DEI2I_ERR_BAD_ARG;

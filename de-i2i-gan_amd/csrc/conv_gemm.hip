@@ -340,8 +340,7 @@ template <int ROWB> DEI2I_D int tr_swz(int row) {
 // ------------------------------------------------------------------------------------------------
 // wgrad:  dw[co][k] = sum_m dy[m][co] * gather(src)[m][k]
 // The pixel range is split over gridDim.z; split z stores its partial to slab z (dw + z*slab_elems, plain stores) and
-// wgrad_reduce_unpack sums the slabs in a fixed order -- deterministic, no atomics.  Callers that hand in a bare packed
-// buffer (dei2i_conv2d_wgrad) get a single split.
+// wgrad_reduce_unpack sums the slabs in a fixed order -- deterministic, no atomics.
 // ------------------------------------------------------------------------------------------------
 template <typename T, int BM, int BN>
 __global__ __launch_bounds__(256) void wgrad_kernel(const GatherDesc g, const T* __restrict__ src,
@@ -696,12 +695,11 @@ static hipError_t launch_wg(const GatherDesc& g, const void* src, const void* dy
   const int tiles_k = (g.K + BN - 1) / BN;
   const int nchunks = (g.M + BR - 1) / BR;
   const int tiles = tiles_c * tiles_k;
-  const bool slabs = nsplit_out != nullptr;            // deterministic mode: one slab per split, reduced by the caller
   int splits = (2 * g_num_cu + tiles - 1) / tiles;     // every split costs a slab write + read
   if (splits > nchunks / 2) splits = nchunks / 2;
   const long long slab_elems = wgrad_slab_elems(co_rows, g.K);
-  if (slabs && (size_t)slab_elems * (size_t)splits > capacity_elems) splits = (int)(capacity_elems / (size_t)slab_elems);
-  if (splits < 1 || !slabs) splits = 1;                // a bare packed buffer: one split, plain stores
+  if ((size_t)slab_elems * (size_t)splits > capacity_elems) splits = (int)(capacity_elems / (size_t)slab_elems);
+  if (splits < 1) splits = 1;
   const int cps = (nchunks + splits - 1) / splits;
   const int zs = (nchunks + cps - 1) / cps;
   const size_t lds = 2 * (size_t)BR * (BM + BN) * sizeof(T);
@@ -712,11 +710,11 @@ static hipError_t launch_wg(const GatherDesc& g, const void* src, const void* dy
     if (e != hipSuccess) return e;
     attr_done = true;
   }
-  if (slabs) *nsplit_out = zs;
+  *nsplit_out = zs;
   count_launch(K_WGRAD_V1);
   prof_begin(PROF_WGRAD, 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)co_rows, st);
   hipLaunchKernelGGL(kern, dim3(tiles, 1, zs), dim3(256), lds, st, g, (const T*)src, (const T*)dy, co_rows, ldy, dw,
-                     tiles_k, cps, slabs ? slab_elems : 0ll);
+                     tiles_k, cps, slab_elems);
   prof_end(PROF_WGRAD, st);
   return hipGetLastError();
 }
@@ -724,7 +722,7 @@ static hipError_t launch_wg(const GatherDesc& g, const void* src, const void* dy
 hipError_t wgrad_gemm(int dtype, const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* dw,
                       size_t capacity_elems, int* nsplit_out, hipStream_t st) {
   if (g.M <= 0) {
-    if (nsplit_out) *nsplit_out = 0;      // empty sum: the reduce kernel writes zeros
+    *nsplit_out = 0;      // empty sum: the reduce kernel writes zeros
     return hipSuccess;
   }
   if (dtype == DT_BF16) {

@@ -255,12 +255,6 @@ __global__ void nan_to_num_kernel(T* __restrict__ x, size_t nvec, const int* __r
   }
 }
 
-template <typename T>
-__global__ void cast_from_f32_kernel(const float* __restrict__ src, T* __restrict__ dst, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    Elem<T>::store(dst + i, src[i]);
-}
-
 // nn.AvgPool2d(2, 2) on NHWC (the down-scaling ResBlocks of the conv StyleExtractor, architecture.py:157-168): fp32 sum of the 2x2
 // cell, one rounding; backward spreads dout / 4 over the cell
 template <typename T>
@@ -351,30 +345,9 @@ int dei2i_nhwc_to_nchw(int dtype, int N, int C, int H, int W, int Cs, const void
   return (int)hipGetLastError();
 }
 
-int dei2i_affine_act_fwd(int dtype, size_t pixels, int C, const void* x, const float* a, const float* b, const void* res,
-                         int act, void* out, void* out_e4m3, float e4m3_scale, dei2i_stream s) {
-  const int vec = vec_of(dtype);
-  if (pixels == 0 || C <= 0 || C % vec || !x || !a || !b || !out) return DEI2I_ERR_BAD_ARG;
-  if (out_e4m3 != nullptr && (dtype != DT_BF16 || !(e4m3_scale > 0.f))) return DEI2I_ERR_BAD_ARG;
-  unsigned char* o8 = (unsigned char*)out_e4m3;
-  const size_t nvec = pixels * (size_t)(C / vec);
-  const int cv = C / vec;
-  const bool inv = (256 % cv) == 0;
-  const unsigned grid = grid_for(nvec, 256, EW_CAP);
-  hipStream_t st = (hipStream_t)s;
-  if (dtype == DT_BF16) {
-    if (inv) hipLaunchKernelGGL((affine_act_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, a, b, (const bf16_t*)res, (bf16_t*)out, nvec, cv, act, o8, e4m3_scale);
-    else hipLaunchKernelGGL((affine_act_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, a, b, (const bf16_t*)res, (bf16_t*)out, nvec, cv, act, o8, e4m3_scale);
-  } else {
-    if (inv) hipLaunchKernelGGL((affine_act_kernel<float, true>), dim3(grid), dim3(256), 0, st, (const float*)x, a, b, (const float*)res, (float*)out, nvec, cv, act, o8, e4m3_scale);
-    else hipLaunchKernelGGL((affine_act_kernel<float, false>), dim3(grid), dim3(256), 0, st, (const float*)x, a, b, (const float*)res, (float*)out, nvec, cv, act, o8, e4m3_scale);
-  }
-  return (int)hipGetLastError();
-}
-
 /* `groups` groups of `pixels` pixels each, coefficient rows a, b: (groups, C) -- one launch (grid.y = group) */
-int dei2i_affine_act_groups_fwd(int dtype, int groups, size_t pixels, int C, const void* x, const float* a, const float* b, const void* res,
-                                int act, void* out, void* out_e4m3, float e4m3_scale, dei2i_stream s) {
+int dei2i_affine_act_fwd(int dtype, int groups, size_t pixels, int C, const void* x, const float* a, const float* b, const void* res,
+                         int act, void* out, void* out_e4m3, float e4m3_scale, dei2i_stream s) {
   const int vec = vec_of(dtype);
   if (groups <= 0 || pixels == 0 || C <= 0 || C % vec || !x || !a || !b || !out) return DEI2I_ERR_BAD_ARG;
   if (out_e4m3 != nullptr && (dtype != DT_BF16 || !(e4m3_scale > 0.f))) return DEI2I_ERR_BAD_ARG;
@@ -486,17 +459,6 @@ int dei2i_nan_guard(int dtype, size_t n, void* x, int* flag, dei2i_stream s) {
     hipLaunchKernelGGL(nan_flag_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, nvec, flag);
     hipLaunchKernelGGL(nan_to_num_kernel<float>, dim3(grid), dim3(256), 0, st, (float*)x, nvec, (const int*)flag);
   }
-  return (int)hipGetLastError();
-}
-
-int dei2i_cast_from_f32(int dtype, size_t n, const float* src, void* dst, dei2i_stream s) {
-  if (n == 0 || !src || !dst) return DEI2I_ERR_BAD_ARG;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(cast_from_f32_kernel<bf16_t>, dim3(grid_for(n, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, src,
-                       (bf16_t*)dst, n);
-  else
-    hipLaunchKernelGGL(cast_from_f32_kernel<float>, dim3(grid_for(n, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, src,
-                       (float*)dst, n);
   return (int)hipGetLastError();
 }
 

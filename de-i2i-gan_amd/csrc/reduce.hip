@@ -220,26 +220,11 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
   block_combine_store<2, VEC>(v, cv, rpp, smem, partial + (size_t)chunk * 2 * C, C);
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int C,
-                                                              float* __restrict__ dweight, float* __restrict__ dbias,
-                                                              float* __restrict__ acc_dweight, float* __restrict__ acc_dbias) {
-  const int c = blockIdx.x;
-  double sq[2];
-  combine_records<2>(partial, 0, chunks, C, c, sq);
-  if (threadIdx.x != 0) return;
-  dbias[c] = (float)sq[0];
-  dweight[c] = (float)sq[1];
-  if (acc_dweight != nullptr) {      // a further use of the same parameters in this backward pass: add into its gradient
-    acc_dbias[c] += (float)sq[0];
-    acc_dweight[c] += (float)sq[1];
-  }
-}
-
-// The same for `groups` groups of the batch: per group its own sums (gsum[g][0][c] = dweight, gsum[g][1][c] = dbias: what the apply kernel
+// Per group of the batch (`groups` of them; 1: the whole batch) its own sums (gsum[g][0][c] = dweight, gsum[g][1][c] = dbias: what the apply kernel
 // of the group needs), the parameters' gradient = their total over the groups (written, or added when `accumulate`).
-__global__ __launch_bounds__(256) void bn_bwd_finalize_groups_kernel(const float* __restrict__ partial, int chunks, int C, int groups,
-                                                                     float* __restrict__ gsum, float* __restrict__ dweight,
-                                                                     float* __restrict__ dbias, int accumulate) {
+__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int C, int groups,
+                                                              float* __restrict__ gsum, float* __restrict__ dweight,
+                                                              float* __restrict__ dbias, int accumulate) {
   const int c = blockIdx.x;
   double tw = 0.0, tb = 0.0;
   for (int g = 0; g < groups; ++g) {
@@ -834,53 +819,20 @@ int dei2i_moments_partial(int dtype, int N, int HW, int C, const void* x, float*
   return (int)hipGetLastError();
 }
 
-int dei2i_bn_finalize_train(int N, int HW, int C, const float* partial, const float* weight, const float* bias,
-                            float* running_mean, float* running_var, float momentum, float eps, float* mean, float* rstd,
-                            float* a, float* b, long long* num_batches_tracked, dei2i_stream s) {
-  if (N <= 0 || HW <= 0 || C <= 0 || !partial || !weight || !bias || !mean || !rstd || !a || !b) return DEI2I_ERR_BAD_ARG;
-  hipLaunchKernelGGL(bn_finalize_train_kernel, dim3(C), dim3(combine_threads(N * dei2i_moments_chunks(HW))), 0, (hipStream_t)s, partial, N,
-                     dei2i_moments_chunks(HW), C, (double)N * (double)HW, weight, bias, running_mean, running_var, momentum,
-                     eps, mean, rstd, a, b, num_batches_tracked, 0);
-  return (int)hipGetLastError();
-}
-
-int dei2i_bn_finalize_train_chunks(int N, int HW, int C, int chunks, const float* partial, const float* weight, const float* bias,
-                                   float* running_mean, float* running_var, float momentum, float eps, float* mean, float* rstd,
-                                   float* a, float* b, long long* num_batches_tracked, dei2i_stream s) {
-  if (N <= 0 || HW <= 0 || C <= 0 || chunks <= 0 || !partial || !weight || !bias || !mean || !rstd || !a || !b) return DEI2I_ERR_BAD_ARG;
-  hipLaunchKernelGGL(bn_finalize_train_kernel, dim3(C), dim3(combine_threads(N * chunks)), 0, (hipStream_t)s, partial, N, chunks, C,
-                     (double)N * (double)HW, weight, bias, running_mean, running_var, momentum, eps, mean, rstd, a, b,
-                     num_batches_tracked, 0);
-  return (int)hipGetLastError();
-}
-
-int dei2i_bn_finalize_train_groups(int groups, int N, int HW, int C, int chunks, const float* partial, const float* weight, const float* bias,
-                                   float* running_mean, float* running_var, int running_stride, float momentum, float eps, float* mean,
-                                   float* rstd, float* a, float* b, dei2i_stream s) {
+int dei2i_bn_finalize_train(int groups, int N, int HW, int C, int chunks, const float* partial, const float* weight, const float* bias,
+                            float* running_mean, float* running_var, int running_stride, float momentum, float eps, float* mean,
+                            float* rstd, float* a, float* b, long long* num_batches_tracked, dei2i_stream s) {
   if (groups <= 0 || N <= 0 || HW <= 0 || C <= 0 || chunks <= 0 || !partial || !weight || !bias || !mean || !rstd || !a || !b ||
       (running_mean == nullptr) != (running_var == nullptr) || (running_mean != nullptr && groups > 1 && running_stride < C))
     return DEI2I_ERR_BAD_ARG;
   hipLaunchKernelGGL(bn_finalize_train_kernel, dim3(C, groups), dim3(combine_threads(N * chunks)), 0, (hipStream_t)s, partial, N, chunks, C,
                      (double)N * (double)HW, weight, bias, running_mean, running_var, momentum, eps, mean, rstd, a, b,
-                     (long long*)nullptr, running_stride);
+                     num_batches_tracked, running_stride);
   return (int)hipGetLastError();
 }
 
-int dei2i_affine_act_stats_fwd(int dtype, int N, int HW, int C, const void* x, const float* a, const float* b, const void* res,
-                               int act, void* out, float* partial, dei2i_stream s) {
-  if (N <= 0 || HW <= 0 || !cv_ok(dtype, C) || !x || !a || !b || !out || !partial) return DEI2I_ERR_BAD_ARG;
-  const int chunks = dei2i_moments_chunks(HW);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(affine_act_stats_kernel<bf16_t>, dim3(chunks, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const bf16_t*)x, a, b, (const bf16_t*)res, (bf16_t*)out, partial, HW, C, chunks, act, 0);
-  else
-    hipLaunchKernelGGL(affine_act_stats_kernel<float>, dim3(chunks, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const float*)x, a, b, (const float*)res, (float*)out, partial, HW, C, chunks, act, 0);
-  return (int)hipGetLastError();
-}
-
-int dei2i_affine_act_stats_groups_fwd(int dtype, int groups, int N, int HW, int C, const void* x, const float* a, const float* b,
-                                      const void* res, int act, void* out, float* partial, dei2i_stream s) {
+int dei2i_affine_act_stats_fwd(int dtype, int groups, int N, int HW, int C, const void* x, const float* a, const float* b,
+                               const void* res, int act, void* out, float* partial, dei2i_stream s) {
   if (groups <= 0 || N <= 0 || N % groups != 0 || HW <= 0 || !cv_ok(dtype, C) || !x || !a || !b || !out || !partial) return DEI2I_ERR_BAD_ARG;
   const int chunks = dei2i_moments_chunks(HW);
   if (dtype == DT_BF16)
@@ -923,18 +875,11 @@ int dei2i_bn_finalize_eval(int C, const float* weight, const float* bias, const 
   return (int)hipGetLastError();
 }
 
-int dei2i_in_finalize_chunks(int N, int HW, int C, int chunks, const float* partial, float eps, float* mean, float* rstd,
-                             dei2i_stream s) {
+int dei2i_in_finalize(int N, int HW, int C, int chunks, const float* partial, float eps, float* mean, float* rstd,
+                      dei2i_stream s) {
   if (N <= 0 || HW <= 0 || C <= 0 || chunks <= 0 || !partial || !mean || !rstd) return DEI2I_ERR_BAD_ARG;
   hipLaunchKernelGGL(in_finalize_kernel, dim3(C, N), dim3(combine_threads(chunks)), 0, (hipStream_t)s, partial, N, chunks, C,
                      (double)HW, eps, mean, rstd);
-  return (int)hipGetLastError();
-}
-
-int dei2i_in_finalize(int N, int HW, int C, const float* partial, float eps, float* mean, float* rstd, dei2i_stream s) {
-  if (N <= 0 || HW <= 0 || C <= 0 || !partial || !mean || !rstd) return DEI2I_ERR_BAD_ARG;
-  hipLaunchKernelGGL(in_finalize_kernel, dim3(C, N), dim3(combine_threads(dei2i_moments_chunks(HW))), 0, (hipStream_t)s, partial, N,
-                     dei2i_moments_chunks(HW), C, (double)HW, eps, mean, rstd);
   return (int)hipGetLastError();
 }
 
@@ -964,21 +909,8 @@ int dei2i_bn_bwd_chunks(size_t pixels) {      // one workgroup per chunk: >= 64 
   return (int)c;
 }
 
-int dei2i_bn_bwd_partial(int dtype, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
+int dei2i_bn_bwd_partial(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
                          const float* mean, const float* rstd, int act, float* partial, dei2i_stream s) {
-  if (pixels == 0 || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !partial) return DEI2I_ERR_BAD_ARG;
-  const int chunks = dei2i_bn_bwd_chunks(pixels);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<bf16_t>, dim3(chunks), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const bf16_t*)dz, (const bf16_t*)y, a, b, mean, rstd, act, partial, pixels, C, chunks);
-  else
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<float>, dim3(chunks), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const float*)dz, (const float*)y, a, b, mean, rstd, act, partial, pixels, C, chunks);
-  return (int)hipGetLastError();
-}
-
-int dei2i_bn_bwd_partial_groups(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
-                                const float* mean, const float* rstd, int act, float* partial, dei2i_stream s) {
   if (groups <= 0 || pixels == 0 || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !partial) return DEI2I_ERR_BAD_ARG;
   const int chunks = dei2i_bn_bwd_chunks(pixels);
   if (dtype == DT_BF16)
@@ -993,15 +925,15 @@ int dei2i_bn_bwd_partial_groups(int dtype, int groups, size_t pixels, int C, con
 /* `groups` groups of `pixels` pixels each, coefficient rows (groups, C), records (groups, chunks, 2, C): two launches for all groups.
  * group_sums: (groups, 2, C) floats of scratch (each group's own sums, read by its share of the apply launch); dweight / dbias (C): the
  * total over the groups, written -- or added to when `accumulate` (a further use of the same parameters in this backward pass). */
-int dei2i_bn_bwd_apply_groups(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
-                              const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
-                              float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s) {
+int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
+                       const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
+                       float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s) {
   const int vec = dtype == DT_BF16 ? 8 : 4;
   if (groups <= 0 || pixels == 0 || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !partial || !group_sums || !dweight ||
       !dbias || !dy || chunks <= 0)
     return DEI2I_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(bn_bwd_finalize_groups_kernel, dim3(C), dim3(combine_threads(chunks)), 0, st, partial, chunks, C, groups, group_sums,
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(combine_threads(chunks)), 0, st, partial, chunks, C, groups, group_sums,
                      dweight, dbias, accumulate);
   const size_t nvec = pixels * (size_t)(C / vec);
   const unsigned grid = grid_for((nvec + 1) / 2, 256, 256u * 8u);
@@ -1016,31 +948,6 @@ int dei2i_bn_bwd_apply_groups(int dtype, int groups, size_t pixels, int C, const
   } else {
     if (invc) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), dim3(grid, groups), dim3(256), 0, st, (const float*)dz, (const float*)y, a, b, mean, rstd, act, train, gw, gb, inv, (float*)dy, nvec, cv, 2 * C);
     else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), dim3(grid, groups), dim3(256), 0, st, (const float*)dz, (const float*)y, a, b, mean, rstd, act, train, gw, gb, inv, (float*)dy, nvec, cv, 2 * C);
-  }
-  return (int)hipGetLastError();
-}
-
-int dei2i_bn_bwd_apply(int dtype, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
-                       const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
-                       float* dweight, float* dbias, float* acc_dweight, float* acc_dbias, void* dy, dei2i_stream s) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
-  if (pixels == 0 || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !partial || !dweight || !dbias || !dy ||
-      (acc_dweight == nullptr) != (acc_dbias == nullptr))
-    return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(combine_threads(chunks)), 0, st, partial, chunks, C, dweight, dbias,
-                     acc_dweight, acc_dbias);
-  const size_t nvec = pixels * (size_t)(C / vec);
-  const unsigned grid = grid_for((nvec + 1) / 2, 256, 256u * 8u);
-  const float inv = 1.f / (float)pixels;
-  const int cv = C / vec;
-  const bool invc = (256 % cv) == 0;
-  if (dtype == DT_BF16) {
-    if (invc) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)y, a, b, mean, rstd, act, train, (const float*)dweight, (const float*)dbias, inv, (bf16_t*)dy, nvec, cv, 0);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)y, a, b, mean, rstd, act, train, (const float*)dweight, (const float*)dbias, inv, (bf16_t*)dy, nvec, cv, 0);
-  } else {
-    if (invc) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), dim3(grid), dim3(256), 0, st, (const float*)dz, (const float*)y, a, b, mean, rstd, act, train, (const float*)dweight, (const float*)dbias, inv, (float*)dy, nvec, cv, 0);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), dim3(grid), dim3(256), 0, st, (const float*)dz, (const float*)y, a, b, mean, rstd, act, train, (const float*)dweight, (const float*)dbias, inv, (float*)dy, nvec, cv, 0);
   }
   return (int)hipGetLastError();
 }

@@ -977,23 +977,10 @@ class bn_running_deferred:
         bn_running_deferred.current = self.prev
         return False
 
-    def take(self, running_mean, running_var, num_batches_tracked, momentum, group=0):
-        dev, n = running_mean.device, running_mean.numel()
-        index = self.pass_index[group] if isinstance(self.pass_index, (tuple, list)) else self.pass_index
-        arena, off = bn_running_deferred._arenas.get(dev), self._used.get(dev, 0)
-        if arena is None or off + 2 * n > arena.numel() or running_mean.dtype != torch.float32:
-            zm, zv = torch.zeros_like(running_mean), torch.zeros_like(running_var)          # (first step / an odd buffer: its own zeros)
-            if running_mean.dtype == torch.float32:
-                self._want = getattr(self, "_want", 0) + 2 * n
-        else:
-            zm, zv = arena[off:off + n], arena[off + n:off + 2 * n]
-            self._used[dev] = off + 2 * n
-        self.updates.append((index, running_mean, running_var, num_batches_tracked, zm, zv, momentum))
-        return zm, zv
-
     def take_groups(self, running_mean, running_var, num_batches_tracked, momentum, groups):
-        """take() for every group at once, the buffers evenly spaced in ONE block -- (groups, 2, n): group g's mean at row (g, 0), its
-        variance at (g, 1) -- so that one finalize launch serves all groups (dei2i_bn_finalize_train_groups: stride 2 n)."""
+        """Zeroed buffers for this pass's m * batch statistics, one pair per group, evenly spaced in ONE block -- (groups, 2, n): group
+        g's mean at row (g, 0), its variance at (g, 1) -- so that one finalize launch serves all groups (dei2i_bn_finalize_train:
+        stride 2 n)."""
         dev, n = running_mean.device, running_mean.numel()
         arena, off = bn_running_deferred._arenas.get(dev), self._used.get(dev, 0)
         if arena is None or off + 2 * n * groups > arena.numel() or running_mean.dtype != torch.float32:
@@ -1033,18 +1020,33 @@ class bn_running_deferred:
         self._used, self._want = {}, 0
 
 
-def _bn_coefs_grouped(lib, y, prec, weight, bias, running_mean, running_var, momentum, eps, num_batches_tracked, groups):
-    """Training-mode statistics + coefficients per group of the batch (see bn_batch_groups): a, b, mean, rstd of shape (groups, C)."""
+def _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, momentum, eps, num_batches_tracked, groups=1):
+    """BatchNorm2d statistics + affine coefficients of an NHWC tensor: a[c] = weight * rstd, b[c] = bias - mean * a (batch
+    statistics in training mode, running statistics otherwise; running buffers and the counter are updated in place).
+    a, b, mean, rstd of shape (groups, C): training-mode statistics per group of the batch (see bn_batch_groups).
+    The statistics come from the records its producer left (conv epilogue / affine_act_stats) when there are any."""
     n, h, w, c = y.shape
     dev, st = y.device, _stream()
     w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
     nf = w32.numel()
-    deferred = bn_running_deferred.current
     if n % groups or nf > c or running_mean.numel() != nf or running_var.numel() != nf:
         raise ValueError(f"batchnorm_act: {groups} groups over a batch of {n} / {nf} features for a {c}-channel activation")
-    if deferred is None or not isinstance(deferred.pass_index, (tuple, list)) or len(deferred.pass_index) != groups:
+    deferred = bn_running_deferred.current if training else None
+    if groups > 1 and (deferred is None or not isinstance(deferred.pass_index, (tuple, list)) or len(deferred.pass_index) != groups):
         raise RuntimeError("batchnorm_act: grouped batch statistics want a bn_running_deferred scope with one pass index per group")
-    a, b, mean, rstd = (torch.empty((groups, c), dtype=torch.float32, device=dev) for _ in range(4))
+    # the channel stride is padded to a 16-byte vector (c > num_features: widths that are no multiple of 8 / 4): the kernels index
+    # every per-channel vector up to c, so hand them padded copies -- weight = bias = 0 makes the padded channels' a = b = 0 (their
+    # activations stay zero) -- and copy the live running statistics back
+    if nf < c:
+        w32, b32 = (torch.cat([v, v.new_zeros(c - nf)]) for v in (w32, b32))
+    a, b = (torch.empty((groups, c), dtype=torch.float32, device=dev) for _ in range(2))
+    if not training:
+        rm, rv = running_mean, running_var
+        if nf < c:
+            rm, rv = torch.cat([rm.detach(), rm.new_zeros(c - nf)]), torch.cat([rv.detach(), rv.new_ones(c - nf)])
+        L.check(lib.dei2i_bn_finalize_eval(c, _p(w32), _p(b32), _p(rm), _p(rv), eps, _p(a), _p(b), st), "bn_finalize_eval")
+        return a, b, rm.detach().clone().view(1, c), torch.rsqrt(rv.detach() + eps).view(1, c), nf
+    mean, rstd = (torch.empty((groups, c), dtype=torch.float32, device=dev) for _ in range(2))
     have = _stats_of(y, n, h * w, c) if fuse_norm else None
     if have is not None:
         partial, chunks = have
@@ -1052,74 +1054,22 @@ def _bn_coefs_grouped(lib, y, prec, weight, bias, running_mean, running_var, mom
         chunks = lib.dei2i_moments_chunks(h * w)
         partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
         L.check(lib.dei2i_moments_partial(prec.code, n, h * w, c, _p(y), _p(partial), st), "moments_partial")
-    ng = n // groups
-    if nf == c and running_mean.dtype == torch.float32:
-        block = deferred.take_groups(running_mean, running_var, num_batches_tracked, float(momentum), groups)       # (groups, 2, c)
-        L.check(lib.dei2i_bn_finalize_train_groups(groups, ng, h * w, c, chunks, _p(partial), _p(w32), _p(b32), _p(block[0, 0]), _p(block[0, 1]),
-                                                   2 * c, momentum, eps, _p(mean), _p(rstd), _p(a), _p(b), st), "bn_finalize_train_groups")
-        return a, b, mean, rstd, nf
-    if nf < c:                                   # padded channel stride (see _bn_coefs): c-sized vectors for the kernel
-        w32, b32 = (torch.cat([v, v.new_zeros(c - nf)]) for v in (w32, b32))
-    for g in range(groups):
-        rm, rv = live = deferred.take(running_mean, running_var, num_batches_tracked, float(momentum), group=g)
-        if nf < c:
-            rm, rv = torch.zeros(c, dtype=torch.float32, device=dev), torch.zeros(c, dtype=torch.float32, device=dev)
-        L.check(lib.dei2i_bn_finalize_train_chunks(ng, h * w, c, chunks, _p(partial[g * ng:]), _p(w32), _p(b32), _p(rm), _p(rv),
-                                                   momentum, eps, _p(mean[g]), _p(rstd[g]), _p(a[g]), _p(b[g]), None, st),
-                "bn_finalize_train")
-        if nf < c:
-            live[0].copy_(rm[:nf])
-            live[1].copy_(rv[:nf])
-    return a, b, mean, rstd, nf
-
-
-def _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, momentum, eps, num_batches_tracked):
-    """BatchNorm2d statistics + affine coefficients of an NHWC tensor: a[c] = weight * rstd, b[c] = bias - mean * a (batch
-    statistics in training mode, running statistics otherwise; running buffers and the counter are updated in place).
-    The statistics come from the records its producer left (conv epilogue / affine_act_stats) when there are any."""
-    n, h, w, c = y.shape
-    dev, st = y.device, _stream()
-    a = torch.empty(c, dtype=torch.float32, device=dev)
-    b = torch.empty(c, dtype=torch.float32, device=dev)
-    w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
-    nf = w32.numel()
-    if nf > c or running_mean.numel() != nf or running_var.numel() != nf:
-        raise ValueError(f"batchnorm_act: {nf} features for a {c}-channel activation")
-    rm, rv = running_mean, running_var
-    deferred = bn_running_deferred.current if training else None
     if deferred is not None:                     # this pass's m * batch statistics go to buffers of their own (see bn_running_deferred)
-        rm, rv = deferred.take(running_mean, running_var, num_batches_tracked, float(momentum))
-        running_mean, running_var, num_batches_tracked = rm, rv, None
+        block = deferred.take_groups(running_mean, running_var, num_batches_tracked, float(momentum), groups)       # (groups, 2, nf)
+        rm, rv, num_batches_tracked = block[:, 0], block[:, 1], None
+    else:                                        # (groups == 1) the module's own buffers and counter
+        rm, rv = running_mean.view(1, nf), running_var.view(1, nf)
+    live = rm, rv
+    if nf < c:                                   # c-sized rows for the kernel; the live [:nf] is copied back below
+        pad = torch.zeros((groups, 2, c), dtype=torch.float32, device=dev)
+        if deferred is None:                     # (the deferred buffers are zeros already)
+            pad[0, 0, :nf], pad[0, 1, :nf] = running_mean, running_var
+        rm, rv = pad[:, 0], pad[:, 1]
+    L.check(lib.dei2i_bn_finalize_train(groups, n // groups, h * w, c, chunks, _p(partial), _p(w32), _p(b32), _p(rm), _p(rv), rm.stride(0),
+                                        momentum, eps, _p(mean), _p(rstd), _p(a), _p(b), _p(num_batches_tracked), st), "bn_finalize_train")
     if nf < c:
-        # the channel stride is padded to a 16-byte vector (c > num_features: widths that are no multiple of 8 / 4): the
-        # kernels index every per-channel vector up to c, so hand them padded copies -- weight = bias = 0 makes the
-        # padded channels' a = b = 0 (their activations stay zero) -- and copy the live running statistics back
-        def _padded(v, fill):
-            o = torch.full((c,), fill, dtype=torch.float32, device=dev)
-            o[:nf] = v.detach()
-            return o
-        w32, b32, rm, rv = _padded(w32, 0.0), _padded(b32, 0.0), _padded(running_mean, 0.0), _padded(running_var, 1.0)
-    if training:
-        mean = torch.empty(c, dtype=torch.float32, device=dev)
-        rstd = torch.empty(c, dtype=torch.float32, device=dev)
-        have = _stats_of(y, n, h * w, c) if fuse_norm else None
-        if have is not None:
-            partial, chunks = have
-        else:
-            chunks = lib.dei2i_moments_chunks(h * w)
-            partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
-            L.check(lib.dei2i_moments_partial(prec.code, n, h * w, c, _p(y), _p(partial), st), "moments_partial")
-        L.check(lib.dei2i_bn_finalize_train_chunks(n, h * w, c, chunks, _p(partial), _p(w32), _p(b32), _p(rm), _p(rv),
-                                                   momentum, eps, _p(mean), _p(rstd), _p(a), _p(b), _p(num_batches_tracked), st),
-                "bn_finalize_train")
-        if nf < c:
-            running_mean.copy_(rm[:nf])
-            running_var.copy_(rv[:nf])
-    else:
-        L.check(lib.dei2i_bn_finalize_eval(c, _p(w32), _p(b32), _p(rm), _p(rv), eps, _p(a), _p(b), st),
-                "bn_finalize_eval")
-        mean = rm.detach().clone()
-        rstd = torch.rsqrt(rv.detach() + eps)
+        live[0].copy_(rm[:, :nf])
+        live[1].copy_(rv[:, :nf])
     return a, b, mean, rstd, nf
 
 
@@ -1132,64 +1082,33 @@ def _bn_backward(lib, prec, dout, y, a, b, mean, rstd, act, training, weight, bi
     have = hint.take(dout) if hint is not None else None
     dout = dout.contiguous()
     n, h, w, c = y.shape
-    groups = a.shape[0] if a.dim() == 2 else 1
-    ng = n // groups
-    pixels = ng * h * w
-    a, b, mean, rstd = (t.view(groups, c) for t in (a, b, mean, rstd))
+    groups = a.shape[0]
+    pixels = n // groups * h * w
     if have is not None:
-        partial, chunks = have[0], ng * have[1]          # (n, records per image, 2, c): a group's records are contiguous
-    elif groups > 1:
-        chunks = lib.dei2i_bn_bwd_chunks(pixels)
-        partial = torch.empty((groups * chunks, 2, c), dtype=torch.float32, device=y.device)
-        L.check(lib.dei2i_bn_bwd_partial_groups(prec.code, groups, pixels, c, _p(dout), _p(y), _p(a), _p(b), _p(mean), _p(rstd), act,
-                                                _p(partial), st), "bn_bwd_partial_groups")
+        partial, chunks = have[0], n // groups * have[1]     # (n, records per image, 2, c): a group's records are contiguous
     else:
         chunks = lib.dei2i_bn_bwd_chunks(pixels)
         partial = torch.empty((groups * chunks, 2, c), dtype=torch.float32, device=y.device)
-        for g in range(groups):
-            L.check(lib.dei2i_bn_bwd_partial(prec.code, pixels, c, _p(dout[g * ng:]), _p(y[g * ng:]), _p(a[g]), _p(b[g]), _p(mean[g]),
-                                             _p(rstd[g]), act, _p(partial[g * chunks:]), st), "bn_bwd_partial")
-    padded = nf < c               # padded channel stride: c-sized scratch vectors, sliced to num_features below
-    if padded:
-        tmp_wb = torch.empty((2, c), dtype=torch.float32, device=y.device)
-        dweight = dbias = None
-        dw_ptr, db_ptr, acc_w, acc_b = tmp_wb.data_ptr(), tmp_wb.data_ptr() + 4 * c, 0, 0
+        L.check(lib.dei2i_bn_bwd_partial(prec.code, groups, pixels, c, _p(dout), _p(y), _p(a), _p(b), _p(mean), _p(rstd), act,
+                                         _p(partial), st), "bn_bwd_partial")
+    if nf < c:                    # padded channel stride: c-sized scratch vectors, sliced to num_features below
+        wb = torch.empty((2, c), dtype=torch.float32, device=y.device)
+        dw_ptr, db_ptr, accumulate = wb[0].data_ptr(), wb[1].data_ptr(), 0
     else:
-        dweight, dw_ptr, acc_w = _grad_target(weight, (c,), y.device)
+        # the parameters' gradient is written, or added to when an earlier use of them in this pass holds the tensor already
+        dweight, dw_ptr, accumulate = _grad_target(weight, (c,), y.device)
         dbias, db_ptr, acc_b = _grad_target(bias, (c,), y.device)
-    acc_ptrs = (None, None)
-    if acc_w or acc_b:            # the kernel needs this call's own sums as well: they go to scratch vectors
-        if not (acc_w and acc_b):
+        if accumulate != acc_b:
             # one of the pair lost its first gradient tensor (see _grad_target): give both a fresh tensor
             dweight = torch.empty((c,), dtype=torch.float32, device=y.device)
             dbias = torch.empty((c,), dtype=torch.float32, device=y.device)
-            dw_ptr, db_ptr, acc_w, acc_b = dweight.data_ptr(), dbias.data_ptr(), 0, 0
-        else:
-            acc_ptrs = (c_void_p(dw_ptr), c_void_p(db_ptr))
-            tmp = torch.empty((2, c), dtype=torch.float32, device=y.device)
-            dw_ptr, db_ptr = tmp.data_ptr(), tmp.data_ptr() + 4 * c
+            dw_ptr, db_ptr, accumulate = dweight.data_ptr(), dbias.data_ptr(), 0
     dy = torch.empty_like(y)
-    parts = partial.view(groups, -1)
-    if groups > 1:
-        # every group in two launches: the groups' own sums (read by their share of the apply launch) go to scratch, their total to the
-        # parameters' gradient -- written, or added when an earlier use of the parameters in this pass holds the tensor already
-        gsum = torch.empty((groups, 2, c), dtype=torch.float32, device=y.device)
-        accumulate = acc_ptrs[0] is not None
-        tgt_w, tgt_b = (acc_ptrs[0], acc_ptrs[1]) if accumulate else (c_void_p(dw_ptr), c_void_p(db_ptr))
-        L.check(lib.dei2i_bn_bwd_apply_groups(prec.code, groups, pixels, c, _p(dout), _p(y), _p(a), _p(b), _p(mean), _p(rstd), act,
-                                              1 if training else 0, _p(partial), chunks, _p(gsum), tgt_w, tgt_b, 1 if accumulate else 0,
-                                              _p(dy), st), "bn_bwd_apply_groups")
-    for g in range(groups if groups == 1 else 0):
-        if g == 1:                # the later groups add into where the first one's sums went
-            if acc_ptrs[0] is None:
-                acc_ptrs = (c_void_p(dw_ptr), c_void_p(db_ptr))
-            tmp = torch.empty((2, c), dtype=torch.float32, device=y.device)
-            dw_ptr, db_ptr = tmp.data_ptr(), tmp.data_ptr() + 4 * c
-        L.check(lib.dei2i_bn_bwd_apply(prec.code, pixels, c, _p(dout[g * ng:]), _p(y[g * ng:]), _p(a[g]), _p(b[g]), _p(mean[g]),
-                                       _p(rstd[g]), act, 1 if training else 0, _p(parts[g]), chunks, c_void_p(dw_ptr), c_void_p(db_ptr),
-                                       acc_ptrs[0], acc_ptrs[1], _p(dy[g * ng:]), st), "bn_bwd_apply")
-    if padded:
-        dweight, dbias = tmp_wb[0, :nf].clone(), tmp_wb[1, :nf].clone()
+    gsum = torch.empty((groups, 2, c), dtype=torch.float32, device=y.device)      # each group's own sums, read by its share of the apply
+    L.check(lib.dei2i_bn_bwd_apply(prec.code, groups, pixels, c, _p(dout), _p(y), _p(a), _p(b), _p(mean), _p(rstd), act, 1 if training else 0,
+                                   _p(partial), chunks, _p(gsum), c_void_p(dw_ptr), c_void_p(db_ptr), accumulate, _p(dy), st), "bn_bwd_apply")
+    if nf < c:
+        dweight, dbias = wb[0, :nf].clone(), wb[1, :nf].clone()
     return dy, dweight, dbias
 
 
@@ -1205,40 +1124,26 @@ class _BatchNormAct(torch.autograd.Function):
         st = _stream()
         dev = y.device
         groups = bn_groups if training else 1
-        if groups > 1:
-            a, b, mean, rstd, nf = _bn_coefs_grouped(lib, y, prec, weight, bias, running_mean, running_var, momentum, eps,
-                                                     num_batches_tracked, groups)
-        else:
-            a, b, mean, rstd, nf = _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, momentum, eps,
-                                             num_batches_tracked)
+        a, b, mean, rstd, nf = _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, momentum, eps,
+                                         num_batches_tracked, groups)
         out = torch.empty_like(y)
         if res is not None:
             res = res.contiguous()
         xq = torch.empty(out.numel(), dtype=torch.uint8, device=dev) if _fp8_copy_wanted(prec, c) else None
         ng = n // groups
-        av, bv = a.view(groups, c), b.view(groups, c)
         partial = None
         if want_stats and fuse_norm and xq is None:
             # the statistics records of the output in the same pass (an InstanceNorm / BatchNorm reads this tensor next)
             chunks = lib.dei2i_moments_chunks(h * w)
             partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
             _stats_stash.append((partial, chunks))
-        if groups > 1:                                    # every group in one launch (grid.y = group; coefficient rows (groups, c))
-            if partial is not None:
-                L.check(lib.dei2i_affine_act_stats_groups_fwd(prec.code, groups, n, h * w, c, _p(y), _p(av), _p(bv), _p(res), act, _p(out),
-                                                              _p(partial), st), "affine_act_stats_groups")
-            else:
-                L.check(lib.dei2i_affine_act_groups_fwd(prec.code, groups, ng * h * w, c, _p(y), _p(av), _p(bv), _p(res), act, _p(out), _p(xq),
-                                                        FP8_ACT_SCALE, st), "affine_act_groups")
-        for g in range(groups if groups == 1 else 0):
-            lo = g * ng
-            rg = res[lo:] if res is not None else None
-            if partial is not None:
-                L.check(lib.dei2i_affine_act_stats_fwd(prec.code, ng, h * w, c, _p(y[lo:]), _p(av[g]), _p(bv[g]), _p(rg), act, _p(out[lo:]),
-                                                       _p(partial[lo:]), st), "affine_act_stats")
-            else:
-                L.check(lib.dei2i_affine_act_fwd(prec.code, ng * h * w, c, _p(y[lo:]), _p(av[g]), _p(bv[g]), _p(rg), act, _p(out[lo:]),
-                                                 _p(xq[lo * h * w * c:]) if xq is not None else None, FP8_ACT_SCALE, st), "affine_act")
+        # every group in one launch (grid.y = group; coefficient rows (groups, c))
+        if partial is not None:
+            L.check(lib.dei2i_affine_act_stats_fwd(prec.code, groups, n, h * w, c, _p(y), _p(a), _p(b), _p(res), act, _p(out), _p(partial), st),
+                    "affine_act_stats")
+        else:
+            L.check(lib.dei2i_affine_act_fwd(prec.code, groups, ng * h * w, c, _p(y), _p(a), _p(b), _p(res), act, _p(out), _p(xq),
+                                             FP8_ACT_SCALE, st), "affine_act")
         if xq is not None:
             _fp8_stash.append(xq)
         ctx.prec, ctx.act, ctx.training, ctx.has_res = prec, act, training, res is not None
@@ -1369,11 +1274,11 @@ class _AffineAdd(torch.autograd.Function):
             n, hw = x.shape[0], x.shape[1] * x.shape[2]
             chunks = lib.dei2i_moments_chunks(hw)
             partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=x.device)
-            L.check(lib.dei2i_affine_act_stats_fwd(prec.code, n, hw, c, _p(x), _p(ones), _p(zeros), _p(res), L.ACT_NONE, _p(out),
+            L.check(lib.dei2i_affine_act_stats_fwd(prec.code, 1, n, hw, c, _p(x), _p(ones), _p(zeros), _p(res), L.ACT_NONE, _p(out),
                                                    _p(partial), _stream()), "add_stats")
             _stats_stash.append((partial, chunks))
         else:
-            L.check(lib.dei2i_affine_act_fwd(prec.code, x.numel() // c, c, _p(x), _p(ones), _p(zeros), _p(res),
+            L.check(lib.dei2i_affine_act_fwd(prec.code, 1, x.numel() // c, c, _p(x), _p(ones), _p(zeros), _p(res),
                                              L.ACT_NONE, _p(out), None, 1.0, _stream()), "add")
         return out
 
@@ -1440,7 +1345,7 @@ class _SpadeRelu(torch.autograd.Function):
             chunks = lib.dei2i_moments_chunks(hs * ws)
             partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
             L.check(lib.dei2i_moments_partial(prec.code, n, hs * ws, c, _p(x), _p(partial), st), "moments_partial")
-        L.check(lib.dei2i_in_finalize_chunks(n, hs * ws, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
+        L.check(lib.dei2i_in_finalize(n, hs * ws, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
         out = torch.empty((n, h, w, c), dtype=prec.dtype, device=dev)
         xq = torch.empty(out.numel(), dtype=torch.uint8, device=dev) if _fp8_copy_wanted(prec, c) else None
         L.check(lib.dei2i_spade_act_fwd(prec.code, n, h, w, c, 1 if up else 0, _p(x), _p(mean), _p(rstd), _p(gb), gb_mode,
@@ -1644,17 +1549,15 @@ class _InstanceNormAct(torch.autograd.Function):
             chunks = lib.dei2i_moments_chunks(h * w)
             partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
             L.check(lib.dei2i_moments_partial(prec.code, n, h * w, c, _p(x), _p(partial), st), "moments_partial")
-        L.check(lib.dei2i_in_finalize_chunks(n, h * w, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
+        L.check(lib.dei2i_in_finalize(n, h * w, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
         a, b = rstd, -mean * rstd
         out = torch.empty_like(x)
         cv = c // (8 if prec is BF16 else 4)
         if 256 % cv == 0 or cv % 256 == 0:                # (the per-image kernel keeps one channel vector per thread)
             L.check(lib.dei2i_affine_act_img_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), slope, _p(out), st), "affine_act_img")
-        else:                                             # odd channel counts: the per-channel kernel, image by image
+        else:                                             # odd channel counts: the per-channel kernel, one group per image
             act = {1.0: L.ACT_NONE, 0.0: L.ACT_RELU, 0.2: L.ACT_LRELU}[slope]
-            for i in range(n):
-                L.check(lib.dei2i_affine_act_fwd(prec.code, h * w, c, _p(x[i]), _p(a[i]), _p(b[i]), None, act, _p(out[i]), None, 1.0, st),
-                        "affine_act")
+            L.check(lib.dei2i_affine_act_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), None, act, _p(out), None, 1.0, st), "affine_act")
         if res is not None:
             out = out + res
         ctx.prec, ctx.slope, ctx.has_res = prec, slope, res is not None
@@ -1819,7 +1722,7 @@ class _Scale(torch.autograd.Function):
         x = x.contiguous()
         c = x.shape[-1]
         out = torch.empty_like(x)
-        L.check(_lib_for(x).dei2i_affine_act_fwd(precision_of(x).code, x.numel() // c, c, _p(x), _p(_const_vec(x.device, c, float(s))),
+        L.check(_lib_for(x).dei2i_affine_act_fwd(precision_of(x).code, 1, x.numel() // c, c, _p(x), _p(_const_vec(x.device, c, float(s))),
                                                  _p(_const_vec(x.device, c, 0.0)), None, L.ACT_NONE, _p(out), None, 1.0, _stream()), "scale")
         ctx.s = s
         return out
@@ -1843,7 +1746,7 @@ class _Act(torch.autograd.Function):
         x = x.contiguous()
         c = x.shape[-1]
         out = torch.empty_like(x)
-        L.check(_lib_for(x).dei2i_affine_act_fwd(precision_of(x).code, x.numel() // c, c, _p(x), _p(_const_vec(x.device, c, 1.0)),
+        L.check(_lib_for(x).dei2i_affine_act_fwd(precision_of(x).code, 1, x.numel() // c, c, _p(x), _p(_const_vec(x.device, c, 1.0)),
                                                  _p(_const_vec(x.device, c, 0.0)), None, act, _p(out), None, 1.0, _stream()), "act")
         ctx.act = act
         ctx.save_for_backward(out)
@@ -1888,18 +1791,16 @@ class _InAffineAct(torch.autograd.Function):
             chunks = lib.dei2i_moments_chunks(h * w)
             partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
             L.check(lib.dei2i_moments_partial(prec.code, n, h * w, c, _p(x), _p(partial), st), "moments_partial")
-        L.check(lib.dei2i_in_finalize_chunks(n, h * w, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
+        L.check(lib.dei2i_in_finalize(n, h * w, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
         a = rstd * (1.0 + gb[:, :c].float())
         b = gb[:, c:].float() - mean * a
         out = torch.empty_like(x)
         cv = c // (8 if prec is BF16 else 4)
         if 256 % cv == 0 or cv % 256 == 0:
             L.check(lib.dei2i_affine_act_img_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), slope, _p(out), st), "affine_act_img")
-        else:
+        else:                                             # odd channel counts: the per-channel kernel, one group per image
             act = {1.0: L.ACT_NONE, 0.0: L.ACT_RELU, 0.2: L.ACT_LRELU}[slope]
-            for i in range(n):
-                L.check(lib.dei2i_affine_act_fwd(prec.code, h * w, c, _p(x[i]), _p(a[i].contiguous()), _p(b[i].contiguous()), None, act,
-                                                 _p(out[i]), None, 1.0, st), "affine_act")
+            L.check(lib.dei2i_affine_act_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), None, act, _p(out), None, 1.0, st), "affine_act")
         ctx.prec, ctx.slope, ctx.cl = prec, slope, cl
         ctx.save_for_backward(x, mean, rstd, gb)
         return out

@@ -62,8 +62,6 @@ int dei2i_pack_weight_fwd(const dei2i_conv* c, const float* w_oihw, void* packed
 int dei2i_pack_weight_dgrad(const dei2i_conv* c, const float* w_oihw, void* packed, dei2i_stream s);
 /* both layouts in one launch (the training path: a weight is re-packed once per optimizer step) */
 int dei2i_pack_weight_both(const dei2i_conv* c, const float* w_oihw, void* packed_fwd, void* packed_dgrad, dei2i_stream s);
-/* packed fp32 wgrad [Cout][kh*kw][CinS] -> OIHW fp32 (beta = 0: overwrite, 1: accumulate) */
-int dei2i_unpack_wgrad(const dei2i_conv* c, const float* dw_packed, float* dw_oihw, float beta, dei2i_stream s);
 
 /* ---- convolution (ATen convolution / convolution_backward) ---- */
 void dei2i_conv2d_out_shape(const dei2i_conv* c, int* Ho, int* Wo);
@@ -83,9 +81,6 @@ int dei2i_conv2d_dgrad_input(const dei2i_conv* c, const void* dy, const void* wd
 /* one wgrad slab: the packed [Cout][kh*kw][CinS] fp32 gradient with Cout rounded up to 8 rows (the kernels store
  * 8-row groups unguarded; the extra rows are never read) */
 size_t dei2i_wgrad_slab_elems(const dei2i_conv* c);
-/* dw_packed (fp32, dei2i_wgrad_slab_elems), written by a single pass over the pixels (plain stores, deterministic);
- * the production path is dei2i_conv2d_wgrad_oihw, which splits the pixel range over slabs */
-int dei2i_conv2d_wgrad(const dei2i_conv* c, const void* x, const void* dy, float* dw_packed, dei2i_stream s);
 /* wgrad straight to the OIHW fp32 gradient (what autograd hands to the optimizer).  scratch: fp32 device buffer of at
  * least dei2i_wgrad_slab_elems(c) floats; extra capacity lets the kernels split the pixel range over more
  * workgroups (one partial slab per split, summed and un-packed by a second kernel: no float atomics). */
@@ -117,29 +112,34 @@ int dei2i_nhwc_to_nchw(int dtype, int N, int C, int H, int W, int Cs, const void
  * normalization.py:29) */
 int dei2i_nchw_to_nhwc_resize(int dtype, int N, int C, int hs, int ws, int H, int W, int Cs, const float* src, void* dst,
                               dei2i_stream s);
-/* fp32 -> compute dtype cast of a flat buffer */
-int dei2i_cast_from_f32(int dtype, size_t n, const float* src, void* dst, dei2i_stream s);
 
 /* ---- per-channel moments (native_batch_norm statistics; generator.py:71,113,124; normalization.py:14) ----
  * partial: (N, chunks, 2, C) fp32 sums / sums of squares.  chunks = dei2i_moments_chunks(HW). */
 int dei2i_moments_chunks(int HW);
 int dei2i_moments_partial(int dtype, int N, int HW, int C, const void* x, float* partial, dei2i_stream s);
-/* BatchNorm2d train: batch stats over (N,HW) -> scale/shift a[c], b[c]; mean/rstd saved for backward; running
- * stats updated (momentum 0.1, unbiased var).  All vectors fp32[C]. */
-/* num_batches_tracked (int64 device scalar, may be NULL) is incremented by the same launch */
-int dei2i_bn_finalize_train(int N, int HW, int C, const float* partial, const float* weight, const float* bias,
-                            float* running_mean, float* running_var, float momentum, float eps, float* mean,
+/* ---- BatchNorm groups: a batch that carries several passes takes statistics, apply and backward per GROUP of the batch, one launch
+ * for all groups (the paired generator passes of the G loss: defectgan_model.py:185-190 as two passes over 2 x batch); groups = 1 is
+ * plain BatchNorm over the whole batch.  N / pixels are PER GROUP, the groups are consecutive in the activation tensors, mean / rstd /
+ * a / b hold one row of C per group, the statistics records one block per group. ---- */
+/* BatchNorm2d train: batch stats over (N,HW) from `chunks` records per image -> scale/shift a[c], b[c]; mean/rstd saved for backward;
+ * running stats (both or neither, may be NULL; group g's at + g * running_stride floats) updated (momentum 0.1, unbiased var).
+ * num_batches_tracked (int64 device scalar, may be NULL) is incremented once by the same launch. */
+int dei2i_bn_finalize_train(int groups, int N, int HW, int C, int chunks, const float* partial, const float* weight, const float* bias,
+                            float* running_mean, float* running_var, int running_stride, float momentum, float eps, float* mean,
                             float* rstd, float* a, float* b, long long* num_batches_tracked, dei2i_stream s);
 int dei2i_bn_finalize_eval(int C, const float* weight, const float* bias, const float* running_mean,
                            const float* running_var, float eps, float* a, float* b, dei2i_stream s);
-/* InstanceNorm2d(affine=False): per (n,c) mean / rstd, fp32 [N][C] */
-int dei2i_in_finalize(int N, int HW, int C, const float* partial, float eps, float* mean, float* rstd, dei2i_stream s);
+/* InstanceNorm2d(affine=False): per (n,c) mean / rstd, fp32 [N][C], from `chunks` records per image */
+int dei2i_in_finalize(int N, int HW, int C, int chunks, const float* partial, float eps, float* mean, float* rstd, dei2i_stream s);
 
 /* ---- fused normalisation + activation, forward ---- */
 /* out = act(a[c]*x + b[c]) (+ res)   -- BatchNorm apply + LeakyReLU (+ ResBlock identity), architecture.py:116-118,174-176 */
 /* out_e4m3 (bf16 only, may be NULL): also write e4m3(out * e4m3_scale) -- the operand copy of the fp8 forward mode */
-int dei2i_affine_act_fwd(int dtype, size_t pixels, int C, const void* x, const float* a, const float* b, const void* res,
+int dei2i_affine_act_fwd(int dtype, int groups, size_t pixels, int C, const void* x, const float* a, const float* b, const void* res,
                          int act, void* out, void* out_e4m3, float e4m3_scale, dei2i_stream s);
+/* the same, also writing the statistics records of its output: partial (N, dei2i_moments_chunks(HW), 2, C); N: the whole batch */
+int dei2i_affine_act_stats_fwd(int dtype, int groups, int N, int HW, int C, const void* x, const float* a, const float* b,
+                               const void* res, int act, void* out, float* partial, dei2i_stream s);
 /* SPADE + ReLU (normalization.py:24-37, architecture.py:241-245,343-350):
  *   out[n,h,w,c] = relu( (x[n,h>>up,w>>up,c] - mean[n,c]) * rstd[n,c] * (1 + gamma) + beta ) (+ nothing)
  * gb is (N, Hg, Wg, 2*C): gamma = [..., :C], beta = [..., C:].  gb_mode 0: Hg x Wg == output extent;
@@ -154,17 +154,17 @@ int dei2i_act_bwd(int dtype, size_t n, const void* dz, const void* z, int act, v
  * partial is fp32 scratch of dei2i_colsum_blocks(rows) * C floats. */
 int dei2i_colsum_blocks(size_t rows);
 int dei2i_colsum(int dtype, size_t rows, int C, const void* g, float* partial, float* out, dei2i_stream s);
-/* BatchNorm backward (train): z = act(a*y+b); g = dz*act'(z); needs sum(g), sum(g*xhat) per channel.
- * bn_bwd_partial writes (chunks, 2, C) partial sums over `pixels` rows; bn_bwd_apply finishes:
- *   dy = a * (g - sum_g/M - xhat * sum_gx/M),  dweight = sum_gx, dbias = sum_g.   train = 0 -> dy = a*g.
- *   acc_dweight / acc_dbias (both or neither, may be NULL): this call's sums are ALSO added into them -- the gradient
- *   buffers of parameters that an earlier node of the same backward pass already wrote. */
+/* BatchNorm backward (train): z = act(a*y+b); g = dz*act'(z); needs sum(g), sum(g*xhat) per channel and group.
+ * bn_bwd_partial writes (groups, chunks, 2, C) partial sums over each group's `pixels` rows; bn_bwd_apply finishes:
+ *   dy = a * (g - sum_g/M - xhat * sum_gx/M) with the group's own sums (group_sums: (groups, 2, C) floats of scratch),
+ *   dweight = sum_gx, dbias = sum_g totalled over the groups -- written, or added to when `accumulate` (a further use of the same
+ *   parameters in this backward pass).   train = 0 -> dy = a*g. */
 int dei2i_bn_bwd_chunks(size_t pixels);
-int dei2i_bn_bwd_partial(int dtype, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
+int dei2i_bn_bwd_partial(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
                          const float* mean, const float* rstd, int act, float* partial, dei2i_stream s);
-int dei2i_bn_bwd_apply(int dtype, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
+int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
                        const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
-                       float* dweight, float* dbias, float* acc_dweight, float* acc_dbias, void* dy, dei2i_stream s);
+                       float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s);
 /* SPADE backward.  z = relu(v), v = xhat*(1+gamma)+beta is RECOMPUTED from x and the gamma/beta table in both passes (the
  * op keeps neither its output nor a dxhat tensor): g = dz*[v>0]; dgamma = g*xhat, dbeta = g -> dgb (T: dense tensor, or
  * the (N,5,5,2C) border-class table -- its 24 border classes are written by pass 1, the interior class by pass 2); partial (N, chunks, 4, C) fp32 sums of dxhat = g*(1+gamma), dxhat*xhat and the
@@ -273,24 +273,6 @@ int dei2i_spectral_bwd(int Cout, int K, const float* G, const float* w_eff, cons
 int dei2i_fold_bn_weight(int Cout, int K, const float* W, const float* bn_weight, const float* bn_bias, const float* running_mean,
                          const float* running_var, float eps, float* w_eff, float* b_eff, dei2i_stream s);
 
-/* ---- BatchNorm over a batch that carries several passes: statistics, apply and backward per GROUP of the batch, one launch for all
- * groups (the paired generator passes of the G loss: defectgan_model.py:185-190 as two passes over 2 x batch).  Same kernels and
- * argument meaning as the one-group entry points above (finalize_train_chunks, affine_act / affine_act_stats, bn_bwd_partial / apply); N /
- * pixels are PER GROUP, the groups are consecutive in the activation tensors, mean / rstd / a / b hold one row of C per group, the
- * statistics records one block per group; running_mean / running_var of group g at + g * running_stride floats. ---- */
-int dei2i_bn_finalize_train_groups(int groups, int N, int HW, int C, int chunks, const float* partial, const float* weight, const float* bias,
-                                   float* running_mean, float* running_var, int running_stride, float momentum, float eps, float* mean,
-                                   float* rstd, float* a, float* b, dei2i_stream s);
-int dei2i_affine_act_groups_fwd(int dtype, int groups, size_t pixels, int C, const void* x, const float* a, const float* b, const void* res,
-                                int act, void* out, void* out_e4m3, float e4m3_scale, dei2i_stream s);
-int dei2i_affine_act_stats_groups_fwd(int dtype, int groups, int N, int HW, int C, const void* x, const float* a, const float* b,
-                                      const void* res, int act, void* out, float* partial, dei2i_stream s);   /* N: the whole batch */
-int dei2i_bn_bwd_partial_groups(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
-                                const float* mean, const float* rstd, int act, float* partial, dei2i_stream s);
-int dei2i_bn_bwd_apply_groups(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
-                              const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
-                              float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s);
-
 /* ---- SPADE's label path, second stage, for all modules of a generator at once (csrc/label_path.hip) ----
  * normalization.py:17-37 with a constant label map (the 5 x 5 class image of networks/architecture.py SPADE): gamma | beta =
  * conv3x3(actv; mlp_gamma | mlp_beta) + bias per module, every module reading `hidden` channels at its offset `in_off` of ONE activation
@@ -346,7 +328,7 @@ int dei2i_prof_collect(int family, int64_t* launches, double* total_ms, double* 
  *   - `stats` (epilogue): per-channel sum / sum of squares of the conv's stored output, one record per 8x32-pixel tile,
  *     (N, dei2i_conv2d_stats_chunks, 2, CoutS) fp32 -- the dei2i_moments_partial layout, consumed by the finalize kernels;
  *   - `pro` (operand path): the conv's INPUT is z = act(A[n*n_stride + c] * x + B[...]), act(v) = max(v,0) + slope*min(v,0),
- *     applied to the input halo in LDS; z is never written to memory.  BatchNorm: A = a, B = b of dei2i_bn_finalize_*,
+ *     applied to the input halo in LDS; z is never written to memory.  BatchNorm: A = a, B = b of dei2i_bn_finalize_train / _eval,
  *     n_stride = 0, slope = 0.2.  SPADE on a constant label map: A, B, ring from dei2i_spade_prep, n_stride = CinS,
  *     slope = 0; `ring` holds z of the logical input's 2-pixel frame (whose gamma / beta differ per pixel),
  *     [N][dei2i_ring_pixels(H<<up, W<<up)][CinS] in the compute dtype.
@@ -433,15 +415,6 @@ size_t dei2i_ring_pixels(int H, int W);                                        /
  * (N,5,5,2C) table, and (ring != NULL) relu(IN(x)*(1+gamma)+beta) of the 2-pixel frame of the (Hs<<up, Ws<<up) image */
 int dei2i_spade_prep(int dtype, int N, int Hs, int Ws, int C, int up, const void* x, const float* partial, int chunks, float eps,
                      const void* gb_table, float* mean, float* rstd, float* A, float* B, void* ring, dei2i_stream s);
-/* dei2i_in_finalize / dei2i_bn_finalize_train with an explicit record count per image (records written by a conv epilogue) */
-int dei2i_in_finalize_chunks(int N, int HW, int C, int chunks, const float* partial, float eps, float* mean, float* rstd,
-                             dei2i_stream s);
-int dei2i_bn_finalize_train_chunks(int N, int HW, int C, int chunks, const float* partial, const float* weight, const float* bias,
-                                   float* running_mean, float* running_var, float momentum, float eps, float* mean, float* rstd,
-                                   float* a, float* b, long long* num_batches_tracked, dei2i_stream s);
-/* dei2i_affine_act_fwd that also writes the statistics records of its output: partial (N, dei2i_moments_chunks(HW), 2, C) */
-int dei2i_affine_act_stats_fwd(int dtype, int N, int HW, int C, const void* x, const float* a, const float* b, const void* res,
-                               int act, void* out, float* partial, dei2i_stream s);
 
 /* ---- which kernel served a call: host-side launch counters per MFMA kernel family (tests assert the family, so a
  * fall-through from a tuned kernel to the generic GEMM cannot pass unnoticed).  dei2i_launch_counts copies up to n

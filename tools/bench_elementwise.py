@@ -53,15 +53,15 @@ for (H, W, C) in SHAPES:
     chunks = lib.dei2i_moments_chunks(H * W)
     partial = torch.empty(N, chunks, 4, C, device=DEV)
     timeit(tag + " moments_partial", lambda: lib.dei2i_moments_partial(BF, N, H * W, C, p(x), p(partial), st), T)
-    timeit(tag + " affine_act", lambda: lib.dei2i_affine_act_fwd(BF, pix, C, p(x), p(a), p(b), None, L.ACT_LRELU, p(out), None, 1.0, st), 2 * T)
-    timeit(tag + " affine_act+res", lambda: lib.dei2i_affine_act_fwd(BF, pix, C, p(x), p(a), p(b), p(y), L.ACT_NONE, p(out), None, 1.0, st), 3 * T)
+    timeit(tag + " affine_act", lambda: lib.dei2i_affine_act_fwd(BF, 1, pix, C, p(x), p(a), p(b), None, L.ACT_LRELU, p(out), None, 1.0, st), 2 * T)
+    timeit(tag + " affine_act+res", lambda: lib.dei2i_affine_act_fwd(BF, 1, pix, C, p(x), p(a), p(b), p(y), L.ACT_NONE, p(out), None, 1.0, st), 3 * T)
     timeit(tag + " act_bwd", lambda: lib.dei2i_act_bwd(BF, pix * C, p(dz), p(y), L.ACT_LRELU, p(out), st), 3 * T)
     bchunks = lib.dei2i_bn_bwd_chunks(pix)
     bpart = torch.empty(bchunks, 2, C, device=DEV)
-    dwt, dbs = torch.empty(C, device=DEV), torch.empty(C, device=DEV)
+    dwt, dbs, gsum = torch.empty(C, device=DEV), torch.empty(C, device=DEV), torch.empty(2, C, device=DEV)
     csp = torch.empty(lib.dei2i_colsum_blocks(pix) * C, device=DEV)
-    timeit(tag + " bn_bwd_partial", lambda: lib.dei2i_bn_bwd_partial(BF, pix, C, p(dz), p(y), p(a), p(b), p(mean), p(rstd), L.ACT_LRELU, p(bpart), st), 2 * T)
-    timeit(tag + " bn_bwd_apply", lambda: lib.dei2i_bn_bwd_apply(BF, pix, C, p(dz), p(y), p(a), p(b), p(mean), p(rstd), L.ACT_LRELU, 1, p(bpart), bchunks, p(dwt), p(dbs), None, None, p(out), st), 3 * T)
+    timeit(tag + " bn_bwd_partial", lambda: lib.dei2i_bn_bwd_partial(BF, 1, pix, C, p(dz), p(y), p(a), p(b), p(mean), p(rstd), L.ACT_LRELU, p(bpart), st), 2 * T)
+    timeit(tag + " bn_bwd_apply", lambda: lib.dei2i_bn_bwd_apply(BF, 1, pix, C, p(dz), p(y), p(a), p(b), p(mean), p(rstd), L.ACT_LRELU, 1, p(bpart), bchunks, p(gsum), p(dwt), p(dbs), 0, p(out), st), 3 * T)
     ext = torch.randn(N, H + 2, W + 2, C, device=DEV).bfloat16()
     timeit(tag + " fold_pad reflect1", lambda: lib.dei2i_fold_pad(BF, N, H, W, C, 1, L.PAD_REFLECT, 0, p(ext), None, p(out), st), 2 * T)
     # SPADE (class-mode gamma/beta table), no upsample

@@ -46,13 +46,13 @@ for (H, W, C) in ((64, 64, 256), (128, 128, 128), (256, 256, 64)):
     rstd = torch.rand(C, device=DEV) + 0.5
     bchunks = lib.dei2i_bn_bwd_chunks(pix)
     bpart = torch.zeros(bchunks, 2, C, device=DEV)
-    dwt, dbs = torch.empty(C, device=DEV), torch.empty(C, device=DEV)
+    dwt, dbs, gsum = torch.empty(C, device=DEV), torch.empty(C, device=DEV), torch.empty(2, C, device=DEV)
     for skew in (0, 256, 4096 + 256, 65536 + 2048 + 256, (1 << 20) + 8192 + 512):
         dz = carve((N, H, W, C), 0)
         y = carve((N, H, W, C), skew)
         out = carve((N, H, W, C), 2 * skew)
-        t_bn = timeit(lambda: lib.dei2i_bn_bwd_apply(0, pix, C, p(dz), p(y), p(a), p(b), p(mean), p(rstd), L.ACT_LRELU, 1, p(bpart), bchunks,
-                                                     p(dwt), p(dbs), None, None, p(out), st))
+        t_bn = timeit(lambda: lib.dei2i_bn_bwd_apply(0, 1, pix, C, p(dz), p(y), p(a), p(b), p(mean), p(rstd), L.ACT_LRELU, 1, p(bpart), bchunks,
+                                                     p(gsum), p(dwt), p(dbs), 0, p(out), st))
         t_add = timeit(lambda: torch.add(dz, y, out=out))
         print("%dx%dx%d skew %8d: bn_bwd_apply %6.1f us %5.2f TB/s | torch.add %6.1f us %5.2f TB/s | ptr mod 2MB: %x %x %x" % (
             H, W, C, skew, t_bn, 3 * T / t_bn / 1e6, t_add, 3 * T / t_add / 1e6, dz.data_ptr() % (2 << 20), y.data_ptr() % (2 << 20),
