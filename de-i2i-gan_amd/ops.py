@@ -591,9 +591,15 @@ def _wgrad_scratch(lib, d, device, slot="wgrad"):
 # non-leaf weights (spectral norm's effective weight, concatenated heads / gamma|beta weights) ARE read inside the pass by
 # the next autograd node and stay on the main stream.  The data-parallel reducer makes its all-reduce stream wait for the
 # side stream as well (parallel.GradReducer._launch).
+# The side stream reads its operands -- above all the incoming gradient g -- after the node has returned, and autograd may write
+# into g IN PLACE on the main stream meanwhile: ``ops.add``'s backward hands the same g to the residual branch's conv and to the
+# shortcut, and behind an identity shortcut g lands in the block input's InputBuffer, which adds the other branch's gradient into it
+# (``g.add_(dx)``) when it holds the only reference.  So every side-stream launch keeps its operands referenced until an event
+# behind it on the side stream has completed (or the pass's join): with a second reference autograd adds out of place (same bits).
 wgrad_side_stream = True
 _wgrad_streams = {}
 _wgrad_join_pending = {}         # device -> graph-task id of the pass whose end-of-pass join is queued
+_wgrad_pins = {}                 # device -> [(event on the side stream, operands the side stream reads)], oldest first
 
 
 def wgrad_stream(device):
@@ -606,6 +612,7 @@ def _wgrad_join(device, tid):
         if _wgrad_join_pending.get(device) == tid:
             del _wgrad_join_pending[device]
         side = _wgrad_streams[device]
+        _wgrad_pins.pop(device, None)          # every stream that goes on waits for the side stream below
         if capture_stream is not None and _capturing(side):
             # inside a graph capture only streams of the capture may wait (a wait on the default stream -- not captured -- would
             # invalidate it): the current stream, the capture's own stream and the chain streams the pass forked into it
@@ -677,6 +684,12 @@ def _conv_wgrad(lib, prec, geom, x, g, weight, pro=None, keep=()):
     for t in (x, g, dw) + tuple(keep):                        # the allocator must not hand their memory out before the side stream is done
         if t is not None:
             t.record_stream(side)
+    pins = _wgrad_pins.setdefault(dev, [])
+    while pins and pins[0][0].query():                        # (one stream: events complete in order)
+        pins.pop(0)
+    done = torch.cuda.Event()
+    done.record(side)
+    pins.append((done, (x, g) + tuple(keep)))                 # no in-place write into them until the side stream has read them
     if _wgrad_join_pending.get(dev) != tid:                   # (a pass that raised never ran its callback: its id is stale)
         _wgrad_join_pending[dev] = tid
         torch.autograd.Variable._execution_engine.queue_callback(_wgrad_join(dev, tid))
@@ -1928,9 +1941,31 @@ class _DiffAugAdjoint(torch.autograd.Function):
         return _DiffAug.apply(gg, ctx.tab, ctx.run, 1, None), None, None
 
 
+# Data-parallel stargan-v2 (stargan.Solver under parallel.attach_ddp): each rank holds rows [rank * n, (rank + 1) * n) of the global
+# batch, and the reference augments the whole global batch with one draw per function.  Inside ``diffaug_sharded(rank, world)`` the
+# draws are those of the global batch (utils.diffaug.draw_params(shard=...)) and only the rank's rows are uploaded and applied.
+diffaug_shard = None
+
+
+class diffaug_sharded:
+    def __init__(self, rank: int, world: int):
+        self.shard = (int(rank), int(world))
+
+    def __enter__(self):
+        global diffaug_shard
+        self.prev, diffaug_shard = diffaug_shard, self.shard
+        return self
+
+    def __exit__(self, *exc):
+        global diffaug_shard
+        diffaug_shard = self.prev
+        return False
+
+
 def diff_augment(x, policy=""):
     """DiffAugment(x, policy) of utils/diffaug.py on an NCHW fp32 GPU image batch: the same draws from the global CPU RNG, one upload
-    of the parameter table per call, one or two launches per canonical-order policy run.  ``policy == ""`` returns ``x`` itself."""
+    of the parameter table per call, one or two launches per canonical-order policy run.  ``policy == ""`` returns ``x`` itself.
+    Inside ``diffaug_sharded`` ``x`` is one rank's rows of the global batch (above)."""
     if not policy:
         return x
     from .utils.diffaug import draw_params
@@ -1938,7 +1973,7 @@ def diff_augment(x, policy=""):
     if x.dim() != 4 or x.dtype != torch.float32:
         raise TypeError("diff_augment expects an NCHW fp32 image batch")
     n, _, h, w = x.shape
-    rec, runs = draw_params(policy, n, h, w)
+    rec, runs = draw_params(policy, n, h, w, shard=diffaug_shard)
     host = torch.empty(rec.shape, dtype=torch.int32, pin_memory=True)
     host.copy_(torch.from_numpy(rec))
     tab = host.to(x.device, non_blocking=True)

@@ -147,9 +147,10 @@ class GradReducer:
         self._inflight.append((work, buf if flat else None, grads))
 
     # ---- after backward ----------------------------------------------------------------------------------
-    def reduce(self, net: torch.nn.Module) -> None:
-        """Finish the step's gradient exchange: after this returns (stream-ordered), every ``p.grad`` holds the SUM
-        over ranks.  Use ``FusedAdam.grad_scale = 1/world`` (set by ``attach_ddp``) for the average."""
+    def reduce(self, *nets: torch.nn.Module) -> None:
+        """Finish the step's gradient exchange for the networks one backward pass produced gradients for: after this returns
+        (stream-ordered), every ``p.grad`` holds the SUM over ranks.  Use ``FusedAdam.grad_scale = 1/world`` (set by ``attach_ddp``)
+        for the average."""
         if not self.active:
             return
         t_host = time.perf_counter()
@@ -157,10 +158,11 @@ class GradReducer:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record(torch.cuda.current_stream())
             self._bwd_done.append(ev)
-        if id(net) not in self._attached or not self.overlap:
-            for p in net.parameters():                      # no-overlap path: same bucketing, issued now
-                if p.grad is not None:
-                    self._on_grad_ready(p)
+        for net in nets:
+            if id(net) not in self._attached or not self.overlap:
+                for p in net.parameters():                  # no-overlap path: same bucketing, issued now
+                    if p.grad is not None:
+                        self._on_grad_ready(p)
         self._flush_bucket()
         for work, flat, grads in self._inflight:
             dev = grads[0].device
@@ -243,8 +245,12 @@ class _NullCtx:
 
 
 def attach_ddp(trainer, process_group=None, **kw) -> GradReducer:
-    """Make a DefectGanTrainer data-parallel: gradients are summed across ranks after each backward and averaged
-    inside the fused Adam kernel; generator BatchNorm buffers follow rank 0."""
+    """Make a DefectGanTrainer or a stargan ``Solver`` data-parallel: gradients are summed across ranks after each backward and
+    averaged inside the fused Adam kernel.  DefectGanTrainer: generator BatchNorm buffers follow rank 0.  Solver: see
+    ``_attach_solver``."""
+    from .stargan import Solver
+    if isinstance(trainer, Solver):
+        return _attach_solver(trainer, process_group, **kw)
     red = GradReducer(process_group, **kw)
     release = getattr(trainer, "release_graphs", None)          # (graph_step: the captured step has no collectives)
     if release is not None:
@@ -258,4 +264,26 @@ def attach_ddp(trainer, process_group=None, **kw) -> GradReducer:
         red.attach(mask_token)
         red.broadcast_parameters(mask_token)
     trainer.reducer = red
+    return red
+
+
+def _attach_solver(solver, process_group=None, **kw) -> GradReducer:
+    """stargan-v2: the reducer on the four trained networks; rank 0's parameters of ``nets`` and ``nets_ema`` and rank 0's global CPU
+    RNG state (DiffAugment's draws, and whatever the caller draws from it next) on every rank; 1/world in the four Adams.  Attach
+    before the first iteration (the Adam moments are not exchanged).  ``Solver.train_iteration`` then reduces exactly the gradients each
+    ``step()`` consumes, the discarded ones (D during the G updates, S during the reference-guided one) are not computed."""
+    red = GradReducer(process_group, **kw)
+    for name, net in vars(solver.nets).items():
+        red.attach(net)
+        red.broadcast_parameters(net)
+        getattr(solver.optims, name).grad_scale = 1.0 / red.world
+    for net in vars(solver.nets_ema).values():
+        red.broadcast_parameters(net)
+    if red.world > 1:
+        state = torch.get_rng_state()
+        if dist.get_backend(process_group) == "nccl":          # RCCL moves device tensors only
+            state = state.to(solver.device)
+        dist.broadcast(state, src=0, group=process_group)
+        torch.set_rng_state(state.cpu())
+    solver.reducer = red
     return red

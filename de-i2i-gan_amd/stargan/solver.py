@@ -9,17 +9,47 @@ names, argument meaning and return values (loss tensor + a namespace of floats);
   * Adam with coupled weight decay per network, EMA (beta 0.999) of the generator-side networks.
 
 Not the reference's iteration: ``generator.update_stats()`` is not called (open item), and the w_hpf > 0 / SEAN paths
-(heat-map masks, their downloaded weights) are not built."""
+(heat-map masks, their downloaded weights) are not built.
+
+Data-parallel (``parallel.attach_ddp(solver)``, the reference's ``nn.DataParallel``): every rank holds rows [rank * b, (rank + 1) * b)
+of the same global batch and the ranks together compute what one process computes on the whole batch -- stargan-v2 has no batch
+statistics and every loss term is a mean over samples, so the SUM of the ranks' gradients with 1/world in Adam is the global batch's
+gradient; DiffAugment draws the global batch's parameters on every rank and applies the rank's rows (``ops.diffaug_sharded``); the
+reported losses are the global batch's (``global_means``)."""
+import contextlib
 from types import SimpleNamespace
 
 import torch
+import torch.distributed as dist
 
 from .. import ops
 from ..optim import FusedAdam, ema_lerp_
 
+_reducer = None         # the attached GradReducer while Solver.train_iteration runs data-parallel: the loss reads become global_means
 
-def _floats(*losses):
-    """the values of 0-dim loss tensors, in one device-to-host read"""
+
+def global_means(terms, n, group=None):
+    """Per-rank loss terms (0-dim tensors, each a mean over the rank's n samples) -> the global batch's values as floats, the same on
+    every rank: ONE small SUM all-reduce of the stacked terms and one device-to-host read.  The message also carries n and n * n:
+    sum(n)^2 == world * sum(n^2) holds only when every rank has the same n, and only then is the mean of the ranks' means the global
+    mean (and 1/world the right gradient average).  On a mismatch every rank has received the same sums and raises ValueError, so no
+    rank goes on to a collective the others skip."""
+    world = dist.get_world_size(group)
+    v = torch.stack([t.detach().double() for t in terms])
+    v = torch.cat([v, v.new_tensor([float(n), float(n) * n])])
+    dist.all_reduce(v, op=dist.ReduceOp.SUM, group=group)
+    s = v.tolist()
+    if s[-2] * s[-2] != world * s[-1]:
+        raise ValueError(f"stargan data-parallel: the ranks' local batch sizes differ (sum {s[-2]:.0f}, sum of squares {s[-1]:.0f} over "
+                         f"{world} ranks); every rank must hold the same number of rows of the global batch")
+    return [x / world for x in s[:-2]]
+
+
+def _floats(n, *losses):
+    """the values of 0-dim loss tensors (means over a batch of n), in one device-to-host read -- the global batch's values while the
+    Solver runs data-parallel"""
+    if _reducer is not None:
+        return global_means(losses, n, _reducer.pg)
     return torch.stack([t.detach().float() for t in losses]).tolist()
 
 
@@ -59,7 +89,7 @@ def compute_d_loss(nets, args, x_real, y_org, y_trg, z_trg=None, x_ref=None, mas
     out = nets.discriminator(ops.diff_augment(x_fake, policy), y_trg)
     loss_fake = adv_loss(out, 0)
     loss = loss_real + loss_fake + args.lambda_reg * loss_reg
-    real, fake, reg = _floats(loss_real, loss_fake, loss_reg)
+    real, fake, reg = _floats(x_real.size(0), loss_real, loss_fake, loss_reg)
     return loss, SimpleNamespace(real=real, fake=fake, reg=reg)
 
 
@@ -81,7 +111,7 @@ def compute_g_loss(nets, args, x_real, y_org, y_trg, z_trgs=None, x_refs=None, m
     x_rec = nets.generator(x_fake, s_org, labels=y_org, masks=None)
     loss_cyc = ops.l1(x_rec, x_real)
     loss = loss_adv + args.lambda_sty * loss_sty - args.lambda_ds * loss_ds + args.lambda_cyc * loss_cyc
-    adv, sty, ds, cyc = _floats(loss_adv, loss_sty, loss_ds, loss_cyc)
+    adv, sty, ds, cyc = _floats(x_real.size(0), loss_adv, loss_sty, loss_ds, loss_cyc)
     return loss, SimpleNamespace(adv=adv, sty=sty, ds=ds, cyc=cyc)
 
 
@@ -99,6 +129,7 @@ class Solver:
     def __init__(self, args, nets, nets_ema, device="cuda:0"):
         self.args, self.nets, self.nets_ema, self.device = args, nets, nets_ema, torch.device(device)
         self.initial_lambda_ds = args.lambda_ds          # the lambda_ds decay step is initial / ds_iter (solver.py:311-313)
+        self.reducer = None                              # set by parallel.attach_ddp(): gradient all-reduce across ranks
         for ns in (nets, nets_ema):
             for m in vars(ns).values():
                 m.to(self.device)
@@ -112,27 +143,71 @@ class Solver:
         for opt in vars(self.optims).values():
             opt.zero_grad()
 
+    @contextlib.contextmanager
+    def _data_parallel(self):
+        """while the iteration runs under an active reducer: the loss reads are global_means, DiffAugment draws the global batch"""
+        global _reducer
+        red = self.reducer
+        if red is None or not red.active:
+            yield None
+            return
+        prev, _reducer = _reducer, red
+        try:
+            with ops.diffaug_sharded(dist.get_rank(red.pg), red.world):
+                yield red
+        finally:
+            _reducer = prev
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _frozen(red, *nets):
+        """Under a reducer: the networks' parameters do not require grad while a G loss graph is built and differentiated.  The reference
+        computes their weight gradients there and zeroes them before they are used; here they are not computed, so they never enter a
+        collective (gradients still flow THROUGH the networks)."""
+        params = [p for net in nets for p in net.parameters() if p.requires_grad] if red is not None else []
+        for p in params:
+            p.requires_grad_(False)
+        try:
+            yield
+        finally:
+            for p in params:
+                p.requires_grad_(True)
+
     def train_iteration(self, x_real, y_org, y_trg, x_ref, x_ref2, z_trg, z_trg2):
+        """One iteration on (a rank's rows of) the batch.  Under ``parallel.attach_ddp``: every rank passes rows
+        [rank * b, (rank + 1) * b) of the same global batch (z codes included) and the same b; the returned losses are the global
+        batch's on every rank."""
         args, nets, optims = self.args, self.nets, self.optims
         out = {}
-        d_loss, out["d_latent"] = compute_d_loss(nets, args, x_real, y_org, y_trg, z_trg=z_trg)
-        self._reset_grad()
-        d_loss.backward()
-        optims.discriminator.step()
-        d_loss, out["d_ref"] = compute_d_loss(nets, args, x_real, y_org, y_trg, x_ref=x_ref)
-        self._reset_grad()
-        d_loss.backward()
-        optims.discriminator.step()
-        g_loss, out["g_latent"] = compute_g_loss(nets, args, x_real, y_org, y_trg, z_trgs=[z_trg, z_trg2])
-        self._reset_grad()
-        g_loss.backward()
-        optims.generator.step()
-        optims.mapping_network.step()
-        optims.style_encoder.step()
-        g_loss, out["g_ref"] = compute_g_loss(nets, args, x_real, y_org, y_trg, x_refs=[x_ref, x_ref2])
-        self._reset_grad()
-        g_loss.backward()
-        optims.generator.step()
+        with self._data_parallel() as red:
+            d_loss, out["d_latent"] = compute_d_loss(nets, args, x_real, y_org, y_trg, z_trg=z_trg)
+            self._reset_grad()
+            d_loss.backward()
+            if red is not None:
+                red.reduce(nets.discriminator)
+            optims.discriminator.step()
+            d_loss, out["d_ref"] = compute_d_loss(nets, args, x_real, y_org, y_trg, x_ref=x_ref)
+            self._reset_grad()
+            d_loss.backward()
+            if red is not None:
+                red.reduce(nets.discriminator)
+            optims.discriminator.step()
+            with self._frozen(red, nets.discriminator):
+                g_loss, out["g_latent"] = compute_g_loss(nets, args, x_real, y_org, y_trg, z_trgs=[z_trg, z_trg2])
+                self._reset_grad()
+                g_loss.backward()
+            if red is not None:
+                red.reduce(nets.generator, nets.mapping_network, nets.style_encoder)
+            optims.generator.step()
+            optims.mapping_network.step()
+            optims.style_encoder.step()
+            with self._frozen(red, nets.discriminator, nets.style_encoder):
+                g_loss, out["g_ref"] = compute_g_loss(nets, args, x_real, y_org, y_trg, x_refs=[x_ref, x_ref2])
+                self._reset_grad()
+                g_loss.backward()
+            if red is not None:
+                red.reduce(nets.generator)
+            optims.generator.step()
         for name in ("generator", "mapping_network", "style_encoder"):
             moving_average(getattr(nets, name), getattr(self.nets_ema, name), beta=0.999)
         if args.lambda_ds > 0:

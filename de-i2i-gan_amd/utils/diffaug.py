@@ -97,11 +97,19 @@ def policy_runs(policy):
     return runs
 
 
-def draw_params(policy, n, h, w):
+def draw_params(policy, n, h, w, shard=None):
     """Draw the per-sample parameters of ``policy`` for an (n, *, h, w) batch from the global CPU torch RNG, in the order and shapes
     of the policy functions above (one (n,1,1,1) float draw per color function, two (n,1,1) integer draws per translation / cutout).
     Returns (records, runs): records an int32 (len(runs), n, 8) array of struct dei2i_diffaug_rec (the four floats stored bitwise),
-    runs a list of (has_color, cut_h, cut_w) -- cut_h = cut_w = 0 when the run has no cutout."""
+    runs a list of (has_color, cut_h, cut_w) -- cut_h = cut_w = 0 when the run has no cutout.
+
+    ``shard=(rank, world)``: n is one rank's share of a global batch of n * world rows.  The parameters of the whole global batch are
+    drawn, exactly as the unsharded call for n * world draws them (same RNG consumption), and rows [rank * n, (rank + 1) * n) are
+    returned: ranks that hold the same RNG state see the augmentation one process would apply to the global batch."""
+    if shard is not None:
+        rank, world = shard
+        rec, meta = draw_params(policy, n * world, h, w)
+        return np.ascontiguousarray(rec[:, rank * n:(rank + 1) * n]), meta
     runs = policy_runs(policy)
     rec = np.zeros((len(runs), n, REC_FIELDS), dtype=np.int32)
     f = rec.view(np.float32)
