@@ -12,6 +12,9 @@
 //   grid     : (pixel splits, combos) with combos = ceil(Cout/128) * Cs/64; the combos of one split share an XCD's L2
 //   LDS      : 2 stages x [dy 128 px x 256 B | halo 208 px x 128 B]; both pixel-major (the reduction index is the row),
 //              fragments fetched with ds_read_b64_tr_b16; rows swizzled for its 2 x 32 lane groups (tr_swz)
+//   reads    : per wave and half-tile 8 dy + 36 halo fragments (two ds_read_b64_tr_b16 each) for 72 MFMAs: the half-tile is
+//              walked by halo row, whose fragment serves the tap rows of up to three tile rows (compute_rows; walked by tile
+//              row it was 8 + 72).  The 64 x 64 heads variant (taps split 5 / 4 over two wave groups) walks tile rows.
 //   waves    : 8 = 4 (32-channel blocks of co) x 2 (32-channel blocks of ci); wave (cb, ib) owns dw[cb][ib] for 9 taps
 //   output   : each split's partial block goes to its fp32 slab [Cout][9][Cs] with plain 128-byte stores; the slabs are
 //              summed and un-packed to OIHW by wgrad_reduce_unpack_kernel (wgrad_v2.hip) -- no atomics, deterministic
@@ -252,23 +255,87 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
     return r;
   };
 
-  auto compute = [&](int stage) {
-    const unsigned char* ab = smem + stage * HW_STAGE;
-    const unsigned char* bb = ab + HW_A_BYTES;
-#pragma unroll 2
-    for (int kb = 0; kb < 8; ++kb) {                                      // 16-pixel reduction blocks of the half-tile
-      const int ra = kb * 16 + 8 * lh + tr_q;                             // dy rows ra, ra+4
-      const u32x4 af = tr_read(ab, ra * ROWB_A + (a_colb ^ hw_swz<ROWB_A>(ra)), (ra + 4) * ROWB_A + (a_colb ^ hw_swz<ROWB_A>(ra + 4)));
-      const int py = kb >> 1, px0 = (kb & 1) * 16;
+  typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
+  auto tr_read_lds = [&](unsigned a0, unsigned a1) {                      // two 32-bit LDS addresses -> one 8 x bf16 fragment
+    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(uintptr_t)a0);
+    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(uintptr_t)a1);
+    u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
+    u32x4 r;
+    r.x = l2.x; r.y = l2.y; r.z = h2.x; r.w = h2.y;
+    return r;
+  };
+  // NTG == 1 (a wave owns all nine taps): the half-tile is walked by HALO row.  The halo fragment of (hy, half, tx) serves
+  // tap row ty of tile row py = hy - ty for every ty, so it is read once and multiplied with the (up to three) live dy
+  // fragments: 36 halo + 8 dy fragments per half-tile instead of 72 + 8.  For a fixed tap the (py, half) products still
+  // arrive in ascending py, then half -- the fp32 sums are those of the tile-row walk below, bit for bit.
+  // Every row is (a constant) + lq, and both swizzles depend on the row's two low bits only, so a read's address is one of
+  // five per-lane bases (dy; halo by (constant & 3)) plus an immediate offset (< 64 KB).  The bases are made opaque per call:
+  // left to itself the compiler materialises all 88 addresses in registers and spills.
+  const int lq = 8 * lh + tr_q;
+  const int a_lane = lq * ROWB_A + (a_colb ^ hw_swz<ROWB_A>(lq));
+  int b_lane[4];
 #pragma unroll
-      for (int t = 0; t < TPW; ++t) {
-        const int tap = tap0 + t;                                         // wave-uniform
-        if (NTG > 1 && tap >= 9) break;
-        const int ty = tap / 3, tx = tap - ty * 3;
-        const int rb = (py + ty) * HW_HWD + px0 + tx + 8 * lh + tr_q;     // halo pixels rb, rb+4
-        const u32x4 bf = tr_read(bb, rb * ROWB_B + (b_colb ^ hw_swz<ROWB_B>(rb)), (rb + 4) * ROWB_B + (b_colb ^ hw_swz<ROWB_B>(rb + 4)));
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bf), acc[t], 0, 0, 0);
+  for (int k = 0; k < 4; ++k) b_lane[k] = lq * ROWB_B + (b_colb ^ hw_swz<ROWB_B>(k + lq));
+  auto compute_rows = [&](int stage) {
+    if constexpr (NTG == 1) {
+      unsigned ab = smem_lds + stage * HW_STAGE + a_lane;                 // 32-bit LDS addresses
+      unsigned bk[4];
+      asm volatile("" : "+v"(ab));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        bk[k] = smem_lds + stage * HW_STAGE + HW_A_BYTES + b_lane[k];
+        asm volatile("" : "+v"(bk[k]));
       }
+      u32x4 af[3][2];                                                       // dy fragments of tile rows hy, hy-1, hy-2
+#pragma unroll
+      for (int hy = 0; hy < HW_HH; ++hy) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          if (hy < HW_TH) {
+            const int ra = (hy * 2 + half) * 16;                            // dy rows ra + lq, + 4
+            af[hy % 3][half] = tr_read_lds(ab + ra * ROWB_A, ab + (ra + 4) * ROWB_A);
+          }
+          u32x4 bf[3];
+#pragma unroll
+          for (int tx = 0; tx < 3; ++tx) {
+            const int rb = hy * HW_HWD + half * 16 + tx;                    // halo pixels rb + lq, + 4
+            bf[tx] = tr_read_lds(bk[rb & 3] + rb * ROWB_B, bk[rb & 3] + (rb + 4) * ROWB_B);
+          }
+#pragma unroll
+          for (int ty = 0; ty < 3; ++ty) {
+            const int py = hy - ty;
+            if (py < 0 || py >= HW_TH) continue;
+#pragma unroll
+            for (int tx = 0; tx < 3; ++tx)
+              acc[3 * ty + tx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[py % 3][half]),
+                                                                         __builtin_bit_cast(bf16x8, bf[tx]), acc[3 * ty + tx], 0, 0, 0);
+          }
+        }
+      }
+    }
+  };
+
+  auto compute = [&](int stage) {
+    if constexpr (NTG > 1) {                                              // taps split 5 / 4 over two wave groups: by tile row
+      const unsigned char* ab = smem + stage * HW_STAGE;
+      const unsigned char* bb = ab + HW_A_BYTES;
+#pragma unroll 2
+      for (int kb = 0; kb < 8; ++kb) {                                    // 16-pixel reduction blocks of the half-tile
+        const int ra = kb * 16 + 8 * lh + tr_q;                           // dy rows ra, ra+4
+        const u32x4 af = tr_read(ab, ra * ROWB_A + (a_colb ^ hw_swz<ROWB_A>(ra)), (ra + 4) * ROWB_A + (a_colb ^ hw_swz<ROWB_A>(ra + 4)));
+        const int py = kb >> 1, px0 = (kb & 1) * 16;
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) {
+          const int tap = tap0 + t;                                       // wave-uniform
+          if (tap >= 9) break;
+          const int ty = tap / 3, tx = tap - ty * 3;
+          const int rb = (py + ty) * HW_HWD + px0 + tx + 8 * lh + tr_q;   // halo pixels rb, rb+4
+          const u32x4 bf = tr_read(bb, rb * ROWB_B + (b_colb ^ hw_swz<ROWB_B>(rb)), (rb + 4) * ROWB_B + (b_colb ^ hw_swz<ROWB_B>(rb + 4)));
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bf), acc[t], 0, 0, 0);
+        }
+      }
+    } else {
+      compute_rows(stage);
     }
   };
 
