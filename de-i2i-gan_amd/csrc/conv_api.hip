@@ -260,10 +260,10 @@ int dei2i_pack_weight_fwd(const dei2i_conv* c, const float* w, void* packed, dei
   hipStream_t st = (hipStream_t)s;
   const size_t total = dei2i_packed_fwd_elems(c);
   const unsigned grid = grid_for(total, 256);
-  if (c->dtype == DT_BF16)
-    hipLaunchKernelGGL(pack_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, w, (bf16_t*)packed, c->Cout, c->Cin, c->CinS, c->kh, c->kw);
-  else
-    hipLaunchKernelGGL(pack_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, w, (float*)packed, c->Cout, c->Cin, c->CinS, c->kh, c->kw);
+  by_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(pack_fwd_kernel<T>, dim3(grid), dim3(256), 0, st, w, (T*)packed, c->Cout, c->Cin, c->CinS, c->kh, c->kw);
+  });
   return (int)hipGetLastError();
 }
 
@@ -279,12 +279,11 @@ int dei2i_pack_weight_dgrad(const dei2i_conv* c, const float* w, void* packed, d
       if (total == 0) continue;
       const unsigned grid = grid_for(total, 256);
       void* dst = (char*)packed + off * esz;
-      if (c->dtype == DT_BF16)
-        hipLaunchKernelGGL(pack_dgrad_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, w, (bf16_t*)dst, c->Cout, c->Cin, c->CoutS,
-                           c->kh, c->kw, c->stride, ay, ax, th, tw);
-      else
-        hipLaunchKernelGGL(pack_dgrad_kernel<float>, dim3(grid), dim3(256), 0, st, w, (float*)dst, c->Cout, c->Cin, c->CoutS,
-                           c->kh, c->kw, c->stride, ay, ax, th, tw);
+      by_dtype(c->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(pack_dgrad_kernel<T>, dim3(grid), dim3(256), 0, st, w, (T*)dst, c->Cout, c->Cin, c->CoutS, c->kh, c->kw,
+                           c->stride, ay, ax, th, tw);
+      });
       off += total;
     }
   return (int)hipGetLastError();
@@ -318,21 +317,19 @@ int dei2i_pack_weight_both(const dei2i_conv* c, const float* w, void* packed_fwd
                           PT_CO * PT_MAXTAPS * PT_ROW * (int)sizeof(float));
       attr_done = true;
     }
-    if (c->dtype == DT_BF16)
-      hipLaunchKernelGGL(pack_tiled_kernel<bf16_t>, tg, dim3(256), plds, (hipStream_t)s, w, (bf16_t*)packed_fwd, (bf16_t*)packed_dgrad, pa,
-                         c->Cout, c->Cin, c->CinS, c->CoutS, c->kh, c->kw, c->stride);
-    else
-      hipLaunchKernelGGL(pack_tiled_kernel<float>, tg, dim3(256), plds, (hipStream_t)s, w, (float*)packed_fwd, (float*)packed_dgrad, pa,
-                         c->Cout, c->Cin, c->CinS, c->CoutS, c->kh, c->kw, c->stride);
+    by_dtype(c->dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(pack_tiled_kernel<T>, tg, dim3(256), plds, (hipStream_t)s, w, (T*)packed_fwd, (T*)packed_dgrad, pa, c->Cout,
+                         c->Cin, c->CinS, c->CoutS, c->kh, c->kw, c->stride);
+    });
     return (int)hipGetLastError();
   }
   const unsigned grid = grid_for((size_t)(pa.fwd_total + off), 256);
-  if (c->dtype == DT_BF16)
-    hipLaunchKernelGGL(pack_all_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, w, (bf16_t*)packed_fwd, (bf16_t*)packed_dgrad,
-                       pa, c->Cout, c->Cin, c->CinS, c->CoutS, c->kh, c->kw, c->stride);
-  else
-    hipLaunchKernelGGL(pack_all_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, w, (float*)packed_fwd, (float*)packed_dgrad,
-                       pa, c->Cout, c->Cin, c->CinS, c->CoutS, c->kh, c->kw, c->stride);
+  by_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(pack_all_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)s, w, (T*)packed_fwd, (T*)packed_dgrad, pa, c->Cout,
+                       c->Cin, c->CinS, c->CoutS, c->kh, c->kw, c->stride);
+  });
   return (int)hipGetLastError();
 }
 

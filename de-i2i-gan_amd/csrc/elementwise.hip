@@ -320,12 +320,11 @@ int dei2i_nchw_to_nhwc_resize(int dtype, int N, int C, int hs, int ws, int H, in
   if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || hs <= 0 || ws <= 0 || Cs < C || Cs % vec_of(dtype) || !src || !dst)
     return DEI2I_ERR_BAD_ARG;
   const size_t total = (size_t)N * H * W * (Cs / vec_of(dtype));
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, src,
-                       (bf16_t*)dst, N, C, hs, ws, H, W, Cs);
-  else
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, src,
-                       (float*)dst, N, C, hs, ws, H, W, Cs);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, src, (T*)dst, N, C,
+                       hs, ws, H, W, Cs);
+  });
   return (int)hipGetLastError();
 }
 
@@ -336,12 +335,11 @@ int dei2i_nchw_to_nhwc(int dtype, int N, int C, int H, int W, int Cs, const floa
 int dei2i_nhwc_to_nchw(int dtype, int N, int C, int H, int W, int Cs, const void* src, float* dst, dei2i_stream s) {
   if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || Cs < C || !src || !dst) return DEI2I_ERR_BAD_ARG;
   const size_t total = (size_t)N * C * H * W;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const bf16_t*)src, dst, N, C, H, W, Cs);
-  else
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const float*)src, dst, N, C, H, W, Cs);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, (const T*)src, dst,
+                       N, C, H, W, Cs);
+  });
   return (int)hipGetLastError();
 }
 
@@ -357,13 +355,15 @@ int dei2i_affine_act_fwd(int dtype, int groups, size_t pixels, int C, const void
   const bool inv = (256 % cv) == 0;
   const unsigned grid = grid_for(nvec, 256, EW_CAP);
   hipStream_t st = (hipStream_t)s;
-  if (dtype == DT_BF16) {
-    if (inv) hipLaunchKernelGGL((affine_act_kernel<bf16_t, true>), dim3(grid, groups), dim3(256), 0, st, (const bf16_t*)x, a, b, (const bf16_t*)res, (bf16_t*)out, nvec, cv, act, o8, e4m3_scale);
-    else hipLaunchKernelGGL((affine_act_kernel<bf16_t, false>), dim3(grid, groups), dim3(256), 0, st, (const bf16_t*)x, a, b, (const bf16_t*)res, (bf16_t*)out, nvec, cv, act, o8, e4m3_scale);
-  } else {
-    if (inv) hipLaunchKernelGGL((affine_act_kernel<float, true>), dim3(grid, groups), dim3(256), 0, st, (const float*)x, a, b, (const float*)res, (float*)out, nvec, cv, act, o8, e4m3_scale);
-    else hipLaunchKernelGGL((affine_act_kernel<float, false>), dim3(grid, groups), dim3(256), 0, st, (const float*)x, a, b, (const float*)res, (float*)out, nvec, cv, act, o8, e4m3_scale);
-  }
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (inv)
+      hipLaunchKernelGGL((affine_act_kernel<T, true>), dim3(grid, groups), dim3(256), 0, st, (const T*)x, a, b, (const T*)res, (T*)out,
+                         nvec, cv, act, o8, e4m3_scale);
+    else
+      hipLaunchKernelGGL((affine_act_kernel<T, false>), dim3(grid, groups), dim3(256), 0, st, (const T*)x, a, b, (const T*)res, (T*)out,
+                         nvec, cv, act, o8, e4m3_scale);
+  });
   return (int)hipGetLastError();
 }
 
@@ -377,12 +377,11 @@ int dei2i_affine_act_img_fwd(int dtype, int N, int HW, int C, const void* x, con
   unsigned blocks = (unsigned)std::min<size_t>((nvec_img + 255) / 256, 512);
   if (cv > 256) blocks = (blocks / (cv / 256)) * (cv / 256);
   if (blocks < 1) blocks = cv > 256 ? cv / 256 : 1;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(affine_act_img_kernel<bf16_t>, dim3(blocks, N), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, A, B, (bf16_t*)out,
-                       nvec_img, cv, slope);
-  else
-    hipLaunchKernelGGL(affine_act_img_kernel<float>, dim3(blocks, N), dim3(256), 0, (hipStream_t)s, (const float*)x, A, B, (float*)out,
-                       nvec_img, cv, slope);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(affine_act_img_kernel<T>, dim3(blocks, N), dim3(256), 0, (hipStream_t)s, (const T*)x, A, B, (T*)out, nvec_img,
+                       cv, slope);
+  });
   return (int)hipGetLastError();
 }
 
@@ -396,12 +395,11 @@ int dei2i_spade_act_fwd(int dtype, int N, int H, int W, int C, int up, const voi
   if (up && ((H | W) & 1)) return DEI2I_ERR_BAD_ARG;
   if (gb_mode == 1 && (H < 4 || W < 4)) return DEI2I_ERR_BAD_ARG;
   const size_t total = (size_t)N * H * W * (C / vec);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(spade_act_kernel<bf16_t>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const bf16_t*)x, mean, rstd, (const bf16_t*)gb, (bf16_t*)out, N, H, W, C, up, gb_mode, o8, e4m3_scale);
-  else
-    hipLaunchKernelGGL(spade_act_kernel<float>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const float*)x, mean, rstd, (const float*)gb, (float*)out, N, H, W, C, up, gb_mode, o8, e4m3_scale);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(spade_act_kernel<T>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, (const T*)x, mean, rstd,
+                       (const T*)gb, (T*)out, N, H, W, C, up, gb_mode, o8, e4m3_scale);
+  });
   return (int)hipGetLastError();
 }
 
@@ -409,12 +407,11 @@ int dei2i_act_bwd(int dtype, size_t n, const void* dz, const void* z, int act, v
   const int vec = vec_of(dtype);
   if (n == 0 || n % vec || !dz || !z || !g) return DEI2I_ERR_BAD_ARG;
   const size_t nvec = n / vec;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3(grid_for(nvec, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const bf16_t*)dz, (const bf16_t*)z, (bf16_t*)g, nvec, act);
-  else
-    hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(grid_for(nvec, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const float*)dz, (const float*)z, (float*)g, nvec, act);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(grid_for(nvec, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, (const T*)dz, (const T*)z,
+                       (T*)g, nvec, act);
+  });
   return (int)hipGetLastError();
 }
 
@@ -422,12 +419,11 @@ int dei2i_compose_fwd(int dtype, int N, int H, int W, int Cs, const void* raw, c
                       dei2i_stream s) {
   if (N <= 0 || H <= 0 || W <= 0 || Cs < 4 || Cs % vec_of(dtype) || !raw || !x_in || !out || !prob) return DEI2I_ERR_BAD_ARG;
   const size_t total = (size_t)N * H * W;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(compose_fwd_kernel<bf16_t>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const bf16_t*)raw, x_in, out, prob, N, H * W, Cs);
-  else
-    hipLaunchKernelGGL(compose_fwd_kernel<float>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const float*)raw, x_in, out, prob, N, H * W, Cs);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(compose_fwd_kernel<T>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, (const T*)raw, x_in,
+                       out, prob, N, H * W, Cs);
+  });
   return (int)hipGetLastError();
 }
 
@@ -435,12 +431,11 @@ int dei2i_compose_bwd(int dtype, int N, int H, int W, int Cs, const void* raw, c
                       const float* d_prob, void* d_raw, float* d_x, dei2i_stream s) {
   if (N <= 0 || H <= 0 || W <= 0 || Cs < 4 || Cs % vec_of(dtype) || !raw || !x_in || !d_raw) return DEI2I_ERR_BAD_ARG;
   const size_t total = (size_t)N * H * W;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(compose_bwd_kernel<bf16_t>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const bf16_t*)raw, x_in, d_out, d_prob, (bf16_t*)d_raw, d_x, N, H * W, Cs);
-  else
-    hipLaunchKernelGGL(compose_bwd_kernel<float>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s,
-                       (const float*)raw, x_in, d_out, d_prob, (float*)d_raw, d_x, N, H * W, Cs);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(compose_bwd_kernel<T>, dim3(grid_for(total, 256, EW_CAP)), dim3(256), 0, (hipStream_t)s, (const T*)raw, x_in,
+                       d_out, d_prob, (T*)d_raw, d_x, N, H * W, Cs);
+  });
   return (int)hipGetLastError();
 }
 
@@ -452,13 +447,11 @@ int dei2i_nan_guard(int dtype, size_t n, void* x, int* flag, dei2i_stream s) {
   if (e != hipSuccess) return (int)e;
   const size_t nvec = n / vec;
   const unsigned grid = grid_for(nvec, 256, EW_CAP);
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(nan_flag_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, nvec, flag);
-    hipLaunchKernelGGL(nan_to_num_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (bf16_t*)x, nvec, (const int*)flag);
-  } else {
-    hipLaunchKernelGGL(nan_flag_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, nvec, flag);
-    hipLaunchKernelGGL(nan_to_num_kernel<float>, dim3(grid), dim3(256), 0, st, (float*)x, nvec, (const int*)flag);
-  }
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(nan_flag_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)x, nvec, flag);
+    hipLaunchKernelGGL(nan_to_num_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)x, nvec, (const int*)flag);
+  });
   return (int)hipGetLastError();
 }
 
@@ -467,12 +460,11 @@ int dei2i_avgpool2_fwd(int dtype, int N, int H, int W, int C, const void* x, voi
   const int vec = vec_of(dtype);
   if (N <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C <= 0 || C % vec || !x || !out) return DEI2I_ERR_BAD_ARG;
   const size_t total = (size_t)N * (H / 2) * (W / 2) * (C / vec);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(avgpool2_fwd_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (bf16_t*)out,
-                       N, H / 2, W / 2, C);
-  else
-    hipLaunchKernelGGL(avgpool2_fwd_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)s, (const float*)x, (float*)out, N,
-                       H / 2, W / 2, C);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(avgpool2_fwd_kernel<T>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)out, N, H / 2,
+                       W / 2, C);
+  });
   return (int)hipGetLastError();
 }
 
@@ -480,12 +472,11 @@ int dei2i_avgpool2_bwd(int dtype, int N, int H, int W, int C, const void* dout, 
   const int vec = vec_of(dtype);
   if (N <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C <= 0 || C % vec || !dout || !dx) return DEI2I_ERR_BAD_ARG;
   const size_t total = (size_t)N * (H / 2) * (W / 2) * (C / vec);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(avgpool2_bwd_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dout, (bf16_t*)dx,
-                       N, H / 2, W / 2, C);
-  else
-    hipLaunchKernelGGL(avgpool2_bwd_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)s, (const float*)dout, (float*)dx, N,
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(avgpool2_bwd_kernel<T>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)s, (const T*)dout, (T*)dx, N,
                        H / 2, W / 2, C);
+  });
   return (int)hipGetLastError();
 }
 

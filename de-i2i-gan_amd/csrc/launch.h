@@ -71,6 +71,14 @@ hipError_t wgrad_thin(const GatherDesc& g, const void* src, const void* dy, int 
 hipError_t wgrad_reduce_unpack(float* slabs, int nsplit, long long slab_elems, float* dw, int Cout, int Cin, int CinS,
                                int taps, int accumulate, hipStream_t st);
 
+// A typed launch written once: f gets a value of the element type (bf16_t for DT_BF16, float for every other code) --
+//   by_dtype(dtype, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL(k<T>, ..., (const T*)x, ...); });
+template <typename F>
+static inline void by_dtype(int dtype, F&& f) {
+  if (dtype == DT_BF16) f(bf16_t{});
+  else f(float{});
+}
+
 inline unsigned grid_for(size_t work_items, int threads, unsigned cap = 256u * 8u) {
   size_t b = (work_items + threads - 1) / threads;
   if (b < 1) b = 1;

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) void spade_bwd_partial_kernel(const T* __restr
                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                 const T* __restrict__ gb, int gb_mode,
                                                                 T* __restrict__ dgb_dense, float* __restrict__ partial, int H,
-                                                                int W, int C, int up, int chunks, float slope = 0.f) {
+                                                                int W, int C, int up, int chunks, float slope) {
   constexpr int VEC = Elem<T>::VEC;
   extern __shared__ float smem[];
   const int cv = C / VEC, rpp = 256 / cv;
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(256) void spade_bwd_partial_kernel(const T* __restr
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         const float xh = (xv[e] - mv[e]) * rv[e];
-        const float g = fmaf(xh, 1.f + gm[e], bt[e]) > 0.f ? d[e] : slope * d[e];      // (slope: 0 = ReLU -- SPADE; dei2i_in_act_bwd: any)
+        const float g = fmaf(xh, 1.f + gm[e], bt[e]) > 0.f ? d[e] : slope * d[e];      // (slope: 0 = ReLU -- SPADE; the InstanceNorm ops: any)
         const float dxh = g * (1.f + gm[e]);
         dg[e] = g * xh;
         db[e] = g;
@@ -395,7 +395,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void spade_bwd_border_kernel(const T* __restrict__ dz, const T* __restrict__ x,
                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                const T* __restrict__ gb, T* __restrict__ dgb_cls, int H,
-                                                               int W, int C, int up, float slope = 0.f) {
+                                                               int W, int C, int up, float slope) {
   constexpr int VEC = Elem<T>::VEC;
   extern __shared__ float smem[];
   const int cls = blockIdx.x, n = blockIdx.y;
@@ -466,7 +466,7 @@ template <typename T>
 __global__ void spade_bwd_apply_kernel(const T* __restrict__ dz, const T* __restrict__ x, const float* __restrict__ mean,
                                        const float* __restrict__ rstd, const T* __restrict__ gb, int gb_mode,
                                        const float* __restrict__ coef, const T* __restrict__ addend, T* __restrict__ dx, int N,
-                                       int H, int W, int C, int up, float slope = 0.f) {
+                                       int H, int W, int C, int up, float slope) {
   constexpr int VEC = Elem<T>::VEC;
   const int cv = C / VEC;
   const int Hs = H >> up, Ws = W >> up;
@@ -793,10 +793,10 @@ __global__ __launch_bounds__(256) void spade_prep_kernel(const T* __restrict__ x
 using namespace dei2i;
 
 static inline bool cv_ok(int dtype, int C) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
+  const int vec = vec_of(dtype);
   return C > 0 && C % vec == 0 && C / vec <= 256;
 }
-static inline size_t combine_lds(int dtype, int nv) { return (size_t)nv * (dtype == DT_BF16 ? 8 : 4) * 256 * sizeof(float); }
+static inline size_t combine_lds(int dtype, int nv) { return (size_t)nv * vec_of(dtype) * 256 * sizeof(float); }
 
 extern "C" {
 
@@ -810,12 +810,11 @@ int dei2i_moments_chunks(int HW) {            // per image: >= 64 rows per workg
 int dei2i_moments_partial(int dtype, int N, int HW, int C, const void* x, float* partial, dei2i_stream s) {
   if (N <= 0 || HW <= 0 || !cv_ok(dtype, C) || !x || !partial) return DEI2I_ERR_BAD_ARG;
   const int chunks = dei2i_moments_chunks(HW);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(moments_partial_kernel<bf16_t>, dim3(chunks, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const bf16_t*)x, partial, HW, C, chunks);
-  else
-    hipLaunchKernelGGL(moments_partial_kernel<float>, dim3(chunks, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const float*)x, partial, HW, C, chunks);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(moments_partial_kernel<T>, dim3(chunks, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s, (const T*)x,
+                       partial, HW, C, chunks);
+  });
   return (int)hipGetLastError();
 }
 
@@ -835,12 +834,11 @@ int dei2i_affine_act_stats_fwd(int dtype, int groups, int N, int HW, int C, cons
                                const void* res, int act, void* out, float* partial, dei2i_stream s) {
   if (groups <= 0 || N <= 0 || N % groups != 0 || HW <= 0 || !cv_ok(dtype, C) || !x || !a || !b || !out || !partial) return DEI2I_ERR_BAD_ARG;
   const int chunks = dei2i_moments_chunks(HW);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(affine_act_stats_kernel<bf16_t>, dim3(chunks, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const bf16_t*)x, a, b, (const bf16_t*)res, (bf16_t*)out, partial, HW, C, chunks, act, N / groups);
-  else
-    hipLaunchKernelGGL(affine_act_stats_kernel<float>, dim3(chunks, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const float*)x, a, b, (const float*)res, (float*)out, partial, HW, C, chunks, act, N / groups);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(affine_act_stats_kernel<T>, dim3(chunks, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s, (const T*)x, a,
+                       b, (const T*)res, (T*)out, partial, HW, C, chunks, act, N / groups);
+  });
   return (int)hipGetLastError();
 }
 
@@ -852,18 +850,17 @@ int dei2i_spade_prep(int dtype, int N, int Hs, int Ws, int C, int up, const void
       !rstd || !A || !B)
     return DEI2I_ERR_BAD_ARG;
   if (ring != nullptr && ((Hs << up) < 4 || (Ws << up) < 4)) return DEI2I_ERR_BAD_ARG;
-  const int vec = dtype == DT_BF16 ? 8 : 4;
+  const int vec = vec_of(dtype);
   const int work = ring != nullptr ? ring_pixels(Hs << up, Ws << up) * (C / vec) : 0;
   int blocks = (work + 256 * 8 - 1) / (256 * 8);
   if (blocks < 1) blocks = 1;
   if (blocks > 64) blocks = 64;
   const size_t lds = 2 * (size_t)C * sizeof(float);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(spade_prep_kernel<bf16_t>, dim3(blocks, N), dim3(256), lds, (hipStream_t)s, (const bf16_t*)x, partial,
-                       (const bf16_t*)gb_table, mean, rstd, A, B, (bf16_t*)ring, Hs, Ws, C, up, chunks, (double)Hs * (double)Ws, eps);
-  else
-    hipLaunchKernelGGL(spade_prep_kernel<float>, dim3(blocks, N), dim3(256), lds, (hipStream_t)s, (const float*)x, partial,
-                       (const float*)gb_table, mean, rstd, A, B, (float*)ring, Hs, Ws, C, up, chunks, (double)Hs * (double)Ws, eps);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(spade_prep_kernel<T>, dim3(blocks, N), dim3(256), lds, (hipStream_t)s, (const T*)x, partial,
+                       (const T*)gb_table, mean, rstd, A, B, (T*)ring, Hs, Ws, C, up, chunks, (double)Hs * (double)Ws, eps);
+  });
   return (int)hipGetLastError();
 }
 
@@ -894,10 +891,10 @@ int dei2i_colsum(int dtype, size_t rows, int C, const void* g, float* partial, f
   if (rows == 0 || !cv_ok(dtype, C) || !g || !partial || !out) return DEI2I_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)s;
   const int blocks = dei2i_colsum_blocks(rows);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), combine_lds(dtype, 1), st, (const bf16_t*)g, partial, rows, C);
-  else
-    hipLaunchKernelGGL(colsum_kernel<float>, dim3((unsigned)blocks), dim3(256), combine_lds(dtype, 1), st, (const float*)g, partial, rows, C);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(colsum_kernel<T>, dim3((unsigned)blocks), dim3(256), combine_lds(dtype, 1), st, (const T*)g, partial, rows, C);
+  });
   hipLaunchKernelGGL(colsum_finalize_kernel, dim3((C + 15) / 16), dim3(256), 0, st, (const float*)partial, blocks, C, out);
   return (int)hipGetLastError();
 }
@@ -913,12 +910,11 @@ int dei2i_bn_bwd_partial(int dtype, int groups, size_t pixels, int C, const void
                          const float* mean, const float* rstd, int act, float* partial, dei2i_stream s) {
   if (groups <= 0 || pixels == 0 || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !partial) return DEI2I_ERR_BAD_ARG;
   const int chunks = dei2i_bn_bwd_chunks(pixels);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<bf16_t>, dim3(chunks, groups), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const bf16_t*)dz, (const bf16_t*)y, a, b, mean, rstd, act, partial, pixels, C, chunks);
-  else
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<float>, dim3(chunks, groups), dim3(256), combine_lds(dtype, 2), (hipStream_t)s,
-                       (const float*)dz, (const float*)y, a, b, mean, rstd, act, partial, pixels, C, chunks);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(bn_bwd_partial_kernel<T>, dim3(chunks, groups), dim3(256), combine_lds(dtype, 2), (hipStream_t)s, (const T*)dz,
+                       (const T*)y, a, b, mean, rstd, act, partial, pixels, C, chunks);
+  });
   return (int)hipGetLastError();
 }
 
@@ -928,7 +924,7 @@ int dei2i_bn_bwd_partial(int dtype, int groups, size_t pixels, int C, const void
 int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
                        const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
                        float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
+  const int vec = vec_of(dtype);
   if (groups <= 0 || pixels == 0 || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !partial || !group_sums || !dweight ||
       !dbias || !dy || chunks <= 0)
     return DEI2I_ERR_BAD_ARG;
@@ -942,60 +938,59 @@ int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* 
   const bool invc = (256 % cv) == 0;
   const float* gw = group_sums;
   const float* gb = group_sums + C;
-  if (dtype == DT_BF16) {
-    if (invc) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), dim3(grid, groups), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)y, a, b, mean, rstd, act, train, gw, gb, inv, (bf16_t*)dy, nvec, cv, 2 * C);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false>), dim3(grid, groups), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)y, a, b, mean, rstd, act, train, gw, gb, inv, (bf16_t*)dy, nvec, cv, 2 * C);
-  } else {
-    if (invc) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), dim3(grid, groups), dim3(256), 0, st, (const float*)dz, (const float*)y, a, b, mean, rstd, act, train, gw, gb, inv, (float*)dy, nvec, cv, 2 * C);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), dim3(grid, groups), dim3(256), 0, st, (const float*)dz, (const float*)y, a, b, mean, rstd, act, train, gw, gb, inv, (float*)dy, nvec, cv, 2 * C);
-  }
-  return (int)hipGetLastError();
-}
-
-int dei2i_spade_bwd_partial(int dtype, int N, int H, int W, int C, int up, const void* dz, const void* x, const float* mean,
-                            const float* rstd, const void* gb, int gb_mode, void* dgb, float* partial, dei2i_stream s) {
-  if (N <= 0 || H <= 0 || W <= 0 || !cv_ok(dtype, C) || up < 0 || up > 1 || !dz || !x || !mean || !rstd || !gb || !dgb || !partial)
-    return DEI2I_ERR_BAD_ARG;
-  if (gb_mode == 1 && (H < 4 || W < 4)) return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  const int chunks = dei2i_moments_chunks(H * W);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(spade_bwd_partial_kernel<bf16_t>, dim3(chunks, N), dim3(256), combine_lds(dtype, 4), st,
-                       (const bf16_t*)dz, (const bf16_t*)x, mean, rstd, (const bf16_t*)gb, gb_mode,
-                       gb_mode == 0 ? (bf16_t*)dgb : (bf16_t*)nullptr, partial, H, W, C, up, chunks);
-  else
-    hipLaunchKernelGGL(spade_bwd_partial_kernel<float>, dim3(chunks, N), dim3(256), combine_lds(dtype, 4), st,
-                       (const float*)dz, (const float*)x, mean, rstd, (const float*)gb, gb_mode,
-                       gb_mode == 0 ? (float*)dgb : (float*)nullptr, partial, H, W, C, up, chunks);
-  if (gb_mode == 1) {
-    if (dtype == DT_BF16)
-      hipLaunchKernelGGL(spade_bwd_border_kernel<bf16_t>, dim3(25, N), dim3(256), combine_lds(dtype, 2), st, (const bf16_t*)dz,
-                         (const bf16_t*)x, mean, rstd, (const bf16_t*)gb, (bf16_t*)dgb, H, W, C, up);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (invc)
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(grid, groups), dim3(256), 0, st, (const T*)dz, (const T*)y, a, b, mean,
+                         rstd, act, train, gw, gb, inv, (T*)dy, nvec, cv, 2 * C);
     else
-      hipLaunchKernelGGL(spade_bwd_border_kernel<float>, dim3(25, N), dim3(256), combine_lds(dtype, 2), st, (const float*)dz,
-                         (const float*)x, mean, rstd, (const float*)gb, (float*)dgb, H, W, C, up);
-  }
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(grid, groups), dim3(256), 0, st, (const T*)dz, (const T*)y, a, b, mean,
+                         rstd, act, train, gw, gb, inv, (T*)dy, nvec, cv, 2 * C);
+  });
   return (int)hipGetLastError();
 }
 
+/* The backward of the SPADE family -- SPADE + ReLU (slope 0), InstanceNorm + act and AdaIN / affine InstanceNorm + act (class mode
+ * on an all-zero / a replicated (N,5,5,2C) table, the activation's negative slope: 0.2 LeakyReLU, 1 none) -- is these three entry
+ * points; each of the four kernels is launched from one place.
+ * dgb: the dense (N,H,W,2C) gradient (gb_mode 0, written here), or the class table's (gb_mode 1: its border classes here, the
+ * interior class by dei2i_spade_bwd_apply) -- or NULL in class mode when no table gradient is wanted: the border kernel is then
+ * not launched, and dei2i_spade_bwd_apply is given dgb_cls = NULL as well. */
+int dei2i_spade_bwd_partial(int dtype, int N, int H, int W, int C, int up, const void* dz, const void* x, const float* mean,
+                            const float* rstd, const void* gb, int gb_mode, float slope, void* dgb, float* partial, dei2i_stream s) {
+  if (N <= 0 || H <= 0 || W <= 0 || !cv_ok(dtype, C) || up < 0 || up > 1 || !dz || !x || !mean || !rstd || !gb || !partial)
+    return DEI2I_ERR_BAD_ARG;
+  if (gb_mode != 1 && !dgb) return DEI2I_ERR_BAD_ARG;        // dense mode: the streaming pass stores the gradient itself
+  if (gb_mode == 1 && (H < 4 || W < 4)) return DEI2I_ERR_BAD_ARG;
+  const int chunks = dei2i_moments_chunks(H * W);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(spade_bwd_partial_kernel<T>, dim3(chunks, N), dim3(256), combine_lds(dtype, 4), (hipStream_t)s, (const T*)dz,
+                       (const T*)x, mean, rstd, (const T*)gb, gb_mode, gb_mode == 0 ? (T*)dgb : (T*)nullptr, partial, H, W, C, up,
+                       chunks, slope);
+  });
+  if (gb_mode == 1 && dgb != nullptr) return dei2i_spade_bwd_border(dtype, N, H, W, C, up, dz, x, mean, rstd, gb, slope, dgb, s);
+  return (int)hipGetLastError();
+}
+
+/* the border-class half of dei2i_spade_bwd_partial alone (class mode): the 24 classes (cy, cx) != (2, 2) of the table's gradient */
 int dei2i_spade_bwd_border(int dtype, int N, int H, int W, int C, int up, const void* dz, const void* x, const float* mean,
-                           const float* rstd, const void* gb, void* dgb_cls, dei2i_stream s) {
+                           const float* rstd, const void* gb, float slope, void* dgb_cls, dei2i_stream s) {
   if (N <= 0 || H < 4 || W < 4 || !cv_ok(dtype, C) || up < 0 || up > 1 || !dz || !x || !mean || !rstd || !gb || !dgb_cls)
     return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(spade_bwd_border_kernel<bf16_t>, dim3(25, N), dim3(256), combine_lds(dtype, 2), st, (const bf16_t*)dz,
-                       (const bf16_t*)x, mean, rstd, (const bf16_t*)gb, (bf16_t*)dgb_cls, H, W, C, up);
-  else
-    hipLaunchKernelGGL(spade_bwd_border_kernel<float>, dim3(25, N), dim3(256), combine_lds(dtype, 2), st, (const float*)dz,
-                       (const float*)x, mean, rstd, (const float*)gb, (float*)dgb_cls, H, W, C, up);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(spade_bwd_border_kernel<T>, dim3(25, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s, (const T*)dz,
+                       (const T*)x, mean, rstd, (const T*)gb, (T*)dgb_cls, H, W, C, up, slope);
+  });
   return (int)hipGetLastError();
 }
 
+/* dgb_cls: the class table's gradient (its interior class is written by the finalize kernel), NULL when there is none */
 int dei2i_spade_bwd_apply(int dtype, int N, int H, int W, int C, int up, const void* dz, const void* x, const float* mean,
-                          const float* rstd, const void* gb, int gb_mode, const float* partial, int chunks, void* dgb_cls,
-                          float* coef, const void* addend, void* dx, dei2i_stream s) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
+                          const float* rstd, const void* gb, int gb_mode, float slope, const float* partial, int chunks,
+                          void* dgb_cls, float* coef, const void* addend, void* dx, dei2i_stream s) {
+  const int vec = vec_of(dtype);
   if (N <= 0 || H <= 0 || W <= 0 || !cv_ok(dtype, C) || up < 0 || up > 1 || !dz || !x || !mean || !rstd || !gb || !partial ||
       !coef || !dx)
     return DEI2I_ERR_BAD_ARG;
@@ -1004,78 +999,11 @@ int dei2i_spade_bwd_apply(int dtype, int N, int H, int W, int C, int up, const v
                      (double)H * (double)W, coef, dgb_cls, dtype);
   const size_t total = (size_t)N * (H >> up) * (W >> up) * (C / vec);
   const unsigned grid = grid_for(total, 256, 256u * 16u);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(spade_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)x, mean,
-                       rstd, (const bf16_t*)gb, gb_mode, (const float*)coef, (const bf16_t*)addend, (bf16_t*)dx, N, H, W, C, up);
-  else
-    hipLaunchKernelGGL(spade_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dz, (const float*)x, mean,
-                       rstd, (const float*)gb, gb_mode, (const float*)coef, (const float*)addend, (float*)dx, N, H, W, C, up);
-  return (int)hipGetLastError();
-}
-
-/* Backward of z = act(IN(x)), IN = InstanceNorm2d(affine=False), act of the ReLU family with negative slope `slope` (0.2:
- * LeakyReLU, 1: no activation) -- the SPADE backward kernels with gamma = beta = 0: `zero_table` is an all-zero (N,5,5,2C) table
- * in the compute dtype.  partial: (N, dei2i_moments_chunks(H*W), 4, C) floats, coef: (N, 2, C) floats (scratch). */
-int dei2i_in_act_bwd(int dtype, int N, int H, int W, int C, const void* dz, const void* x, const float* mean, const float* rstd,
-                     float slope, const void* zero_table, float* partial, float* coef, const void* addend, void* dx, dei2i_stream s) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
-  if (N <= 0 || H < 4 || W < 4 || !cv_ok(dtype, C) || !dz || !x || !mean || !rstd || !zero_table || !partial || !coef || !dx)
-    return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  const int chunks = dei2i_moments_chunks(H * W);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(spade_bwd_partial_kernel<bf16_t>, dim3(chunks, N), dim3(256), combine_lds(dtype, 4), st, (const bf16_t*)dz,
-                       (const bf16_t*)x, mean, rstd, (const bf16_t*)zero_table, 1, (bf16_t*)nullptr, partial, H, W, C, 0, chunks, slope);
-  else
-    hipLaunchKernelGGL(spade_bwd_partial_kernel<float>, dim3(chunks, N), dim3(256), combine_lds(dtype, 4), st, (const float*)dz,
-                       (const float*)x, mean, rstd, (const float*)zero_table, 1, (float*)nullptr, partial, H, W, C, 0, chunks, slope);
-  hipLaunchKernelGGL(spade_bwd_finalize_kernel, dim3(C, N), dim3(combine_threads(chunks)), 0, st, (const float*)partial, N, chunks, C,
-                     (double)H * (double)W, coef, (void*)nullptr, dtype);
-  const size_t total = (size_t)N * H * W * (C / vec);
-  const unsigned grid = grid_for(total, 256, 256u * 16u);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(spade_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)x, mean, rstd,
-                       (const bf16_t*)zero_table, 1, (const float*)coef, (const bf16_t*)addend, (bf16_t*)dx, N, H, W, C, 0, slope);
-  else
-    hipLaunchKernelGGL(spade_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dz, (const float*)x, mean, rstd,
-                       (const float*)zero_table, 1, (const float*)coef, (const float*)addend, (float*)dx, N, H, W, C, 0, slope);
-  return (int)hipGetLastError();
-}
-
-/* Backward of z = act(IN(x) * (1 + gamma) + beta) with per-(n, c) gamma / beta -- AdaIN (stargan-v2/core/model.py:69-80) and
- * InstanceNorm2d(affine=True) (model.py:39-40, 333: gamma = weight - 1, beta = bias for every image) followed by LeakyReLU(0.2)
- * (or any activation of the ReLU family with negative slope `slope`; 1: none): the SPADE backward kernels in class mode on a
- * (N,5,5,2C) table that holds the same (gamma | beta) in all 25 classes, with the activation's slope.  dgb_table: the table's
- * gradient (the caller sums its 25 classes); partial (N, dei2i_moments_chunks(H*W), 4, C) and coef (N, 2, C) floats are scratch. */
-int dei2i_in_affine_act_bwd(int dtype, int N, int H, int W, int C, const void* dz, const void* x, const float* mean,
-                            const float* rstd, float slope, const void* gb_table, void* dgb_table, float* partial, float* coef,
-                            const void* addend, void* dx, dei2i_stream s) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
-  if (N <= 0 || H < 4 || W < 4 || !cv_ok(dtype, C) || !dz || !x || !mean || !rstd || !gb_table || !dgb_table || !partial || !coef || !dx)
-    return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  const int chunks = dei2i_moments_chunks(H * W);
-  const size_t total = (size_t)N * H * W * (C / vec);
-  const unsigned grid = grid_for(total, 256, 256u * 16u);
-  if (dtype == DT_BF16) {
-    hipLaunchKernelGGL(spade_bwd_partial_kernel<bf16_t>, dim3(chunks, N), dim3(256), combine_lds(dtype, 4), st, (const bf16_t*)dz,
-                       (const bf16_t*)x, mean, rstd, (const bf16_t*)gb_table, 1, (bf16_t*)nullptr, partial, H, W, C, 0, chunks, slope);
-    hipLaunchKernelGGL(spade_bwd_border_kernel<bf16_t>, dim3(25, N), dim3(256), combine_lds(dtype, 2), st, (const bf16_t*)dz,
-                       (const bf16_t*)x, mean, rstd, (const bf16_t*)gb_table, (bf16_t*)dgb_table, H, W, C, 0, slope);
-  } else {
-    hipLaunchKernelGGL(spade_bwd_partial_kernel<float>, dim3(chunks, N), dim3(256), combine_lds(dtype, 4), st, (const float*)dz,
-                       (const float*)x, mean, rstd, (const float*)gb_table, 1, (float*)nullptr, partial, H, W, C, 0, chunks, slope);
-    hipLaunchKernelGGL(spade_bwd_border_kernel<float>, dim3(25, N), dim3(256), combine_lds(dtype, 2), st, (const float*)dz,
-                       (const float*)x, mean, rstd, (const float*)gb_table, (float*)dgb_table, H, W, C, 0, slope);
-  }
-  hipLaunchKernelGGL(spade_bwd_finalize_kernel, dim3(C, N), dim3(combine_threads(chunks)), 0, st, (const float*)partial, N, chunks, C,
-                     (double)H * (double)W, coef, dgb_table, dtype);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(spade_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dz, (const bf16_t*)x, mean, rstd,
-                       (const bf16_t*)gb_table, 1, (const float*)coef, (const bf16_t*)addend, (bf16_t*)dx, N, H, W, C, 0, slope);
-  else
-    hipLaunchKernelGGL(spade_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dz, (const float*)x, mean, rstd,
-                       (const float*)gb_table, 1, (const float*)coef, (const float*)addend, (float*)dx, N, H, W, C, 0, slope);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(spade_bwd_apply_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)dz, (const T*)x, mean, rstd, (const T*)gb,
+                       gb_mode, (const float*)coef, (const T*)addend, (T*)dx, N, H, W, C, up, slope);
+  });
   return (int)hipGetLastError();
 }
 
@@ -1121,29 +1049,28 @@ int dei2i_l1_bwd(size_t n, const float* a, const float* b, const float* gout, fl
 
 int dei2i_noise_fwd(int dtype, size_t rows, int C, const void* x, const float* noise, const float* weight, void* out,
                     dei2i_stream s) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
+  const int vec = vec_of(dtype);
   if (rows == 0 || C <= 0 || C % vec || !x || !noise || !weight || !out) return DEI2I_ERR_BAD_ARG;
   const size_t nvec = rows * (size_t)(C / vec);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(noise_fwd_kernel<bf16_t>, dim3(grid_for(nvec, 256, 4096)), dim3(256), 0, (hipStream_t)s,
-                       (const bf16_t*)x, noise, weight, (bf16_t*)out, nvec, C / vec);
-  else
-    hipLaunchKernelGGL(noise_fwd_kernel<float>, dim3(grid_for(nvec, 256, 4096)), dim3(256), 0, (hipStream_t)s,
-                       (const float*)x, noise, weight, (float*)out, nvec, C / vec);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(noise_fwd_kernel<T>, dim3(grid_for(nvec, 256, 4096)), dim3(256), 0, (hipStream_t)s, (const T*)x, noise, weight,
+                       (T*)out, nvec, C / vec);
+  });
   return (int)hipGetLastError();
 }
 
 int dei2i_noise_bwd(int dtype, size_t rows, int C, const void* dy, const float* noise, float* partials, float* dweight,
                     int accumulate, dei2i_stream s) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
+  const int vec = vec_of(dtype);
   if (rows == 0 || C <= 0 || C % vec || !dy || !noise || !partials || !dweight) return DEI2I_ERR_BAD_ARG;
   const size_t nvec = rows * (size_t)(C / vec);
   hipStream_t st = (hipStream_t)s;
   const unsigned nb = grid_for(nvec, 256, 1024);          // `partials`: at least 1024 floats
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(noise_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t*)dy, noise, nvec, C / vec, partials);
-  else
-    hipLaunchKernelGGL(noise_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)dy, noise, nvec, C / vec, partials);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(noise_bwd_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)dy, noise, nvec, C / vec, partials);
+  });
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, (int)nb, 1.f, dweight, accumulate);
   return (int)hipGetLastError();
 }

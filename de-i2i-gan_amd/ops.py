@@ -76,17 +76,22 @@ fuse_pro = False
 fuse_ring = True
 fuse_bwd = True
 
-_fp8_stash = []          # e4m3 copy produced by the last normalisation kernel, handed to its output tensor by the wrapper
+# The side channel from an autograd Function to its output tensor (a Function cannot set attributes on what it returns: autograd
+# wraps it): the forward leaves attribute -> value here, the public wrapper clears the record before .apply and moves whatever
+# is present onto the output afterwards.  _dei2i_fp8: the e4m3 copy a normalisation kernel wrote beside its output;
+# _dei2i_stats: (partial records, records per image) of a producer (see _stats_of); _dei2i_bwd_hint: see _NormBwdHint.
+_handover = {}
+
+
+def _attach(out):
+    for name, value in _handover.items():
+        setattr(out, name, value)
+    _handover.clear()
+    return out
 
 
 def _fp8_copy_wanted(prec, c: int) -> bool:
     return _fp8_forward and prec is BF16 and c % 128 == 0
-
-
-def _attach_fp8(out):
-    if _fp8_stash:
-        out._dei2i_fp8 = _fp8_stash.pop()
-    return out
 
 
 def wants_fp8(name) -> bool:
@@ -476,15 +481,6 @@ class PackedWeights:
         return self.fp8
 
 
-_stats_stash = []        # (partial records, records per image) of the last producer, handed to its output tensor by the wrapper
-
-
-def _attach_stats(out):
-    if _stats_stash:
-        out._dei2i_stats = _stats_stash.pop()
-    return out
-
-
 def _stats_of(t, n, hw, c):
     """The statistics records a producer kernel left for tensor ``t`` ((N, chunks, 2, C) fp32, chunks), or None."""
     st = getattr(t, "_dei2i_stats", None)
@@ -494,6 +490,40 @@ def _stats_of(t, n, hw, c):
     if partial.shape != (n, chunks, 2, c) or partial.device != t.device:
         return None
     return partial, chunks
+
+
+def _moment_records(lib, prec, x, n, hw, c):
+    """-> ((N, chunks, 2, C) fp32 moment records of the NHWC tensor ``x`` with hw pixels per image, chunks): the records its
+    producer left (conv epilogue / affine kernel, see _stats_of) when ``fuse_norm`` is on and they fit, else one statistics pass."""
+    have = _stats_of(x, n, hw, c) if fuse_norm else None
+    if have is not None:
+        return have
+    chunks = lib.dei2i_moments_chunks(hw)
+    partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=x.device)
+    L.check(lib.dei2i_moments_partial(prec.code, n, hw, c, _p(x), _p(partial), _stream()), "moments_partial")
+    return partial, chunks
+
+
+def _in_stats(lib, prec, x, n, hw, c, eps):
+    """-> (mean, rstd), (N, C) fp32: the InstanceNorm statistics of ``x``"""
+    mean = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    partial, chunks = _moment_records(lib, prec, x, n, hw, c)
+    L.check(lib.dei2i_in_finalize(n, hw, c, chunks, _p(partial), eps, _p(mean), _p(rstd), _stream()), "in_finalize")
+    return mean, rstd
+
+
+def _img_affine_act(lib, prec, x, a, b, slope):
+    """-> act(a[n, c] * x + b[n, c]) in one pass over the NHWC tensor ``x``; a, b (N, C) fp32; slope: 0.2 LeakyReLU, 0 ReLU, 1 none"""
+    n, h, w, c = x.shape
+    out = torch.empty_like(x)
+    cv = c // (8 if prec is BF16 else 4)
+    if 256 % cv == 0 or cv % 256 == 0:                # (the per-image kernel keeps one channel vector per thread)
+        L.check(lib.dei2i_affine_act_img_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), slope, _p(out), _stream()), "affine_act_img")
+    else:                                             # odd channel counts: the per-channel kernel, one group per image
+        act = {1.0: L.ACT_NONE, 0.0: L.ACT_RELU, 0.2: L.ACT_LRELU}[slope]
+        L.check(lib.dei2i_affine_act_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), None, act, _p(out), None, 1.0, _stream()), "affine_act")
+    return out
 
 
 class _NormBwdHint:
@@ -531,13 +561,6 @@ class _NormBwdHint:
 
 
 bwd_fused_counts = {"epilogue": 0, "taken": 0}   # dgrad launches that took the reductions / norm backwards that used them (tests)
-_hint_stash = []         # the hint of the last norm forward, handed to its output tensor by the wrapper
-
-
-def _attach_hint(out):
-    if _hint_stash:
-        out._dei2i_bwd_hint = _hint_stash.pop()
-    return out
 
 
 def _conv_dgrad(lib, prec, geom, x_shape, couts, g, weight, cache, sources, per_call, dtype, device, hint=None):
@@ -799,7 +822,7 @@ class _Conv2d(torch.autograd.Function):
             partial = torch.empty((n, chunks, 2, couts), dtype=torch.float32, device=x.device)
             L.check(lib.dei2i_conv2d_fwd_fused(byref(d), _p(x), _p(wf), _p(b32), act, _p(y), None, _p(partial), _stream()),
                     "conv2d_fwd_fused")
-            _stats_stash.append((partial, chunks))
+            _handover["_dei2i_stats"] = (partial, chunks)
         else:
             ws = _workspace(x.device, lib.dei2i_conv2d_workspace_bytes(byref(d)))
             L.check(lib.dei2i_conv2d_fwd(byref(d), _p(x), _p(wf), _p(b32), act, _p(y), _p(ws), ws.numel() * 4, _stream()),
@@ -850,9 +873,8 @@ class _Conv2d(torch.autograd.Function):
 def conv2d(x, weight, bias, cache: PackedWeights, geom: ConvGeom, act="none", sources=None, stats=False):
     """y = act(conv(x) + bias) on an NHWC activation; ``weight`` is the reference's OIHW fp32 parameter.  ``stats``: a
     BatchNorm / InstanceNorm follows -- leave the statistics records of y with it when the kernel can (see _stats_of)."""
-    del _stats_stash[:]
-    return _attach_stats(_Conv2d.apply(x, weight, bias, cache, tuple(sources) if sources is not None else (weight,), geom,
-                                       ACT[act], bool(stats)))
+    _handover.clear()
+    return _attach(_Conv2d.apply(x, weight, bias, cache, tuple(sources) if sources is not None else (weight,), geom, ACT[act], bool(stats)))
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -1060,13 +1082,7 @@ def _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, m
         L.check(lib.dei2i_bn_finalize_eval(c, _p(w32), _p(b32), _p(rm), _p(rv), eps, _p(a), _p(b), st), "bn_finalize_eval")
         return a, b, rm.detach().clone().view(1, c), torch.rsqrt(rv.detach() + eps).view(1, c), nf
     mean, rstd = (torch.empty((groups, c), dtype=torch.float32, device=dev) for _ in range(2))
-    have = _stats_of(y, n, h * w, c) if fuse_norm else None
-    if have is not None:
-        partial, chunks = have
-    else:
-        chunks = lib.dei2i_moments_chunks(h * w)
-        partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
-        L.check(lib.dei2i_moments_partial(prec.code, n, h * w, c, _p(y), _p(partial), st), "moments_partial")
+    partial, chunks = _moment_records(lib, prec, y, n, h * w, c)
     if deferred is not None:                     # this pass's m * batch statistics go to buffers of their own (see bn_running_deferred)
         block = deferred.take_groups(running_mean, running_var, num_batches_tracked, float(momentum), groups)       # (groups, 2, nf)
         rm, rv, num_batches_tracked = block[:, 0], block[:, 1], None
@@ -1149,7 +1165,7 @@ class _BatchNormAct(torch.autograd.Function):
             # the statistics records of the output in the same pass (an InstanceNorm / BatchNorm reads this tensor next)
             chunks = lib.dei2i_moments_chunks(h * w)
             partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
-            _stats_stash.append((partial, chunks))
+            _handover["_dei2i_stats"] = (partial, chunks)
         # every group in one launch (grid.y = group; coefficient rows (groups, c))
         if partial is not None:
             L.check(lib.dei2i_affine_act_stats_fwd(prec.code, groups, n, h * w, c, _p(y), _p(a), _p(b), _p(res), act, _p(out), _p(partial), st),
@@ -1158,14 +1174,14 @@ class _BatchNormAct(torch.autograd.Function):
             L.check(lib.dei2i_affine_act_fwd(prec.code, groups, ng * h * w, c, _p(y), _p(a), _p(b), _p(res), act, _p(out), _p(xq),
                                              FP8_ACT_SCALE, st), "affine_act")
         if xq is not None:
-            _fp8_stash.append(xq)
+            _handover["_dei2i_fp8"] = xq
         ctx.prec, ctx.act, ctx.training, ctx.has_res = prec, act, training, res is not None
         ctx.params, ctx.nf = (weight, bias), nf
         ctx.save_for_backward(y, a, b, mean, rstd)
         ctx.hint = None
         if fuse_bwd and prec is BF16 and ctx.needs_input_grad[0]:
             ctx.hint = _NormBwdHint(2, y, mean, rstd, a=a, b=b, act=act, group_images=ng if groups > 1 else 0)
-            _hint_stash.append(ctx.hint)
+            _handover["_dei2i_bwd_hint"] = ctx.hint
         return out
 
     @staticmethod
@@ -1181,12 +1197,9 @@ def batchnorm_act(y, weight, bias, running_mean, running_var, training, act="non
                   num_batches_tracked=None, stats=False):
     """num_batches_tracked: the module's int64 counter, incremented inside the statistics kernel in training mode.
     ``stats``: a norm layer reads the output next -- leave its statistics records with it (see _stats_of)."""
-    del _fp8_stash[:]
-    del _stats_stash[:]
-    del _hint_stash[:]
-    return _attach_hint(_attach_stats(_attach_fp8(_BatchNormAct.apply(y, weight, bias, res, running_mean, running_var, bool(training),
-                                                                      float(momentum), float(eps), ACT[act], num_batches_tracked,
-                                                                      bool(stats)))))
+    _handover.clear()
+    return _attach(_BatchNormAct.apply(y, weight, bias, res, running_mean, running_var, bool(training), float(momentum), float(eps),
+                                       ACT[act], num_batches_tracked, bool(stats)))
 
 
 class _BnActConv(torch.autograd.Function):
@@ -1214,7 +1227,7 @@ class _BnActConv(torch.autograd.Function):
         if want_stats:
             chunks = lib.dei2i_conv2d_stats_chunks(byref(d))
             partial = torch.empty((n, chunks, 2, couts), dtype=torch.float32, device=y1.device)
-            _stats_stash.append((partial, chunks))
+            _handover["_dei2i_stats"] = (partial, chunks)
         L.check(lib.dei2i_conv2d_fwd_fused(byref(d), _p(y1), _p(wf), None, L.ACT_NONE, _p(y), byref(pro), _p(partial), _stream()),
                 "conv2d_fwd_fused(bn)")
         ctx.prec, ctx.act, ctx.training, ctx.nf, ctx.geom = prec, act, training, nf, geom
@@ -1260,18 +1273,18 @@ def bn_act_conv_supported(y1, bn_weight, weight, geom: ConvGeom, need_grad: bool
 def bn_act_conv(y1, bn_weight, bn_bias, running_mean, running_var, training, act, weight, cache, geom, momentum=0.1, eps=1e-5,
                 num_batches_tracked=None, sources=None, stats=False):
     """conv(act(BatchNorm2d(y1))), the norm + activation fused into the conv (ask bn_act_conv_supported first)."""
-    del _stats_stash[:]
-    return _attach_stats(_BnActConv.apply(y1, bn_weight, bn_bias, weight, running_mean, running_var, bool(training), float(momentum),
-                                          float(eps), ACT[act], num_batches_tracked, cache,
-                                          tuple(sources) if sources is not None else (weight,), geom, bool(stats)))
+    _handover.clear()
+    return _attach(_BnActConv.apply(y1, bn_weight, bn_bias, weight, running_mean, running_var, bool(training), float(momentum),
+                                    float(eps), ACT[act], num_batches_tracked, cache,
+                                    tuple(sources) if sources is not None else (weight,), geom, bool(stats)))
 
 
 def add(x, res, stats=False):
     """x + res on NHWC activations (NormResBlock identity branch, architecture.py:350).  ``stats``: a norm layer reads the
     sum next -- leave its statistics records with it."""
     c = x.shape[-1]
-    del _stats_stash[:]
-    return _attach_stats(_AffineAdd.apply(x, res, _const_vec(x.device, c, 1.0), _const_vec(x.device, c, 0.0), bool(stats)))
+    _handover.clear()
+    return _attach(_AffineAdd.apply(x, res, _const_vec(x.device, c, 1.0), _const_vec(x.device, c, 0.0), bool(stats)))
 
 
 class _AffineAdd(torch.autograd.Function):
@@ -1289,7 +1302,7 @@ class _AffineAdd(torch.autograd.Function):
             partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=x.device)
             L.check(lib.dei2i_affine_act_stats_fwd(prec.code, 1, n, hw, c, _p(x), _p(ones), _p(zeros), _p(res), L.ACT_NONE, _p(out),
                                                    _p(partial), _stream()), "add_stats")
-            _stats_stash.append((partial, chunks))
+            _handover["_dei2i_stats"] = (partial, chunks)
         else:
             L.check(lib.dei2i_affine_act_fwd(prec.code, 1, x.numel() // c, c, _p(x), _p(ones), _p(zeros), _p(res),
                                              L.ACT_NONE, _p(out), None, 1.0, _stream()), "add")
@@ -1303,29 +1316,31 @@ class _AffineAdd(torch.autograd.Function):
 # --------------------------------------------------------------------------------------------------------------
 # SPADE (InstanceNorm * (1+gamma) + beta) + ReLU, optional fused nearest x2 upsample of x
 # --------------------------------------------------------------------------------------------------------------
-def _spade_backward(lib, prec, dout, dskip, x, gb, mean, rstd, up, gb_mode, out_shape, hint=None):
-    """-> (dx, dgb) of z = relu(IN(x)*(1+gamma)+beta) given dL/dz at the (upsampled) output resolution; dskip (optional) is
-    added to dx inside the apply kernel (the res block's identity branch).  ``hint``: the dgrad of the conv behind the layer may
-    have left the reduction records already (_NormBwdHint); the 24 border classes of the table's gradient are then all that is
-    left of the first pass."""
+def _spade_backward(lib, prec, dout, dskip, x, gb, mean, rstd, up, gb_mode, out_shape, hint=None, slope=0.0, want_dgb=True):
+    """-> (dx, dgb) of z = act(IN(x)*(1+gamma)+beta) given dL/dz at the (upsampled) output resolution -- the one backward of SPADE
+    + ReLU (``slope`` 0), InstanceNorm + act and AdaIN / affine InstanceNorm + act (class mode on an all-zero / a replicated
+    table; slope 0.2 LeakyReLU, 1 none).  dskip (optional) is added to dx inside the apply kernel (the res block's identity
+    branch).  ``want_dgb`` False (class mode): no table gradient, dgb is None.  ``hint`` (SPADE only): the dgrad of the conv
+    behind the layer may have left the reduction records already (_NormBwdHint); the 24 border classes of the table's gradient
+    are then all that is left of the first pass."""
     st = _stream()
     dev = x.device
     have = hint.take(dout) if (hint is not None and gb_mode == 1) else None
     dout = dout.contiguous()
     n, h, w, c = out_shape
-    dgb = torch.empty_like(gb)         # dense (N,H,W,2C), or the (N,5,5,2C) class table -- both written in full
+    dgb = torch.empty_like(gb) if want_dgb else None   # dense (N,H,W,2C), or the (N,5,5,2C) class table -- both written in full
     if have is not None:
         partial, chunks = have
-        L.check(lib.dei2i_spade_bwd_border(prec.code, n, h, w, c, 1 if up else 0, _p(dout), _p(x), _p(mean), _p(rstd), _p(gb),
+        L.check(lib.dei2i_spade_bwd_border(prec.code, n, h, w, c, 1 if up else 0, _p(dout), _p(x), _p(mean), _p(rstd), _p(gb), slope,
                                            _p(dgb), st), "spade_bwd_border")
     else:
         chunks = lib.dei2i_moments_chunks(h * w)
         partial = torch.empty((n, chunks, 4, c), dtype=torch.float32, device=dev)
         L.check(lib.dei2i_spade_bwd_partial(prec.code, n, h, w, c, 1 if up else 0, _p(dout), _p(x), _p(mean), _p(rstd),
-                                            _p(gb), gb_mode, _p(dgb), _p(partial), st), "spade_bwd_partial")
+                                            _p(gb), gb_mode, slope, _p(dgb), _p(partial), st), "spade_bwd_partial")
     coef = torch.empty((n, 2, c), dtype=torch.float32, device=dev)
     dx = torch.empty_like(x)
-    L.check(lib.dei2i_spade_bwd_apply(prec.code, n, h, w, c, 1 if up else 0, _p(dout), _p(x), _p(mean), _p(rstd), _p(gb), gb_mode,
+    L.check(lib.dei2i_spade_bwd_apply(prec.code, n, h, w, c, 1 if up else 0, _p(dout), _p(x), _p(mean), _p(rstd), _p(gb), gb_mode, slope,
                                       _p(partial), chunks, _p(dgb) if gb_mode == 1 else None, _p(coef), _p(dskip), _p(dx), st),
             "spade_bwd_apply")
     return dx, dgb
@@ -1347,31 +1362,21 @@ class _SpadeRelu(torch.autograd.Function):
         lib = _lib_for(x)
         st = _stream()
         dev = x.device
-        mean = torch.empty((n, c), dtype=torch.float32, device=dev)
-        rstd = torch.empty((n, c), dtype=torch.float32, device=dev)
-        # statistics of the upsampled tensor == statistics of the source tensor (every pixel replicated 4x); the records its
-        # producer left (conv epilogue / affine kernel) when there are any
-        have = _stats_of(x, n, hs * ws, c) if fuse_norm else None
-        if have is not None:
-            partial, chunks = have
-        else:
-            chunks = lib.dei2i_moments_chunks(hs * ws)
-            partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
-            L.check(lib.dei2i_moments_partial(prec.code, n, hs * ws, c, _p(x), _p(partial), st), "moments_partial")
-        L.check(lib.dei2i_in_finalize(n, hs * ws, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
+        # statistics of the upsampled tensor == statistics of the source tensor (every pixel replicated 4x)
+        mean, rstd = _in_stats(lib, prec, x, n, hs * ws, c, eps)
         out = torch.empty((n, h, w, c), dtype=prec.dtype, device=dev)
         xq = torch.empty(out.numel(), dtype=torch.uint8, device=dev) if _fp8_copy_wanted(prec, c) else None
         L.check(lib.dei2i_spade_act_fwd(prec.code, n, h, w, c, 1 if up else 0, _p(x), _p(mean), _p(rstd), _p(gb), gb_mode,
                                         _p(out), _p(xq), FP8_ACT_SCALE, st), "spade_act_fwd")
         if xq is not None:
-            _fp8_stash.append(xq)
+            _handover["_dei2i_fp8"] = xq
         ctx.prec, ctx.up, ctx.gb_mode = prec, up, gb_mode
         ctx.out_shape = (n, h, w, c)
         ctx.save_for_backward(x, gb, mean, rstd)        # backward recomputes the ReLU mask; the output is not kept
         ctx.hint = None
         if fuse_bwd and gb_mode == 1 and prec is BF16 and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             ctx.hint = _NormBwdHint(1, x, mean, rstd, gb=gb, up=up)
-            _hint_stash.append(ctx.hint)
+            _handover["_dei2i_bwd_hint"] = ctx.hint
         return (out, x_in) if skip else out
 
     @staticmethod
@@ -1390,12 +1395,11 @@ class _SpadeRelu(torch.autograd.Function):
 
 def spade_relu(x, gb, up: bool, gb_mode: int, eps: float = 1e-5, skip: bool = False):
     """relu(IN(x) * (1 + gamma) + beta); with ``skip`` -> (that, x): x handed through for the res block's identity add."""
-    del _fp8_stash[:]
-    del _hint_stash[:]
+    _handover.clear()
     if skip:
         out, xs = _SpadeRelu.apply(x, gb, bool(up), int(gb_mode), float(eps), True)
-        return _attach_hint(_attach_fp8(out)), xs
-    return _attach_hint(_attach_fp8(_SpadeRelu.apply(x, gb, bool(up), int(gb_mode), float(eps))))
+        return _attach(out), xs
+    return _attach(_SpadeRelu.apply(x, gb, bool(up), int(gb_mode), float(eps)))
 
 
 class _SpadeConv(torch.autograd.Function):
@@ -1421,13 +1425,7 @@ class _SpadeConv(torch.autograd.Function):
         lib = _lib_for(x)
         st = _stream()
         dev = x.device
-        have = _stats_of(x, n, hs * ws, c)
-        if have is not None:
-            partial, chunks = have
-        else:
-            chunks = lib.dei2i_moments_chunks(hs * ws)
-            partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
-            L.check(lib.dei2i_moments_partial(prec.code, n, hs * ws, c, _p(x), _p(partial), st), "moments_partial")
+        partial, chunks = _moment_records(lib, prec, x, n, hs * ws, c)
         coefs = torch.empty((4, n, c), dtype=torch.float32, device=dev)          # mean | rstd | A | B
         ring = torch.empty((n, lib.dei2i_ring_pixels(h, w), c), dtype=prec.dtype, device=dev)
         L.check(lib.dei2i_spade_prep(prec.code, n, hs, ws, c, 1 if up else 0, _p(x), _p(partial), chunks, eps, _p(gb),
@@ -1443,7 +1441,7 @@ class _SpadeConv(torch.autograd.Function):
         if want_stats:
             ochunks = lib.dei2i_conv2d_stats_chunks(byref(d))
             out_partial = torch.empty((n, ochunks, 2, couts), dtype=torch.float32, device=dev)
-            _stats_stash.append((out_partial, ochunks))
+            _handover["_dei2i_stats"] = (out_partial, ochunks)
         z_src = None
         if ring_mode:
             z_src = torch.empty_like(x)
@@ -1513,13 +1511,13 @@ def spade_conv_supported(x, weight, geom: ConvGeom, need_grad: bool):
 def spade_conv(x, gb, weight, cache, geom: ConvGeom, eps: float = 1e-5, skip: bool = False, sources=None, stats=False, mode="pro"):
     """conv(relu(IN(up(x)) * (1 + gamma) + beta)) with the class table ``gb`` (N,5,5,2C); ``geom.up`` = nearest x2 upsample in
     front of the norm.  With ``skip`` -> (y, x).  ``mode``: what spade_conv_supported answered."""
-    del _stats_stash[:]
+    _handover.clear()
     src = tuple(sources) if sources is not None else (weight,)
     ring_mode = mode == "ring"
     if skip:
         y, xs = _SpadeConv.apply(x, gb, weight, bool(geom.up), float(eps), True, cache, src, geom, bool(stats), ring_mode)
-        return _attach_stats(y), xs
-    return _attach_stats(_SpadeConv.apply(x, gb, weight, bool(geom.up), float(eps), False, cache, src, geom, bool(stats), ring_mode))
+        return _attach(y), xs
+    return _attach(_SpadeConv.apply(x, gb, weight, bool(geom.up), float(eps), False, cache, src, geom, bool(stats), ring_mode))
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -1541,8 +1539,8 @@ def _zero_table(device, dtype, n, c):
 class _InstanceNormAct(torch.autograd.Function):
     """z = act(InstanceNorm2d(x)), affine=False, eps 1e-5 (architecture.py:79-118 with norm_layer=nn.InstanceNorm2d): per-(n, c)
     statistics (the producer's records when it left any), then one affine + activation pass with per-image coefficients
-    A = rstd, B = -mean * rstd.  ``slope``: 0.2 LeakyReLU, 0 ReLU, 1 none.  Backward: the SPADE backward kernels with
-    gamma = beta = 0 (dei2i_in_act_bwd); ``res`` (optional) is added to the output and its gradient passed through."""
+    A = rstd, B = -mean * rstd.  ``slope``: 0.2 LeakyReLU, 0 ReLU, 1 none.  Backward: the SPADE backward (_spade_backward) in class
+    mode on an all-zero table, no table gradient; ``res`` (optional) is added to the output and its gradient passed through."""
 
     @staticmethod
     def forward(ctx, x, slope: float, res, eps: float):
@@ -1551,26 +1549,8 @@ class _InstanceNormAct(torch.autograd.Function):
         x = x.contiguous()
         n, h, w, c = x.shape
         lib = _lib_for(x)
-        st = _stream()
-        dev = x.device
-        mean = torch.empty((n, c), dtype=torch.float32, device=dev)
-        rstd = torch.empty((n, c), dtype=torch.float32, device=dev)
-        have = _stats_of(x, n, h * w, c) if fuse_norm else None
-        if have is not None:
-            partial, chunks = have
-        else:
-            chunks = lib.dei2i_moments_chunks(h * w)
-            partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
-            L.check(lib.dei2i_moments_partial(prec.code, n, h * w, c, _p(x), _p(partial), st), "moments_partial")
-        L.check(lib.dei2i_in_finalize(n, h * w, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
-        a, b = rstd, -mean * rstd
-        out = torch.empty_like(x)
-        cv = c // (8 if prec is BF16 else 4)
-        if 256 % cv == 0 or cv % 256 == 0:                # (the per-image kernel keeps one channel vector per thread)
-            L.check(lib.dei2i_affine_act_img_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), slope, _p(out), st), "affine_act_img")
-        else:                                             # odd channel counts: the per-channel kernel, one group per image
-            act = {1.0: L.ACT_NONE, 0.0: L.ACT_RELU, 0.2: L.ACT_LRELU}[slope]
-            L.check(lib.dei2i_affine_act_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), None, act, _p(out), None, 1.0, st), "affine_act")
+        mean, rstd = _in_stats(lib, prec, x, n, h * w, c, eps)
+        out = _img_affine_act(lib, prec, x, rstd, -mean * rstd, slope)
         if res is not None:
             out = out + res
         ctx.prec, ctx.slope, ctx.has_res = prec, slope, res is not None
@@ -1580,16 +1560,9 @@ class _InstanceNormAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, mean, rstd = ctx.saved_tensors
-        prec = ctx.prec
-        n, h, w, c = x.shape
-        lib = _lib_for(x)
-        dout = dout.contiguous()
-        chunks = lib.dei2i_moments_chunks(h * w)
-        partial = torch.empty((n, chunks, 4, c), dtype=torch.float32, device=x.device)
-        coef = torch.empty((n, 2, c), dtype=torch.float32, device=x.device)
-        dx = torch.empty_like(x)
-        L.check(lib.dei2i_in_act_bwd(prec.code, n, h, w, c, _p(dout), _p(x), _p(mean), _p(rstd), ctx.slope,
-                                     _p(_zero_table(x.device, x.dtype, n, c)), _p(partial), _p(coef), None, _p(dx), _stream()), "in_act_bwd")
+        n, c = x.shape[0], x.shape[3]
+        dx, _ = _spade_backward(_lib_for(x), ctx.prec, dout, None, x, _zero_table(x.device, x.dtype, n, c), mean, rstd, False, 1,
+                                tuple(x.shape), slope=ctx.slope, want_dgb=False)
         return dx, None, (dout if ctx.has_res else None), None
 
 
@@ -1779,8 +1752,8 @@ class _InAffineAct(torch.autograd.Function):
     """z = act(InstanceNorm2d(x) * (1 + gamma) + beta), gamma / beta (N, C) fp32 -- stargan-v2's AdaIN (core/model.py:69-80) and its
     InstanceNorm2d(affine=True) (gamma = weight - 1, beta = bias for every image) with the LeakyReLU(0.2) that follows both at every
     call site (model.py:53-61,104-112,333-334).  Forward: statistics -> per-image coefficients A = rstd (1 + gamma), B = beta - mean A
-    -> one affine + activation pass.  Backward: dei2i_in_affine_act_bwd (the SPADE backward kernels in class mode with the
-    activation's slope); the table's 25 classes are summed back to (N, C).  gamma / beta are rounded to the compute dtype first, so
+    -> one affine + activation pass.  Backward: the SPADE backward (_spade_backward) in class mode on the replicated table with the
+    activation's slope; the table's 25 classes are summed back to (N, C).  gamma / beta are rounded to the compute dtype first, so
     that forward and backward see the same values."""
 
     @staticmethod
@@ -1790,30 +1763,15 @@ class _InAffineAct(torch.autograd.Function):
         x = x.contiguous()
         n, h, w, c = x.shape
         lib = _lib_for(x)
-        st, dev = _stream(), x.device
+        dev = x.device
         cl = gamma.shape[1]
         gb = torch.zeros((n, 2 * c), dtype=prec.dtype, device=dev)
         gb[:, :cl] = gamma.detach().to(prec.dtype)
         gb[:, c:c + cl] = beta.detach().to(prec.dtype)
-        mean = torch.empty((n, c), dtype=torch.float32, device=dev)
-        rstd = torch.empty((n, c), dtype=torch.float32, device=dev)
-        have = _stats_of(x, n, h * w, c) if fuse_norm else None
-        if have is not None:
-            partial, chunks = have
-        else:
-            chunks = lib.dei2i_moments_chunks(h * w)
-            partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
-            L.check(lib.dei2i_moments_partial(prec.code, n, h * w, c, _p(x), _p(partial), st), "moments_partial")
-        L.check(lib.dei2i_in_finalize(n, h * w, c, chunks, _p(partial), eps, _p(mean), _p(rstd), st), "in_finalize")
+        mean, rstd = _in_stats(lib, prec, x, n, h * w, c, eps)
         a = rstd * (1.0 + gb[:, :c].float())
         b = gb[:, c:].float() - mean * a
-        out = torch.empty_like(x)
-        cv = c // (8 if prec is BF16 else 4)
-        if 256 % cv == 0 or cv % 256 == 0:
-            L.check(lib.dei2i_affine_act_img_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), slope, _p(out), st), "affine_act_img")
-        else:                                             # odd channel counts: the per-channel kernel, one group per image
-            act = {1.0: L.ACT_NONE, 0.0: L.ACT_RELU, 0.2: L.ACT_LRELU}[slope]
-            L.check(lib.dei2i_affine_act_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), None, act, _p(out), None, 1.0, st), "affine_act")
+        out = _img_affine_act(lib, prec, x, a, b, slope)
         ctx.prec, ctx.slope, ctx.cl = prec, slope, cl
         ctx.save_for_backward(x, mean, rstd, gb)
         return out
@@ -1821,20 +1779,11 @@ class _InAffineAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, mean, rstd, gb = ctx.saved_tensors
-        prec = ctx.prec
         n, h, w, c = x.shape
         if h < 4 or w < 4:
             raise NotImplementedError("in_affine_act backward needs H, W >= 4 (class-mode SPADE kernels)")
-        lib = _lib_for(x)
-        dout = dout.contiguous()
         table = gb.view(n, 1, 1, 2 * c).expand(n, 5, 5, 2 * c).contiguous()
-        dtable = torch.empty_like(table)
-        chunks = lib.dei2i_moments_chunks(h * w)
-        partial = torch.empty((n, chunks, 4, c), dtype=torch.float32, device=x.device)
-        coef = torch.empty((n, 2, c), dtype=torch.float32, device=x.device)
-        dx = torch.empty_like(x)
-        L.check(lib.dei2i_in_affine_act_bwd(prec.code, n, h, w, c, _p(dout), _p(x), _p(mean), _p(rstd), ctx.slope, _p(table), _p(dtable),
-                                            _p(partial), _p(coef), None, _p(dx), _stream()), "in_affine_act_bwd")
+        dx, dtable = _spade_backward(_lib_for(x), ctx.prec, dout, None, x, table, mean, rstd, False, 1, tuple(x.shape), slope=ctx.slope)
         dgb = dtable.float().sum(dim=(1, 2))              # (N, 2C): the 25 classes hold the same (gamma | beta)
         return dx, dgb[:, :ctx.cl], dgb[:, c:c + ctx.cl], None, None
 

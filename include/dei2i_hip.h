@@ -165,17 +165,26 @@ int dei2i_bn_bwd_partial(int dtype, int groups, size_t pixels, int C, const void
 int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
                        const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
                        float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s);
-/* SPADE backward.  z = relu(v), v = xhat*(1+gamma)+beta is RECOMPUTED from x and the gamma/beta table in both passes (the
- * op keeps neither its output nor a dxhat tensor): g = dz*[v>0]; dgamma = g*xhat, dbeta = g -> dgb (T: dense tensor, or
- * the (N,5,5,2C) border-class table -- its 24 border classes are written by pass 1, the interior class by pass 2); partial (N, chunks, 4, C) fp32 sums of dxhat = g*(1+gamma), dxhat*xhat and the
- * interior-class dgamma / dbeta.  chunks = dei2i_moments_chunks(H*W of the OUTPUT). */
+/* SPADE-family backward.  z = act(v), v = xhat*(1+gamma)+beta, act of the ReLU family with negative slope `slope` (0: SPADE's
+ * ReLU, 0.2: LeakyReLU, 1: none), is RECOMPUTED from x and the gamma/beta table in both passes (the op keeps neither its output
+ * nor a dxhat tensor): g = dz*(v>0 ? 1 : slope); dgamma = g*xhat, dbeta = g -> dgb (T: dense tensor, or the (N,5,5,2C)
+ * border-class table -- its 24 border classes are written by pass 1, the interior class by pass 2); partial (N, chunks, 4, C)
+ * fp32 sums of dxhat = g*(1+gamma), dxhat*xhat and the interior-class dgamma / dbeta.  chunks = dei2i_moments_chunks(H*W of the
+ * OUTPUT).  In class mode dgb may be NULL: no table gradient is wanted, its border classes are not reduced (pass 2 is then
+ * given dgb_cls = NULL).  The same two passes are the backward of
+ *   z = act(InstanceNorm2d(x)), affine=False (extractor.py:50-80 with architecture.py:79-176): class mode on an all-zero
+ *     (N,5,5,2C) table, dgb = NULL, up = 0;
+ *   z = act(IN(x) * (1 + gamma) + beta) with per-(n, c) gamma / beta -- AdaIN (stargan-v2/core/model.py:69-80) and
+ *     InstanceNorm2d(affine=True) (model.py:39-40,56-61,333-334: gamma = weight - 1, beta = bias): class mode on a table that holds
+ *     the same (gamma | beta) in all 25 classes; the caller sums the 25 classes of dgb.  Forward of both: dei2i_in_finalize +
+ *     dei2i_affine_act_img_fwd with A = rstd (1 + gamma), B = beta - mean A. */
 int dei2i_spade_bwd_partial(int dtype, int N, int H, int W, int C, int up, const void* dz, const void* x, const float* mean,
-                            const float* rstd, const void* gb, int gb_mode, void* dgb, float* partial, dei2i_stream s);
+                            const float* rstd, const void* gb, int gb_mode, float slope, void* dgb, float* partial, dei2i_stream s);
 /* pass 2 (finalize + apply): dx = rstd*(sum_cell dxhat - cnt*mean(dxhat) - cnt*xhat*mean(dxhat*xhat)) (+ addend).
  * coef: fp32 scratch (N,2,C).  dgb_cls: the class-mode (N,5,5,2C) table of pass 1 (its interior class is written here), or NULL. */
 int dei2i_spade_bwd_apply(int dtype, int N, int H, int W, int C, int up, const void* dz, const void* x, const float* mean,
-                          const float* rstd, const void* gb, int gb_mode, const float* partial, int chunks, void* dgb_cls,
-                          float* coef, const void* addend, void* dx, dei2i_stream s);
+                          const float* rstd, const void* gb, int gb_mode, float slope, const float* partial, int chunks,
+                          void* dgb_cls, float* coef, const void* addend, void* dx, dei2i_stream s);
 
 /* ---- generator heads + compose (generator.py:266-275) ----
  * raw: (N,H,W,Cs>=4) = [fg_pre(3), prob_pre(1)]; x_in, out: NCHW fp32 (N,3,H,W); prob: NCHW fp32 (N,1,H,W)
@@ -385,26 +394,12 @@ int dei2i_conv2d_dgrad_norm_supported(const dei2i_conv* c);                   /*
 int dei2i_conv2d_dgrad_norm_chunks(const dei2i_conv* c);
 int dei2i_conv2d_dgrad_input_norm(const dei2i_conv* c, const void* dy, const void* wd_packed, void* dx, const dei2i_epi_norm* en,
                                   dei2i_stream s);
-/* Backward of z = act(InstanceNorm2d(x)) (affine=False) with an activation of the ReLU family of negative slope `slope` (0.2:
- * LeakyReLU, 1: none) -- the norm of the conv StyleExtractor's blocks (models/networks/extractor.py:50-80 with
- * architecture.py:79-176): the SPADE backward kernels with gamma = beta = 0.  zero_table: an all-zero (N,5,5,2C) table in the
- * compute dtype; partial (N, dei2i_moments_chunks(H*W), 4, C) and coef (N, 2, C) floats are scratch; addend (optional) is added to dx. */
-int dei2i_in_act_bwd(int dtype, int N, int H, int W, int C, const void* dz, const void* x, const float* mean, const float* rstd,
-                     float slope, const void* zero_table, float* partial, float* coef, const void* addend, void* dx, dei2i_stream s);
-/* The same with a real (gamma | beta): z = act(IN(x) * (1 + gamma) + beta), gamma / beta per (n, c) -- AdaIN (stargan-v2/core/model.py:
- * 69-80) and InstanceNorm2d(affine=True) + LeakyReLU (model.py:39-40,56-61,333-334: gamma = weight - 1, beta = bias).  gb_table: the
- * (N,5,5,2C) class table holding the same (gamma | beta) in all 25 classes (compute dtype); dgb_table: its gradient, same shape (the
- * caller sums the 25 classes).  Forward of the op: dei2i_in_finalize + dei2i_affine_act_img_fwd with A = rstd (1 + gamma),
- * B = beta - mean A. */
-int dei2i_in_affine_act_bwd(int dtype, int N, int H, int W, int C, const void* dz, const void* x, const float* mean,
-                            const float* rstd, float slope, const void* gb_table, void* dgb_table, float* partial, float* coef,
-                            const void* addend, void* dx, dei2i_stream s);
 /* nn.AvgPool2d(2, 2) on NHWC (N, H, W, C), H and W even (architecture.py:157-168); out / dout: (N, H/2, W/2, C) */
 int dei2i_avgpool2_fwd(int dtype, int N, int H, int W, int C, const void* x, void* out, dei2i_stream s);
 int dei2i_avgpool2_bwd(int dtype, int N, int H, int W, int C, const void* dout, void* dx, dei2i_stream s);
 /* the border-class half of dei2i_spade_bwd_partial alone (class mode): dgb_cls[n, cy, cx, :] for the 24 classes (cy, cx) != (2, 2) */
 int dei2i_spade_bwd_border(int dtype, int N, int H, int W, int C, int up, const void* dz, const void* x, const float* mean,
-                           const float* rstd, const void* gb, void* dgb_cls, dei2i_stream s);
+                           const float* rstd, const void* gb, float slope, void* dgb_cls, dei2i_stream s);
 /* out[n, p, c] = max(A[n, c] * x[n, p, c] + B[n, c], 0) + slope * min(..., 0): an affine + activation with per-IMAGE
  * coefficients (SPADE's interior class at the source resolution; HW pixels per image) */
 int dei2i_affine_act_img_fwd(int dtype, int N, int HW, int C, const void* x, const float* A, const float* B, float slope, void* out,

@@ -538,6 +538,62 @@ def test_in_affine_act_small_images_forward_only(ops, pname, shape):
         out.backward(to_dev(P["g"], pname))
 
 
+@functools.lru_cache(maxsize=None)
+def _in_zero_table_problem(pname, shape, seed=61):
+    """x, upstream gradient and, per activation, the float64 dgamma / dbeta of act(IN(x) * (1 + gamma) + beta) at gamma = beta = 0"""
+    def make(s):
+        x, g = data(shape, s), data(shape, s + 1, 1.0, 0.0)
+        xr = rounded(x, pname).double()
+        n, c = shape[0], shape[3]
+        gm, bt = (torch.zeros(n, c, dtype=torch.float64, requires_grad=True) for _ in range(2))
+        pre = F.instance_norm(xr, eps=1e-5) * (1 + gm[:, :, None, None]) + bt[:, :, None, None]
+        dgb = {act: torch.autograd.grad(act64(pre, act), [gm, bt], rounded(g, pname).double(), retain_graph=True)
+               for act in ("relu", "leaky_relu", "none")}
+        return dict(x=x, g=g, pre=pre.detach(), dgb=dgb)
+    return clear_of_kinks(make, "relu", seed)
+
+
+@pytest.mark.parametrize("shape", [(2, 4, 4, 16),       # the class-mode minimum: border classes only, no interior
+                                   (2, 5, 12, 16),      # one interior row
+                                   (1, 9, 15, 16)],     # HW = 135: two ragged chunks
+                         ids=_id)
+@pytest.mark.parametrize("pname", PNAMES)
+def test_instance_norm_family_is_one_path(ops, pname, shape):
+    """instance_norm_act, in_affine_act with gamma = beta = 0 and (ReLU) spade_relu with an all-zero class table are the same
+    statistics, the same coefficients (A = rstd (1 + 0) = rstd, B = 0 - mean A = -(mean rstd)) and the same backward kernels: out and
+    dx are BIT-equal between the first two for every activation, dx of the third is bit-equal for ReLU (its forward is another
+    kernel and is not compared).  in_affine_act's dgamma / dbeta at the zero table against float64, at that op's tolerances; the
+    module's shared zero table is still all zeros after instance_norm_act's backward."""
+    n, h, w, c = shape
+    P = _in_zero_table_problem(pname, shape)
+    gg = to_dev(P["g"], pname)
+    for act in ("relu", "leaky_relu", "none"):
+        tag = f"one-path {pname} {shape} {act}"
+        xa, xb = (to_dev(P["x"], pname).requires_grad_(True) for _ in range(2))
+        gmg, btg = (torch.zeros(n, c, device=dev(), requires_grad=True) for _ in range(2))
+        out_a = ops.in_affine_act(xa, gmg, btg, act)
+        out_a.backward(gg)
+        out_b = ops.instance_norm_act(xb, act)
+        out_b.backward(gg)
+        table = ops._zero_tables[(dev(), _dtype(pname), n, c)]
+        assert table.shape == (n, 5, 5, 2 * c) and int(torch.count_nonzero(table)) == 0, tag + ": the shared zero table was written"
+        d_out, d_dx = (out_a.detach().float() - out_b.detach().float()).abs().max().item(), (xa.grad.float() - xb.grad.float()).abs().max().item()
+        note(f"{tag}: in_affine_act vs instance_norm_act max |d out| {d_out:.3e} max |d dx| {d_dx:.3e}")
+        assert torch.equal(out_a.detach(), out_b.detach()), (tag, "out", d_out)
+        assert torch.equal(xa.grad, xb.grad), (tag, "dx", d_dx)
+        if act == "relu":
+            xc = to_dev(P["x"], pname).requires_grad_(True)
+            zeros = torch.zeros(n, 5, 5, 2 * c, dtype=_dtype(pname), device=dev())
+            ops.spade_relu(xc, zeros, False, 1).backward(gg)
+            d_sp = (xc.grad.float() - xb.grad.float()).abs().max().item()
+            note(f"{tag}: spade_relu vs instance_norm_act max |d dx| {d_sp:.3e}")
+            assert torch.equal(xc.grad, xb.grad), (tag, "spade dx", d_sp)
+        dgm, dbt = P["dgb"][act]
+        eg, eb = relmax(gmg.grad, dgm), relmax(btg.grad, dbt)
+        note(f"{tag}: dgamma {eg:.3e} dbeta {eb:.3e} (tol {2 * TOL[pname]:.1e})")
+        assert eg < 2 * TOL[pname] and eb < 2 * TOL[pname]
+
+
 def test_instance_norm_variance_cancellation_f32(ops):
     """The InstanceNorm counterpart of test_batchnorm_variance_cancellation_f32 (mean = 8 std per channel, (2, 64, 65, 8), f32)."""
     shape = (2, 64, 65, 8)
