@@ -88,6 +88,10 @@ SIGNATURES = {
     "dei2i_bn_bwd_chunks": (c_int, [c_size_t]),
     "dei2i_bn_bwd_partial": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P]),
     "dei2i_bn_bwd_apply": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P]),
+    "dei2i_bn_sync_fwd_sums": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "dei2i_bn_sync_fwd_finalize": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P]),
+    "dei2i_bn_sync_bwd_sums": (c_int, [c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P]),
+    "dei2i_bn_sync_bwd_apply": (c_int, [c_int, c_int, c_size_t, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
     "dei2i_spade_bwd_partial": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, _P, _P, _P]),
     "dei2i_spade_bwd_apply": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, _P, c_int, _P, _P, _P, _P, _P]),
     "dei2i_compose_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),

@@ -112,6 +112,27 @@ DEI2I_D void combine_records(const float* __restrict__ partial, size_t rec0, int
 }
 static inline int combine_threads(int nrec) { return nrec > 256 ? 256 : 64; }
 
+// One channel of a group from its sums over `count` elements: mean / rstd, the affine coefficients and the running update.
+DEI2I_D void bn_train_channel(double sum, double sumsq, double count, int c, const float* __restrict__ weight,
+                              const float* __restrict__ bias, float* __restrict__ rmean, float* __restrict__ rvar, float momentum,
+                              float eps, float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ a,
+                              float* __restrict__ b) {
+  const double mu = sum / count;
+  double var = sumsq / count - mu * mu;
+  if (var < 0.0) var = 0.0;
+  const float rs = (float)(1.0 / sqrt(var + (double)eps));
+  mean[c] = (float)mu;
+  rstd[c] = rs;
+  const float av = weight[c] * rs;
+  a[c] = av;
+  b[c] = bias[c] - (float)mu * av;
+  if (rmean != nullptr) {
+    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+    rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mu;
+    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
+  }
+}
+
 __global__ __launch_bounds__(256) void bn_finalize_train_kernel(const float* __restrict__ partial, int N, int chunks, int C, double count,
                                          const float* __restrict__ weight, const float* __restrict__ bias,
                                          float* __restrict__ rmean, float* __restrict__ rvar, float momentum, float eps,
@@ -128,20 +149,38 @@ __global__ __launch_bounds__(256) void bn_finalize_train_kernel(const float* __r
   double sq[2];
   combine_records<2>(partial, 0, N * chunks, C, c, sq);
   if (threadIdx.x != 0) return;
-  const double mu = sq[0] / count;
-  double var = sq[1] / count - mu * mu;
-  if (var < 0.0) var = 0.0;
-  const float rs = (float)(1.0 / sqrt(var + (double)eps));
-  mean[c] = (float)mu;
-  rstd[c] = rs;
-  const float av = weight[c] * rs;
-  a[c] = av;
-  b[c] = bias[c] - (float)mu * av;
-  if (rmean != nullptr) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mu;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
-  }
+  bn_train_channel(sq[0], sq[1], count, c, weight, bias, rmean, rvar, momentum, eps, mean, rstd, a, b);
+}
+
+// The same finalize cut in two where a batch sharded over processes exchanges its statistics (ops.bn_sync).  Stage 1: this process's
+// records -> msg[grp][0..C) = sum x, [C..2C) = sum x^2, [2C] = its element count, in fp64 (the record-order combine above).  The
+// messages of the ranks are then SUMMED outside; stage 2 finalizes every group from the summed message, global count included.
+__global__ __launch_bounds__(256) void bn_sync_fwd_sums_kernel(const float* __restrict__ partial, int N, int chunks, int C, double count,
+                                                               double* __restrict__ msg) {
+  const int c = blockIdx.x, grp = blockIdx.y;
+  partial += (size_t)grp * N * chunks * 2 * C;
+  msg += (size_t)grp * (2 * C + 1);
+  double sq[2];
+  combine_records<2>(partial, 0, N * chunks, C, c, sq);
+  if (threadIdx.x != 0) return;
+  msg[c] = sq[0];
+  msg[C + c] = sq[1];
+  if (c == 0) msg[2 * C] = count;
+}
+
+__global__ __launch_bounds__(64) void bn_sync_fwd_finalize_kernel(const double* __restrict__ msg, int C, const float* __restrict__ weight,
+                                                                  const float* __restrict__ bias, float* __restrict__ rmean,
+                                                                  float* __restrict__ rvar, float momentum, float eps,
+                                                                  float* __restrict__ mean, float* __restrict__ rstd,
+                                                                  float* __restrict__ a, float* __restrict__ b,
+                                                                  long long* __restrict__ num_batches_tracked, int running_stride) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x, grp = blockIdx.y;
+  if (c >= C) return;
+  msg += (size_t)grp * (2 * C + 1);
+  mean += (size_t)grp * C; rstd += (size_t)grp * C; a += (size_t)grp * C; b += (size_t)grp * C;
+  if (rmean != nullptr) { rmean += (size_t)grp * running_stride; rvar += (size_t)grp * running_stride; }
+  if (c == 0 && grp == 0 && num_batches_tracked != nullptr) *num_batches_tracked += 1;
+  bn_train_channel(msg[c], msg[C + c], msg[2 * C], c, weight, bias, rmean, rvar, momentum, eps, mean, rstd, a, b);
 }
 
 __global__ void bn_finalize_eval_kernel(int C, const float* __restrict__ weight, const float* __restrict__ bias,
@@ -222,8 +261,11 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
 
 // Per group of the batch (`groups` of them; 1: the whole batch) its own sums (gsum[g][0][c] = dweight, gsum[g][1][c] = dbias: what the apply kernel
 // of the group needs), the parameters' gradient = their total over the groups (written, or added when `accumulate`).
+// ST = double: the sums are a message to be summed over the ranks of a sharded batch before the apply (ops.bn_sync) -- the
+// parameters' gradient stays THIS process's share (the gradient all-reduce totals it like every other parameter gradient).
+template <typename ST>
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int C, int groups,
-                                                              float* __restrict__ gsum, float* __restrict__ dweight,
+                                                              ST* __restrict__ gsum, float* __restrict__ dweight,
                                                               float* __restrict__ dbias, int accumulate) {
   const int c = blockIdx.x;
   double tw = 0.0, tb = 0.0;
@@ -232,14 +274,19 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     __syncthreads();                                   // (combine_records' scratch is reused)
     combine_records<2>(partial + (size_t)g * chunks * 2 * C, 0, chunks, C, c, sq);
     if (threadIdx.x == 0) {
-      gsum[((size_t)g * 2 + 0) * C + c] = (float)sq[1];
-      gsum[((size_t)g * 2 + 1) * C + c] = (float)sq[0];
+      gsum[((size_t)g * 2 + 0) * C + c] = (ST)sq[1];
+      gsum[((size_t)g * 2 + 1) * C + c] = (ST)sq[0];
       tw += (double)(float)sq[1]; tb += (double)(float)sq[0];
     }
   }
   if (threadIdx.x != 0) return;
   if (accumulate) { dweight[c] += (float)tw; dbias[c] += (float)tb; }
   else { dweight[c] = (float)tw; dbias[c] = (float)tb; }
+}
+
+__global__ void bn_sync_sums_to_f32_kernel(const double* __restrict__ sums, float* __restrict__ out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (float)sums[i];
 }
 
 // dy = a*(g - sum_g/M - xhat*sum_gx/M) with g = dz*act'(a*y+b), xhat = (y-mean)*rstd, folded per channel into
@@ -830,6 +877,24 @@ int dei2i_bn_finalize_train(int groups, int N, int HW, int C, int chunks, const 
   return (int)hipGetLastError();
 }
 
+int dei2i_bn_sync_fwd_sums(int groups, int N, int HW, int C, int chunks, const float* partial, double* msg, dei2i_stream s) {
+  if (groups <= 0 || N <= 0 || HW <= 0 || C <= 0 || chunks <= 0 || !partial || !msg) return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(bn_sync_fwd_sums_kernel, dim3(C, groups), dim3(combine_threads(N * chunks)), 0, (hipStream_t)s, partial, N, chunks,
+                     C, (double)N * (double)HW, msg);
+  return (int)hipGetLastError();
+}
+
+int dei2i_bn_sync_fwd_finalize(int groups, int C, const double* msg, const float* weight, const float* bias, float* running_mean,
+                               float* running_var, int running_stride, float momentum, float eps, float* mean, float* rstd, float* a,
+                               float* b, long long* num_batches_tracked, dei2i_stream s) {
+  if (groups <= 0 || C <= 0 || !msg || !weight || !bias || !mean || !rstd || !a || !b ||
+      (running_mean == nullptr) != (running_var == nullptr) || (running_mean != nullptr && groups > 1 && running_stride < C))
+    return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(bn_sync_fwd_finalize_kernel, dim3((C + 63) / 64, groups), dim3(64), 0, (hipStream_t)s, msg, C, weight, bias,
+                     running_mean, running_var, momentum, eps, mean, rstd, a, b, num_batches_tracked, running_stride);
+  return (int)hipGetLastError();
+}
+
 int dei2i_affine_act_stats_fwd(int dtype, int groups, int N, int HW, int C, const void* x, const float* a, const float* b,
                                const void* res, int act, void* out, float* partial, dei2i_stream s) {
   if (groups <= 0 || N <= 0 || N % groups != 0 || HW <= 0 || !cv_ok(dtype, C) || !x || !a || !b || !out || !partial) return DEI2I_ERR_BAD_ARG;
@@ -918,22 +983,13 @@ int dei2i_bn_bwd_partial(int dtype, int groups, size_t pixels, int C, const void
   return (int)hipGetLastError();
 }
 
-/* `groups` groups of `pixels` pixels each, coefficient rows (groups, C), records (groups, chunks, 2, C): two launches for all groups.
- * group_sums: (groups, 2, C) floats of scratch (each group's own sums, read by its share of the apply launch); dweight / dbias (C): the
- * total over the groups, written -- or added to when `accumulate` (a further use of the same parameters in this backward pass). */
-int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
-                       const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
-                       float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s) {
+// the apply launch of dei2i_bn_bwd_apply and dei2i_bn_sync_bwd_apply: `inv` = 1 / the pixels the sums were taken over
+static void launch_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a,
+                                const float* b, const float* mean, const float* rstd, int act, int train, const float* group_sums,
+                                float inv, void* dy, hipStream_t st) {
   const int vec = vec_of(dtype);
-  if (groups <= 0 || pixels == 0 || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !partial || !group_sums || !dweight ||
-      !dbias || !dy || chunks <= 0)
-    return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(combine_threads(chunks)), 0, st, partial, chunks, C, groups, group_sums,
-                     dweight, dbias, accumulate);
   const size_t nvec = pixels * (size_t)(C / vec);
   const unsigned grid = grid_for((nvec + 1) / 2, 256, 256u * 8u);
-  const float inv = 1.f / (float)pixels;
   const int cv = C / vec;
   const bool invc = (256 % cv) == 0;
   const float* gw = group_sums;
@@ -947,6 +1003,45 @@ int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* 
       hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(grid, groups), dim3(256), 0, st, (const T*)dz, (const T*)y, a, b, mean,
                          rstd, act, train, gw, gb, inv, (T*)dy, nvec, cv, 2 * C);
   });
+}
+
+/* `groups` groups of `pixels` pixels each, coefficient rows (groups, C), records (groups, chunks, 2, C): two launches for all groups.
+ * group_sums: (groups, 2, C) floats of scratch (each group's own sums, read by its share of the apply launch); dweight / dbias (C): the
+ * total over the groups, written -- or added to when `accumulate` (a further use of the same parameters in this backward pass). */
+int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
+                       const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
+                       float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s) {
+  if (groups <= 0 || pixels == 0 || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !partial || !group_sums || !dweight ||
+      !dbias || !dy || chunks <= 0)
+    return DEI2I_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)s;
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel<float>, dim3(C), dim3(combine_threads(chunks)), 0, st, partial, chunks, C, groups, group_sums,
+                     dweight, dbias, accumulate);
+  launch_bn_bwd_apply(dtype, groups, pixels, C, dz, y, a, b, mean, rstd, act, train, group_sums, 1.f / (float)pixels, dy, st);
+  return (int)hipGetLastError();
+}
+
+/* The same backward for a batch sharded over processes (ops.bn_sync), cut where the exchange happens: bwd_sums leaves this process's
+ * (groups, 2, C) fp64 sums as a message and its OWN share of dweight / dbias; bwd_apply takes the message summed over the ranks and the
+ * global pixel count per group (`count`; `pixels` is this process's, it sizes the launch). */
+int dei2i_bn_sync_bwd_sums(int groups, int C, const float* partial, int chunks, double* sums, float* dweight, float* dbias,
+                           int accumulate, dei2i_stream s) {
+  if (groups <= 0 || C <= 0 || chunks <= 0 || !partial || !sums || !dweight || !dbias) return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel<double>, dim3(C), dim3(combine_threads(chunks)), 0, (hipStream_t)s, partial, chunks, C,
+                     groups, sums, dweight, dbias, accumulate);
+  return (int)hipGetLastError();
+}
+
+int dei2i_bn_sync_bwd_apply(int dtype, int groups, size_t pixels, size_t count, int C, const void* dz, const void* y, const float* a,
+                            const float* b, const float* mean, const float* rstd, int act, const double* sums, float* group_sums,
+                            void* dy, dei2i_stream s) {
+  if (groups <= 0 || pixels == 0 || count < pixels || !cv_ok(dtype, C) || !dz || !y || !a || !b || !mean || !rstd || !sums ||
+      !group_sums || !dy)
+    return DEI2I_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)s;
+  const int n = groups * 2 * C;
+  hipLaunchKernelGGL(bn_sync_sums_to_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, sums, group_sums, n);
+  launch_bn_bwd_apply(dtype, groups, pixels, C, dz, y, a, b, mean, rstd, act, 1, group_sums, 1.f / (float)count, dy, st);
   return (int)hipGetLastError();
 }
 

@@ -115,7 +115,11 @@ class DefectGanModel(BaseModel):
         if mask is not None:
             masks = self._upload_mask(mask)
         else:       # the reference's RNG draws on the host (utils/util.py:61-71); the expansion to pixels on the device
-            row0, col0, keep = draw_shifted_mask(imgs.size(), self.opt.patch_size, self.opt.mask_ratio)
+            sync = ops.bn_sync.current          # data-parallel with sync_bn: the GLOBAL batch's draw on every rank, this rank's rows of it
+            n, world = imgs.size(0), sync.world if sync is not None else 1
+            row0, col0, keep = draw_shifted_mask((n * world,) + tuple(imgs.size()[1:]), self.opt.patch_size, self.opt.mask_ratio)
+            if world > 1:
+                keep = keep[sync.rank * n:(sync.rank + 1) * n]
             masks = expand_shifted_mask(self._upload_mask(keep), row0, col0, self.opt.patch_size, imgs.size(2), imgs.size(3))
         self.netG.clear_spade_cache()
         if self.opt.style_norm_block_type == "sean":             # defectgan_model.py:370-372

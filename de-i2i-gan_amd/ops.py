@@ -1055,11 +1055,35 @@ class bn_running_deferred:
         self._used, self._want = {}, 0
 
 
-def _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, momentum, eps, num_batches_tracked, groups=1):
+# ---- a batch sharded over processes: training-mode BatchNorm over the GLOBAL batch (synchronised BatchNorm) --------------------
+# Inside ``bn_sync(exchange)`` every training-mode BatchNorm finalizes in three stages instead of one launch, forward and backward
+# (csrc/reduce.hip: dei2i_bn_sync_*): this process's records -> one small fp64 message for all groups of the layer; ``exchange(msg)``
+# sums the message over the ranks in place, stream-ordered on the current stream (an all-reduce: ``parallel.GradReducer`` with
+# ``sync_bn``; any callable on the tensor serves); finalize / apply from the summed message.  The scope is read when the layer's FORWARD
+# runs and kept with it, so its backward exchanges whether or not the scope is still open.  ``rank`` / ``world`` tell the callers that
+# draw per-sample random numbers on the host (the MAE stage's patch masks) which rows of the global batch are theirs; every rank holds the same number of rows (backward's 1 / global pixels is world x local).
+class bn_sync:
+    current = None
+
+    def __init__(self, exchange, rank: int = 0, world: int = 1):
+        self.exchange = getattr(exchange, "sync_bn_exchange", exchange)
+        self.rank, self.world = int(getattr(exchange, "rank", rank)), int(getattr(exchange, "world", world))
+
+    def __enter__(self):
+        self.prev, bn_sync.current = bn_sync.current, self
+        return self
+
+    def __exit__(self, *exc):
+        bn_sync.current = self.prev
+        return False
+
+
+def _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, momentum, eps, num_batches_tracked, groups=1, sync=None):
     """BatchNorm2d statistics + affine coefficients of an NHWC tensor: a[c] = weight * rstd, b[c] = bias - mean * a (batch
     statistics in training mode, running statistics otherwise; running buffers and the counter are updated in place).
     a, b, mean, rstd of shape (groups, C): training-mode statistics per group of the batch (see bn_batch_groups).
-    The statistics come from the records its producer left (conv epilogue / affine_act_stats) when there are any."""
+    The statistics come from the records its producer left (conv epilogue / affine_act_stats) when there are any.
+    ``sync``: the bn_sync scope of a training-mode layer -- the statistics are those of the batch summed over the ranks."""
     n, h, w, c = y.shape
     dev, st = y.device, _stream()
     w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
@@ -1094,19 +1118,27 @@ def _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, m
         if deferred is None:                     # (the deferred buffers are zeros already)
             pad[0, 0, :nf], pad[0, 1, :nf] = running_mean, running_var
         rm, rv = pad[:, 0], pad[:, 1]
-    L.check(lib.dei2i_bn_finalize_train(groups, n // groups, h * w, c, chunks, _p(partial), _p(w32), _p(b32), _p(rm), _p(rv), rm.stride(0),
-                                        momentum, eps, _p(mean), _p(rstd), _p(a), _p(b), _p(num_batches_tracked), st), "bn_finalize_train")
+    if sync is not None:
+        msg = torch.empty((groups, 2 * c + 1), dtype=torch.float64, device=dev)      # sum x | sum x^2 | count, every group in one message
+        L.check(lib.dei2i_bn_sync_fwd_sums(groups, n // groups, h * w, c, chunks, _p(partial), _p(msg), st), "bn_sync_fwd_sums")
+        sync.exchange(msg)
+        L.check(lib.dei2i_bn_sync_fwd_finalize(groups, c, _p(msg), _p(w32), _p(b32), _p(rm), _p(rv), rm.stride(0), momentum, eps,
+                                               _p(mean), _p(rstd), _p(a), _p(b), _p(num_batches_tracked), _stream()), "bn_sync_fwd_finalize")
+    else:
+        L.check(lib.dei2i_bn_finalize_train(groups, n // groups, h * w, c, chunks, _p(partial), _p(w32), _p(b32), _p(rm), _p(rv), rm.stride(0),
+                                            momentum, eps, _p(mean), _p(rstd), _p(a), _p(b), _p(num_batches_tracked), st), "bn_finalize_train")
     if nf < c:
         live[0].copy_(rm[:, :nf])
         live[1].copy_(rv[:, :nf])
     return a, b, mean, rstd, nf
 
 
-def _bn_backward(lib, prec, dout, y, a, b, mean, rstd, act, training, weight, bias, nf, hint=None):
+def _bn_backward(lib, prec, dout, y, a, b, mean, rstd, act, training, weight, bias, nf, hint=None, sync=None):
     """-> (dy, dweight, dbias) of z = act(a*y + b) given dL/dz (csrc/reduce.hip: bn_bwd_partial / bn_bwd_apply).  ``hint``: the
     dgrad of the conv behind the layer may have left the reduction records already (_NormBwdHint).  a, b, mean, rstd of shape
     (groups, C): statistics per group of the batch (bn_batch_groups) -- the reductions and the apply run per group, the
-    parameter gradients are summed over the groups."""
+    parameter gradients are summed over the groups.  ``sync``: the bn_sync scope the forward ran in -- dy takes the reductions of the
+    batch summed over the ranks; dweight / dbias stay this process's share (the gradient exchange totals parameter gradients)."""
     st = _stream()
     have = hint.take(dout) if hint is not None else None
     dout = dout.contiguous()
@@ -1134,8 +1166,17 @@ def _bn_backward(lib, prec, dout, y, a, b, mean, rstd, act, training, weight, bi
             dw_ptr, db_ptr, accumulate = dweight.data_ptr(), dbias.data_ptr(), 0
     dy = torch.empty_like(y)
     gsum = torch.empty((groups, 2, c), dtype=torch.float32, device=y.device)      # each group's own sums, read by its share of the apply
-    L.check(lib.dei2i_bn_bwd_apply(prec.code, groups, pixels, c, _p(dout), _p(y), _p(a), _p(b), _p(mean), _p(rstd), act, 1 if training else 0,
-                                   _p(partial), chunks, _p(gsum), c_void_p(dw_ptr), c_void_p(db_ptr), accumulate, _p(dy), st), "bn_bwd_apply")
+    if sync is not None and training:
+        msg = torch.empty((groups, 2, c), dtype=torch.float64, device=y.device)        # sum g*xhat | sum g, every group in one message
+        L.check(lib.dei2i_bn_sync_bwd_sums(groups, c, _p(partial), chunks, _p(msg), c_void_p(dw_ptr), c_void_p(db_ptr), accumulate, st),
+                "bn_sync_bwd_sums")
+        sync.exchange(msg)
+        # (every rank holds the same number of rows: the global group is world x this process's pixels)
+        L.check(lib.dei2i_bn_sync_bwd_apply(prec.code, groups, pixels, pixels * sync.world, c, _p(dout), _p(y), _p(a), _p(b), _p(mean),
+                                            _p(rstd), act, _p(msg), _p(gsum), _p(dy), _stream()), "bn_sync_bwd_apply")
+    else:
+        L.check(lib.dei2i_bn_bwd_apply(prec.code, groups, pixels, c, _p(dout), _p(y), _p(a), _p(b), _p(mean), _p(rstd), act, 1 if training else 0,
+                                       _p(partial), chunks, _p(gsum), c_void_p(dw_ptr), c_void_p(db_ptr), accumulate, _p(dy), st), "bn_bwd_apply")
     if nf < c:
         dweight, dbias = wb[0, :nf].clone(), wb[1, :nf].clone()
     return dy, dweight, dbias
@@ -1153,8 +1194,9 @@ class _BatchNormAct(torch.autograd.Function):
         st = _stream()
         dev = y.device
         groups = bn_groups if training else 1
+        ctx.sync = bn_sync.current if training else None
         a, b, mean, rstd, nf = _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, momentum, eps,
-                                         num_batches_tracked, groups)
+                                         num_batches_tracked, groups, sync=ctx.sync)
         out = torch.empty_like(y)
         if res is not None:
             res = res.contiguous()
@@ -1189,7 +1231,7 @@ class _BatchNormAct(torch.autograd.Function):
         y, a, b, mean, rstd = ctx.saved_tensors
         weight, bias = ctx.params
         dy, dweight, dbias = _bn_backward(_lib_for(y), ctx.prec, dout, y, a, b, mean, rstd, ctx.act, ctx.training, weight, bias, ctx.nf,
-                                          hint=ctx.hint)
+                                          hint=ctx.hint, sync=ctx.sync)
         return dy, dweight, dbias, (dout if ctx.has_res else None), None, None, None, None, None, None, None, None
 
 
@@ -1214,8 +1256,9 @@ class _BnActConv(torch.autograd.Function):
         y1 = y1.contiguous()
         n, h, w, c = y1.shape
         lib = _lib_for(y1)
+        ctx.sync = bn_sync.current if training else None
         a, b, mean, rstd, nf = _bn_coefs(lib, y1, prec, bn_w, bn_b, running_mean, running_var, training, momentum, eps,
-                                         num_batches_tracked)
+                                         num_batches_tracked, sync=ctx.sync)
         couts = prec.pad(geom.cout)
         d = _desc(prec, geom, n, h, w, c, couts)
         wf = cache.get(weight, sources, prec, geom, c, couts, need_dgrad=any(s_.requires_grad for s_ in sources))[0]
@@ -1251,7 +1294,8 @@ class _BnActConv(torch.autograd.Function):
             dh = _conv_dgrad(lib, prec, geom, tuple(y1.shape), dy.shape[-1], dy, weight, ctx.cache, ctx.sources, False, y1.dtype, y1.device,
                              hint=hint)
             bn_w, bn_b = ctx.params
-            dy1, dbw, dbb = _bn_backward(lib, prec, dh, y1, a, b, mean, rstd, ctx.act, ctx.training, bn_w, bn_b, ctx.nf, hint=hint)
+            dy1, dbw, dbb = _bn_backward(lib, prec, dh, y1, a, b, mean, rstd, ctx.act, ctx.training, bn_w, bn_b, ctx.nf, hint=hint,
+                                         sync=ctx.sync)
         return (dy1, dbw, dbb, dw) + (None,) * 11
 
 

@@ -16,6 +16,21 @@ MI355X node (8 GPUs, point-to-point xGMI, no switch):
   ``norm_s`` / ``conv_s``; all of D during the G step) simply never enter a collective.
 * BatchNorm statistics stay local (per-shard), like torch DDP without SyncBN; ``broadcast_buffers`` copies rank 0's
   running stats to every rank (torch DDP ``broadcast_buffers`` semantics) -- parity definition in SURVEY.md 8e.
+* ``sync_bn=True`` (DefectGanTrainer / MAETrainer, opt-in): synchronised BatchNorm.  Every training-mode BatchNorm of the generator
+  takes its statistics, and its backward its two reductions, over the GLOBAL batch: N ranks, each on its rows, then compute what ONE
+  process computes on the whole batch (the reference's own single-process run; tests/test_ddp_sync_bn_gpu.py holds two ranks to its
+  goldens) instead of the gradient-accumulation semantics above.  Mechanism (``ops.bn_sync``): each layer's finalize runs as stage 1 (this
+  rank's records -> one fp64 message for all groups of the layer: 2C + 1 doubles per group forward, 2C backward), a SUM all-reduce of
+  that message in the compute stream's order, stage 2 (finalize / apply from the summed message).  The messages travel on a process
+  group of their own (``dist.new_group``) so that the latency-bound messages of backward need not queue behind the gradient buckets on
+  the gradients' communicator -- the reason for the second group, not a measured result.  dweight / dbias of the layer stay LOCAL: the
+  gradient exchange sums parameter gradients over ranks afterwards, the global sums would be counted ``world`` times.  Every rank
+  computes the same running statistics from the same summed message, so ``broadcast_buffers`` does nothing.  The MAE stage draws its
+  patch mask for the global batch on every rank (same RNG consumption; rank 0's CPU RNG state is broadcast at attach) and keeps its
+  rows.  Every rank must hold the same number of rows.  The equality covers the SPADE generator with the default options,
+  ``use_spectral`` and ``cycle_gan``; ``add_noise``, ``diff_aug`` and the SEAN blocks draw per-rank random numbers: they run with
+  ``sync_bn`` but equal no single-process run.  Counted apart from the gradients: ``stats["sync_bn_collectives"]`` / ``["sync_bn_bytes"]``.
+  Off (the default): nothing changes -- same kernels, same launches, same bits.  Eval-mode BatchNorm never exchanges.
 * ``attach_ddp`` broadcasts rank 0's parameters and buffers (spectral-norm u / v included) once, one flat message per
   network, like torch DDP does at construction: replicas start identical whatever each rank's seed or checkpoint was.
 * ``measure=True`` brackets every collective with events on the side stream and marks the end of backward on the compute
@@ -37,11 +52,14 @@ import torch.distributed as dist
 
 class GradReducer:
     def __init__(self, process_group=None, bucket_bytes: int = 16 << 20, direct_bytes: int = 4 << 20, overlap: bool = True,
-                 force_collectives: bool = False, measure: bool = False, comm_dtype: str = "fp32"):
+                 force_collectives: bool = False, measure: bool = False, comm_dtype: str = "fp32", sync_bn: bool = False,
+                 stats_group=None):
         if not dist.is_initialized():
             raise RuntimeError("GradReducer needs an initialised torch.distributed process group")
         self.pg = process_group
-        self.world = dist.get_world_size(process_group)
+        self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+        self.sync_bn = bool(sync_bn)
+        self.stats_pg = stats_group if stats_group is not None else process_group      # BatchNorm statistics messages (attach_ddp: own group)
         self.bucket_bytes, self.direct_bytes, self.overlap = bucket_bytes, direct_bytes, overlap
         self.active = self.world > 1 or force_collectives      # force: run the collective path on a 1-rank group (tests)
         self._attached = set()
@@ -49,7 +67,7 @@ class GradReducer:
         self._bucket: List[torch.Tensor] = []
         self._bucket_nbytes = 0
         self._inflight = []          # (work, flat, [grads]) to finish in reduce()
-        self.stats = {"collectives": 0, "bytes": 0}
+        self.stats = {"collectives": 0, "bytes": 0, "sync_bn_collectives": 0, "sync_bn_bytes": 0}
         self.measure = measure
         if comm_dtype not in ("fp32", "bf16"):
             raise ValueError(f"comm_dtype [{comm_dtype}] is not supported (fp32 | bf16)")
@@ -221,9 +239,25 @@ class GradReducer:
             for p in list(net.parameters()) + list(net.buffers()):
                 p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1
 
+    def sync_bn_exchange(self, msg: torch.Tensor) -> None:
+        """SUM ``msg`` (one BatchNorm layer's fp64 statistics message, ops.bn_sync) over the ranks in place, ordered on the current
+        stream like any kernel: RCCL joins the current stream on both sides, gloo returns when the sum is there."""
+        if not self.active:
+            return
+        dist.all_reduce(msg, op=dist.ReduceOp.SUM, group=self.stats_pg)
+        self.stats["sync_bn_collectives"] += 1
+        self.stats["sync_bn_bytes"] += msg.numel() * msg.element_size()
+
+    def bn_scope(self):
+        """The scope a trainer runs its model calls in: ``ops.bn_sync`` of this reducer with ``sync_bn`` on an active group, else nothing."""
+        if self.sync_bn and self.active:
+            from . import ops
+            return ops.bn_sync(self)
+        return _NullCtx()
+
     def broadcast_buffers(self, net: torch.nn.Module, src: int = 0) -> None:
         bufs = [b for b in net.buffers() if b.is_floating_point()]
-        if not self.active or not bufs:
+        if not self.active or not bufs or self.sync_bn:       # (sync_bn: every rank computed them from the same summed statistics)
             return
         flat = torch.cat([b.reshape(-1) for b in bufs])
         dist.broadcast(flat, src=src, group=self.pg)
@@ -244,14 +278,31 @@ class _NullCtx:
         return False
 
 
-def attach_ddp(trainer, process_group=None, **kw) -> GradReducer:
-    """Make a DefectGanTrainer or a stargan ``Solver`` data-parallel: gradients are summed across ranks after each backward and
-    averaged inside the fused Adam kernel.  DefectGanTrainer: generator BatchNorm buffers follow rank 0.  Solver: see
-    ``_attach_solver``."""
+def _broadcast_rng_state(process_group, device) -> None:
+    """rank 0's global CPU RNG state on every rank"""
+    state = torch.get_rng_state()
+    if dist.get_backend(process_group) == "nccl":          # RCCL moves device tensors only
+        state = state.to(device)
+    dist.broadcast(state, src=0, group=process_group)
+    torch.set_rng_state(state.cpu())
+
+
+def attach_ddp(trainer, process_group=None, sync_bn: bool = False, **kw) -> GradReducer:
+    """Make a DefectGanTrainer, an MAETrainer or a stargan ``Solver`` data-parallel: gradients are summed across ranks after each
+    backward and averaged inside the fused Adam kernel.  The two trainers: generator BatchNorm statistics stay per rank and the
+    buffers follow rank 0 -- or, with ``sync_bn=True``, are taken over the global batch, which makes N ranks on their rows equal ONE
+    process on the whole batch (module docstring: mechanism, and which options the equality covers -- ``add_noise``, ``diff_aug`` and
+    SEAN draw per-rank random numbers and equal no single-process run).  Solver: see ``_attach_solver`` (it has no batch statistics:
+    ``sync_bn`` is a ValueError)."""
     from .stargan import Solver
     if isinstance(trainer, Solver):
+        if sync_bn:
+            raise ValueError("attach_ddp(solver, sync_bn=True): the stargan-v2 networks have no batch statistics to synchronise")
         return _attach_solver(trainer, process_group, **kw)
-    red = GradReducer(process_group, **kw)
+    if sync_bn:        # the statistics messages on a communicator of their own (every rank of the group calls attach_ddp: collective)
+        ranks = dist.get_process_group_ranks(process_group) if process_group is not None else None
+        kw["stats_group"] = dist.new_group(ranks=ranks)
+    red = GradReducer(process_group, sync_bn=sync_bn, **kw)
     release = getattr(trainer, "release_graphs", None)          # (graph_step: the captured step has no collectives)
     if release is not None:
         release()
@@ -263,6 +314,8 @@ def attach_ddp(trainer, process_group=None, **kw) -> GradReducer:
     if isinstance(mask_token, torch.nn.Module):
         red.attach(mask_token)
         red.broadcast_parameters(mask_token)
+    if sync_bn and red.world > 1:                                   # the MAE stage's mask draws: the same global draw on every rank
+        _broadcast_rng_state(process_group, torch.device(trainer.opt.device))
     trainer.reducer = red
     return red
 
@@ -280,10 +333,6 @@ def _attach_solver(solver, process_group=None, **kw) -> GradReducer:
     for net in vars(solver.nets_ema).values():
         red.broadcast_parameters(net)
     if red.world > 1:
-        state = torch.get_rng_state()
-        if dist.get_backend(process_group) == "nccl":          # RCCL moves device tensors only
-            state = state.to(solver.device)
-        dist.broadcast(state, src=0, group=process_group)
-        torch.set_rng_state(state.cpu())
+        _broadcast_rng_state(process_group, solver.device)
     solver.reducer = red
     return red

@@ -1,4 +1,5 @@
 """BaseTrainer (trainers/base_trainer.py:12-131): model creation, one optimizer + one LR scheduler per network."""
+import contextlib
 import math
 from collections import defaultdict
 
@@ -126,6 +127,12 @@ class BaseTrainer:
                     self.losses[kind][name].append(flat[i])
                     i += 1
             self._pending = []
+
+    def _bn_scope(self):
+        """What the model calls of a step run in: under a reducer with ``sync_bn`` (parallel.attach_ddp) the scope in which training-mode
+        BatchNorm takes the global batch's statistics and the MAE stage draws the global batch's masks (ops.bn_sync); else nothing."""
+        red = getattr(self, "reducer", None)
+        return red.bn_scope() if red is not None else contextlib.nullcontext()
 
     def release_graphs(self):
         """Drop the captured graphs of ``graph_step`` (the next step() warms up and captures again)."""

@@ -43,7 +43,8 @@ class DefectGanTrainer(BaseTrainer):
         with_e = "E" in self.optimizers                  # adain: the StyleExtractor is trained by the G loss (:140-141,161-163)
         if with_e:
             self.optimizers["E"].zero_grad()
-        losses = self.model("generator", bg_data, df_labels, df_data)
+        with self._bn_scope():
+            losses = self.model("generator", bg_data, df_labels, df_data)
         gan_loss, clf_loss, rec_loss, sd_cyc_loss, sd_con_loss = losses[:5]
         g_loss = gan_loss + clf_loss * self.loss_weights["clf_g"] + rec_loss * self.loss_weights["rec"] + \
             sd_cyc_loss * self.loss_weights["sd_cyc"] + sd_con_loss * self.loss_weights["sd_con"]
@@ -56,7 +57,7 @@ class DefectGanTrainer(BaseTrainer):
         if with_e:
             self.optimizers["E"].step()
         if self.reducer is not None:
-            self.reducer.broadcast_buffers(self.model.netG)      # BatchNorm running stats follow rank 0
+            self.reducer.broadcast_buffers(self.model.netG)      # BatchNorm running stats follow rank 0 (sync_bn: equal already)
         self._record([("gan", "G"), ("clf", "G"), ("aux", "rec"), ("aux", "cyc"), ("aux", "con")],
                      [gan_loss, clf_loss, rec_loss, sd_cyc_loss, sd_con_loss])
         if self.distill:                                  # (:142-146) logged; the gradients were taken inside the SEAN layers
@@ -65,7 +66,8 @@ class DefectGanTrainer(BaseTrainer):
     def _train_discriminator_once(self, bg_data, df_labels, df_data):
         """defectgan_trainer.py:170-180"""
         self.optimizers["D"].zero_grad()
-        gan_loss, clf_loss = self.model("discriminator", bg_data, df_labels, df_data)
+        with self._bn_scope():
+            gan_loss, clf_loss = self.model("discriminator", bg_data, df_labels, df_data)
         d_loss = gan_loss + clf_loss * self.loss_weights["clf_d"]
         d_loss.backward()
         if self.reducer is not None:

@@ -59,7 +59,8 @@ class MAETrainer(BaseTrainer):
     def _train_generator_once(self, data, labels):
         """mae_trainer.py:124-147"""
         self.optimizers["G"].zero_grad()
-        losses = self.model("mae_generator", data, labels)
+        with self._bn_scope():
+            losses = self.model("mae_generator", data, labels)
         rec_loss, gan_loss, clf_loss = losses[:3]
         g_loss = gan_loss + rec_loss * self.loss_weights["rec"] + clf_loss * self.loss_weights["clf_G"]
         self._scaled_update(g_loss, "G")
@@ -72,7 +73,8 @@ class MAETrainer(BaseTrainer):
     def _train_discriminator_once(self, data, labels):
         """mae_trainer.py:149-158"""
         self.optimizers["D"].zero_grad()
-        gan_loss, clf_loss = self.model("mae_discriminator", data, labels)
+        with self._bn_scope():
+            gan_loss, clf_loss = self.model("mae_discriminator", data, labels)
         d_loss = gan_loss + clf_loss * self.loss_weights["clf_D"]
         self._scaled_update(d_loss, "D")
         self._record([("gan", "D"), ("clf", "D")], [gan_loss, clf_loss])

@@ -165,6 +165,26 @@ int dei2i_bn_bwd_partial(int dtype, int groups, size_t pixels, int C, const void
 int dei2i_bn_bwd_apply(int dtype, int groups, size_t pixels, int C, const void* dz, const void* y, const float* a, const float* b,
                        const float* mean, const float* rstd, int act, int train, const float* partial, int chunks,
                        float* group_sums, float* dweight, float* dbias, int accumulate, void* dy, dei2i_stream s);
+/* ---- BatchNorm over a batch that is sharded across processes (synchronised BatchNorm; ops.bn_sync) ----
+ * The two finalize steps above, each cut in two at the point where the ranks exchange: stage 1 turns this process's records into one
+ * small fp64 message, the caller SUMS the messages of all ranks (all-reduce), stage 2 finishes from the summed message.  Records,
+ * groups, coefficient rows, running buffers (running_stride) and num_batches_tracked are those of dei2i_bn_finalize_train /
+ * dei2i_bn_bwd_apply; N, HW, pixels are THIS process's.  No atomics: the fp64 combine runs in record order.
+ *   fwd_sums:     msg (groups, 2*C + 1) doubles = sum x | sum x^2 | the group's element count (N * HW)
+ *   fwd_finalize: mean / rstd / a / b, running update (unbiased variance with the summed count) and the counter from the summed msg
+ *   bwd_sums:     sums (groups, 2, C) doubles = sum g*xhat | sum g per group; dweight / dbias = THIS process's total over its groups
+ *                 (written, or added when `accumulate`) -- local on purpose: parameter gradients are summed over ranks afterwards
+ *   bwd_apply:    dy from the summed sums and `count` = the group's pixels over all ranks (`pixels`: this process's, sizes the launch);
+ *                 group_sums: (groups, 2, C) floats of scratch */
+int dei2i_bn_sync_fwd_sums(int groups, int N, int HW, int C, int chunks, const float* partial, double* msg, dei2i_stream s);
+int dei2i_bn_sync_fwd_finalize(int groups, int C, const double* msg, const float* weight, const float* bias, float* running_mean,
+                               float* running_var, int running_stride, float momentum, float eps, float* mean, float* rstd, float* a,
+                               float* b, long long* num_batches_tracked, dei2i_stream s);
+int dei2i_bn_sync_bwd_sums(int groups, int C, const float* partial, int chunks, double* sums, float* dweight, float* dbias,
+                           int accumulate, dei2i_stream s);
+int dei2i_bn_sync_bwd_apply(int dtype, int groups, size_t pixels, size_t count, int C, const void* dz, const void* y, const float* a,
+                            const float* b, const float* mean, const float* rstd, int act, const double* sums, float* group_sums,
+                            void* dy, dei2i_stream s);
 /* SPADE-family backward.  z = act(v), v = xhat*(1+gamma)+beta, act of the ReLU family with negative slope `slope` (0: SPADE's
  * ReLU, 0.2: LeakyReLU, 1: none), is RECOMPUTED from x and the gamma/beta table in both passes (the op keeps neither its output
  * nor a dxhat tensor): g = dz*(v>0 ? 1 : slope); dgamma = g*xhat, dbeta = g -> dgb (T: dense tensor, or the (N,5,5,2C)
