@@ -6,12 +6,6 @@
 
 namespace dei2i {
 
-int g_use_wgrad_v2 = 1;
-int g_use_wgrad_halo = 1;
-int g_use_wgrad_thin = 1;
-int g_dgrad_s2_ring = 1;          // option "dgrad_s2_ring": stride-2 reflect dgrads decomposed (interior into dx + ring rectangles)
-extern int g_halo16, g_halo16_fold;
-
 static ConvShape to_shape(const dei2i_conv* c) {
   ConvShape s;
   s.N = c->N; s.H = c->H; s.W = c->W; s.Cin = c->Cin; s.Cout = c->Cout;
@@ -248,11 +242,7 @@ size_t dei2i_packed_fwd_elems(const dei2i_conv* c) { return (size_t)c->Cout * c-
 size_t dei2i_wgrad_slab_elems(const dei2i_conv* c) { return (size_t)wgrad_slab_elems(c->Cout, c->kh * c->kw * c->CinS); }
 
 size_t dei2i_packed_dgrad_elems(const dei2i_conv* c) {
-  size_t n = 0;
-  for (int ay = 0; ay < c->stride; ++ay)
-    for (int ax = 0; ax < c->stride; ++ax)
-      n += (size_t)c->Cin * dgrad_taps(c->kh, c->stride, ay) * dgrad_taps(c->kw, c->stride, ax) * c->CoutS;
-  return n;
+  return (size_t)for_each_dgrad_class(c->Cin, c->CoutS, c->kh, c->kw, c->stride, [](const DgradClass&) {});
 }
 
 int dei2i_pack_weight_fwd(const dei2i_conv* c, const float* w, void* packed, dei2i_stream s) {
@@ -271,21 +261,16 @@ int dei2i_pack_weight_dgrad(const dei2i_conv* c, const float* w, void* packed, d
   if (!valid_conv(c) || !w || !packed) return DEI2I_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)s;
   const size_t esz = c->dtype == DT_BF16 ? 2 : 4;
-  size_t off = 0;
-  for (int ay = 0; ay < c->stride; ++ay)
-    for (int ax = 0; ax < c->stride; ++ax) {
-      const int th = dgrad_taps(c->kh, c->stride, ay), tw = dgrad_taps(c->kw, c->stride, ax);
-      const size_t total = (size_t)c->Cin * th * tw * c->CoutS;
-      if (total == 0) continue;
-      const unsigned grid = grid_for(total, 256);
-      void* dst = (char*)packed + off * esz;
-      by_dtype(c->dtype, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL(pack_dgrad_kernel<T>, dim3(grid), dim3(256), 0, st, w, (T*)dst, c->Cout, c->Cin, c->CoutS, c->kh, c->kw,
-                           c->stride, ay, ax, th, tw);
-      });
-      off += total;
-    }
+  for_each_dgrad_class(c->Cin, c->CoutS, c->kh, c->kw, c->stride, [&](const DgradClass& k) {
+    if (k.count == 0) return;
+    const unsigned grid = grid_for((size_t)k.count, 256);
+    void* dst = (char*)packed + (size_t)k.off * esz;
+    by_dtype(c->dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(pack_dgrad_kernel<T>, dim3(grid), dim3(256), 0, st, w, (T*)dst, c->Cout, c->Cin, c->CoutS, c->kh, c->kw,
+                         c->stride, k.ay, k.ax, k.th, k.tw);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -294,35 +279,26 @@ int dei2i_pack_weight_both(const dei2i_conv* c, const float* w, void* packed_fwd
   PackAll pa;
   pa.fwd_total = (long long)dei2i_packed_fwd_elems(c);
   pa.ncls = 0;
-  long long off = 0;
-  for (int ay = 0; ay < c->stride; ++ay)
-    for (int ax = 0; ax < c->stride; ++ax) {
-      const int th = dgrad_taps(c->kh, c->stride, ay), tw = dgrad_taps(c->kw, c->stride, ax);
-      const long long total = (long long)c->Cin * th * tw * c->CoutS;
-      if (total == 0) continue;
-      pa.ay[pa.ncls] = ay; pa.ax[pa.ncls] = ax; pa.th[pa.ncls] = th; pa.tw[pa.ncls] = tw;
-      pa.cls_begin[pa.ncls++] = off;
-      off += total;
-    }
+  const long long off = for_each_dgrad_class(c->Cin, c->CoutS, c->kh, c->kw, c->stride, [&](const DgradClass& k) {
+    if (k.count == 0) return;
+    pa.ay[pa.ncls] = k.ay; pa.ax[pa.ncls] = k.ax; pa.th[pa.ncls] = k.th; pa.tw[pa.ncls] = k.tw;
+    pa.cls_begin[pa.ncls++] = k.off;
+  });
   pa.cls_begin[pa.ncls] = off;
   for (int k = pa.ncls + 1; k < 17; ++k) pa.cls_begin[k] = off;
   if (c->kh * c->kw <= PT_MAXTAPS && (long long)c->Cout * c->Cin * c->kh * c->kw >= (1 << 16) && c->CoutS % 8 == 0) {
     const dim3 tg((c->CinS + PT_CI - 1) / PT_CI, (c->CoutS + PT_CO - 1) / PT_CO);
     const size_t plds = (size_t)PT_CO * c->kh * c->kw * PT_ROW * sizeof(float);       // <= 67.6 KB
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(pack_tiled_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          PT_CO * PT_MAXTAPS * PT_ROW * (int)sizeof(float));
-      hipFuncSetAttribute(reinterpret_cast<const void*>(pack_tiled_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          PT_CO * PT_MAXTAPS * PT_ROW * (int)sizeof(float));
-      attr_done = true;
-    }
+    hipError_t e = hipSuccess;
     by_dtype(c->dtype, [&](auto t) {
       using T = decltype(t);
+      e = ensure_dyn_lds(reinterpret_cast<const void*>(pack_tiled_kernel<T>), plds);
+      if (e != hipSuccess) return;
       hipLaunchKernelGGL(pack_tiled_kernel<T>, tg, dim3(256), plds, (hipStream_t)s, w, (T*)packed_fwd, (T*)packed_dgrad, pa, c->Cout,
                          c->Cin, c->CinS, c->CoutS, c->kh, c->kw, c->stride);
+      e = hipGetLastError();
     });
-    return (int)hipGetLastError();
+    return (int)e;
   }
   const unsigned grid = grid_for((size_t)(pa.fwd_total + off), 256);
   by_dtype(c->dtype, [&](auto t) {
@@ -372,15 +348,11 @@ int dei2i_conv2d_dgrad(const dei2i_conv* c, const void* dy, const void* wd_packe
   if (ncls > 4) return DEI2I_ERR_BAD_ARG;
   GatherDesc descs[4];
   long long woffs[4];
-  long long off = 0;
   int n = 0;
-  for (int ay = 0; ay < c->stride; ++ay)
-    for (int ax = 0; ax < c->stride; ++ax) {
-      descs[n] = make_dgrad_desc(sh, c->CoutS, ay, ax);
-      woffs[n] = off;
-      off += (long long)c->Cin * dgrad_taps(c->kh, c->stride, ay) * dgrad_taps(c->kw, c->stride, ax) * c->CoutS;
-      ++n;
-    }
+  for_each_dgrad_class(c->Cin, c->CoutS, c->kh, c->kw, c->stride, [&](const DgradClass& k) {
+    descs[n] = make_dgrad_desc(sh, c->CoutS, k.ay, k.ax);
+    woffs[n++] = k.off;
+  });
   // all parity classes in ONE launch (blockIdx.y); split-K accumulates every class into the shared fp32 workspace
   return (int)gather_gemm_multi(c->dtype, descs, woffs, n, dy, wd_packed, c->Cin, nullptr, dx_ext, ws, ws_bytes, c->CinS,
                                 ACT_NONE, (hipStream_t)s);
@@ -392,6 +364,17 @@ int dei2i_conv2d_dgrad(const dei2i_conv* c, const void* dy, const void* wd_packe
  * boundary dgrad on the input grid (one GEMM over N*H*W rows straight into dx -- tile-aligned, no full-size fold
  * pass), the reflect ring (4 thin rectangles of the frame) is a second small multi-descriptor GEMM into ext_scratch,
  * and fold_border_kernel adds the ring's images to the O(perimeter) border pixels of dx. */
+static int fold_border(const dei2i_conv* c, const void* ext, void* dx, int pad, hipStream_t st) {
+  const int vec = c->dtype == DT_BF16 ? 8 : 4;
+  const size_t total = (size_t)c->N * (2 * pad * c->W + 2 * pad * (c->H - 2 * pad)) * (c->CinS / vec);
+  by_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(fold_border_kernel<T>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const T*)ext, (T*)dx, c->N, c->H, c->W,
+                       c->CinS, pad);
+  });
+  return (int)hipGetLastError();
+}
+
 int dei2i_conv2d_dgrad_input(const dei2i_conv* c, const void* dy, const void* wd_packed, void* ext_scratch, void* dx, float* ws,
                              size_t ws_bytes, dei2i_stream s) {
   if (!valid_conv(c) || !dy || !wd_packed || !dx) return DEI2I_ERR_BAD_ARG;
@@ -407,22 +390,13 @@ int dei2i_conv2d_dgrad_input(const dei2i_conv* c, const void* dy, const void* wd
     const GatherDesc interior = make_dgrad_desc(sh, c->CoutS, 0, 0);          // zero: the input grid itself
     if (c->dtype == DT_BF16 && c->kh == 3 && c->kw == 3 && p == 1) {
       // large grids: the 16 x 32 tile kernel folds the ring AND the four corners itself (conv_halo16.hip FOLD): one launch
-      hipError_t ef = halo16_conv(interior, dy, wd_packed, c->Cin, nullptr, dx, c->CinS, ACT_NONE, num_cu(), st, nullptr, nullptr, true);
+      hipError_t ef = halo16_conv(interior, dy, wd_packed, c->Cin, nullptr, dx, c->CinS, ACT_NONE, st, nullptr, nullptr, true);
       if (ef != hipErrorNotSupported) return (int)ef;
     }
     hipError_t e = gather_gemm(c->dtype, interior, dy, wd_packed, c->Cin, nullptr, dx, ws, ws_bytes, c->CinS, ACT_NONE, st);
     if (e != hipSuccess) return (int)e;
-    const int OH = c->H + 2 * p, OW = c->W + 2 * p;
-    GatherDesc ring[4] = {sub_rect_desc(ring_frame, 0, p, 0, OW), sub_rect_desc(ring_frame, c->H + p, p, 0, OW),
-                          sub_rect_desc(ring_frame, p, c->H, 0, p), sub_rect_desc(ring_frame, p, c->H, c->W + p, p)};
-    if (c->kh == 2 * p + 1 && c->kw == 2 * p + 1) {
-      // "same" convs: the top p frame rows only see tap rows 0..p-1 (the others read above dY), the bottom rows only
-      // tap rows kh-p..kh-1, likewise the side columns -- run each rectangle on its live taps (a third of K for 3x3)
-      ring[0] = sub_taps_desc(ring[0], 0, p, 0, c->kw);
-      ring[1] = sub_taps_desc(ring[1], c->kh - p, p, 0, c->kw);
-      ring[2] = sub_taps_desc(ring[2], 0, c->kh, 0, p);
-      ring[3] = sub_taps_desc(ring[3], 0, c->kh, c->kw - p, p);
-    }
+    GatherDesc ring[4];
+    reflect_ring_descs(ring_frame, c->H, c->W, p, c->kh, c->kw, ring);
     const long long woffs[4] = {0, 0, 0, 0};
     // ring launch: dead taps are skipped (2 of 3 tap rows / columns fall outside dY for a whole tile); split-K with a
     // compact workspace -- the partials are indexed by ring row, so memset / finalize touch ring rows only
@@ -430,18 +404,9 @@ int dei2i_conv2d_dgrad_input(const dei2i_conv* c, const void* dy, const void* wd
     e = gather_gemm_multi(c->dtype, ring, woffs, 4, dy, wd_packed, c->Cin, nullptr, ext_scratch, ws, ws_bytes, c->CinS, ACT_NONE, st,
                           true);
     if (e != hipSuccess) return (int)e;
-    const int vec = c->dtype == DT_BF16 ? 8 : 4;
-    const size_t total = (size_t)c->N * (2 * p * c->W + 2 * p * (c->H - 2 * p)) * (c->CinS / vec);
-    const unsigned grid = grid_for(total, 256);
-    if (c->dtype == DT_BF16)
-      hipLaunchKernelGGL(fold_border_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)ext_scratch, (bf16_t*)dx, c->N,
-                         c->H, c->W, c->CinS, p);
-    else
-      hipLaunchKernelGGL(fold_border_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)ext_scratch, (float*)dx, c->N,
-                         c->H, c->W, c->CinS, p);
-    return (int)hipGetLastError();
+    return fold_border(c, ext_scratch, dx, p, st);
   }
-  if (reflect && g_dgrad_s2_ring && c->stride == 2 && c->kh == 4 && c->kw == 4 && p == 1 && !c->up && c->H % 2 == 0 && c->W % 2 == 0 &&
+  if (reflect && g_opt.dgrad_s2_ring && c->stride == 2 && c->kh == 4 && c->kw == 4 && p == 1 && !c->up && c->H % 2 == 0 && c->W % 2 == 0 &&
       c->H >= 8 && c->W >= 8 && (size_t)c->N * c->H * c->W * c->CinS >= ((size_t)48 << 20)) {     // (the fold pass costs ~0.5 us per M elements, the ring ~30 us)
     // The stride-2 4x4 convs of the encoder / discriminator (generator.py:107-116, discriminator.py:60-77), large frames: the same
     // decomposition as above, per parity class.  The frame's interior is the zero-boundary dgrad on the input grid (four classes,
@@ -449,43 +414,21 @@ int dei2i_conv2d_dgrad_input(const dei2i_conv* c, const void* dy, const void* wd
     // 256 x 256 x 64 x 32 images); frame row 0 / H+1 and column 0 / W+1 are one-pixel rectangles of the two classes of their
     // parity, two small launches into ext_scratch (dead taps skipped), folded onto rows 1 / H-2 and columns 1 / W-2 of dx.
     ConvShape sh = to_shape(c);
-    GatherDesc fr[2][2], in4[4];
-    long long woff[2][2], woffs[4], off = 0;
-    for (int ay = 0; ay < 2; ++ay)
-      for (int ax = 0; ax < 2; ++ax) {
-        fr[ay][ax] = make_dgrad_desc(sh, c->CoutS, ay, ax);
-        woff[ay][ax] = off;
-        off += (long long)c->Cin * dgrad_taps(c->kh, 2, ay) * dgrad_taps(c->kw, 2, ax) * c->CoutS;
-      }
+    GatherDesc rows[4], cols[4], in4[4];
+    long long wrows4[4], wcols4[4], woffs[4];
+    s2_ring_descs(sh, c->CoutS, rows, wrows4, cols, wcols4);
     sh.pad_mode = PAD_ZERO;
-    for (int ay = 0; ay < 2; ++ay)
-      for (int ax = 0; ax < 2; ++ax) { in4[2 * ay + ax] = make_dgrad_desc(sh, c->CoutS, ay, ax); woffs[2 * ay + ax] = woff[ay][ax]; }
+    for_each_dgrad_class(c->Cin, c->CoutS, c->kh, c->kw, 2, [&](const DgradClass& k) {
+      in4[2 * k.ay + k.ax] = make_dgrad_desc(sh, c->CoutS, k.ay, k.ax);
+      woffs[2 * k.ay + k.ax] = k.off;
+    });
     hipError_t e = gather_gemm_multi(c->dtype, in4, woffs, 4, dy, wd_packed, c->Cin, nullptr, dx, ws, ws_bytes, c->CinS, ACT_NONE, st);
     if (e != hipSuccess) return (int)e;
-    // frame rows: hp = 0 is row 0 of the classes ay = 0, hp = H + 1 (odd) the last row of the classes ay = 1; all their columns
-    const GatherDesc rows[4] = {sub_rect_desc(fr[0][0], 0, 1, 0, fr[0][0].Wo), sub_rect_desc(fr[0][1], 0, 1, 0, fr[0][1].Wo),
-                                sub_rect_desc(fr[1][0], fr[1][0].Ho - 1, 1, 0, fr[1][0].Wo),
-                                sub_rect_desc(fr[1][1], fr[1][1].Ho - 1, 1, 0, fr[1][1].Wo)};
-    const long long wrows4[4] = {woff[0][0], woff[0][1], woff[1][0], woff[1][1]};
     e = gather_gemm_multi(c->dtype, rows, wrows4, 4, dy, wd_packed, c->Cin, nullptr, ext_scratch, ws, ws_bytes, c->CinS, ACT_NONE, st, true);
     if (e != hipSuccess) return (int)e;
-    // frame columns without the corners (they are in the rows): wp = 0 is column 0 of the classes ax = 0 (class ay = 0 without its
-    // row 0, class ay = 1 without its last row), wp = W + 1 the last column of the classes ax = 1
-    const GatherDesc cols[4] = {sub_rect_desc(fr[0][0], 1, fr[0][0].Ho - 1, 0, 1), sub_rect_desc(fr[1][0], 0, fr[1][0].Ho - 1, 0, 1),
-                                sub_rect_desc(fr[0][1], 1, fr[0][1].Ho - 1, fr[0][1].Wo - 1, 1),
-                                sub_rect_desc(fr[1][1], 0, fr[1][1].Ho - 1, fr[1][1].Wo - 1, 1)};
-    const long long wcols4[4] = {woff[0][0], woff[1][0], woff[0][1], woff[1][1]};
     e = gather_gemm_multi(c->dtype, cols, wcols4, 4, dy, wd_packed, c->Cin, nullptr, ext_scratch, ws, ws_bytes, c->CinS, ACT_NONE, st, true);
     if (e != hipSuccess) return (int)e;
-    const int vec = c->dtype == DT_BF16 ? 8 : 4;
-    const size_t total = (size_t)c->N * (2 * c->W + 2 * (c->H - 2)) * (c->CinS / vec);
-    if (c->dtype == DT_BF16)
-      hipLaunchKernelGGL(fold_border_kernel<bf16_t>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const bf16_t*)ext_scratch, (bf16_t*)dx,
-                         c->N, c->H, c->W, c->CinS, 1);
-    else
-      hipLaunchKernelGGL(fold_border_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, st, (const float*)ext_scratch, (float*)dx, c->N,
-                         c->H, c->W, c->CinS, 1);
-    return (int)hipGetLastError();
+    return fold_border(c, ext_scratch, dx, 1, st);
   }
   const int rc = dei2i_conv2d_dgrad(c, dy, wd_packed, ext_scratch, ws, ws_bytes, s);
   if (rc != 0) return rc;
@@ -493,15 +436,18 @@ int dei2i_conv2d_dgrad_input(const dei2i_conv* c, const void* dy, const void* wd
 }
 
 /* ---- input gradient + the backward reductions of the norm layer in front of the conv, one launch (conv_halo16.hip EPIN) ---- */
+// the interior of the padded frame: the zero-boundary dgrad on the input grid itself
+static GatherDesc interior_dgrad_desc(const dei2i_conv* c) {
+  ConvShape sh = to_shape(c);
+  sh.pad_mode = PAD_ZERO;
+  return make_dgrad_desc(sh, c->CoutS, 0, 0);
+}
+
 static bool dgrad_norm_shape_ok(const dei2i_conv* c) {
-  if (!g_halo16 || !g_halo16_fold) return false;   // A/B options
+  if (!g_opt.halo16 || !g_opt.halo16_fold) return false;   // A/B options
   if (!valid_conv(c) || c->dtype != DT_BF16 || c->up) return false;
   if (c->kh != 3 || c->kw != 3 || c->stride != 1 || c->pad != 1 || c->pad_mode != PAD_REFLECT) return false;
-  if (c->H % 16 != 0 || c->W % 32 != 0 || c->H < 32 || c->W < 64 || c->CinS < 64 || c->CinS % 8 != 0 || c->CoutS % 32 != 0) return false;
-  if ((long long)c->N * c->H * c->W * c->CoutS >= (1ll << 31)) return false;
-  const int tiles_m = c->N * (c->H / 16) * (c->W / 32);
-  const int tn = c->CinS >= 128 ? (c->CinS + 127) / 128 : 1;
-  return tiles_m * tn >= (num_cu() * 7) / 8;
+  return halo16_shape_ok(interior_dgrad_desc(c), c->CinS, true, true, false);
 }
 
 int dei2i_conv2d_dgrad_norm_supported(const dei2i_conv* c) { return dgrad_norm_shape_ok(c) ? 1 : 0; }
@@ -515,15 +461,12 @@ int dei2i_conv2d_dgrad_input_norm(const dei2i_conv* c, const void* dy, const voi
   const int kind = en->kind;
   if (kind == 1 ? !en->gb : (kind != 2 || !en->a || !en->b || en->up)) return DEI2I_ERR_BAD_ARG;
   if (en->group_images < 0 || (en->group_images > 0 && c->N % en->group_images != 0)) return DEI2I_ERR_BAD_ARG;
-  ConvShape sh = to_shape(c);
-  sh.pad_mode = PAD_ZERO;
-  const GatherDesc interior = make_dgrad_desc(sh, c->CoutS, 0, 0);
+  const GatherDesc interior = interior_dgrad_desc(c);
   EpiNorm e;
   e.x = (const uint16_t*)en->x; e.mean = en->mean; e.rstd = en->rstd; e.gb = (const uint16_t*)en->gb; e.a = en->a; e.b = en->b;
   e.partial = en->partial; e.kind = en->kind; e.up = en->up; e.act = en->act;
   e.group_images = kind == 2 ? en->group_images : 0;
-  hipError_t ef = halo16_conv(interior, dy, wd_packed, c->Cin, nullptr, dx, c->CinS, ACT_NONE, num_cu(), (hipStream_t)s, nullptr, nullptr,
-                              true, &e);
+  hipError_t ef = halo16_conv(interior, dy, wd_packed, c->Cin, nullptr, dx, c->CinS, ACT_NONE, (hipStream_t)s, nullptr, nullptr, true, &e);
   return ef == hipErrorNotSupported ? DEI2I_ERR_BAD_ARG : (int)ef;
 }
 
@@ -537,29 +480,16 @@ int dei2i_conv2d_wgrad_oihw(const dei2i_conv* c, const void* x, const void* dy, 
   GatherDesc g = make_fwd_desc(to_shape(c), c->CinS);
   const size_t packed = (size_t)wgrad_slab_elems(c->Cout, g.K);      // slab stride: Cout rounded up to 8 rows
   if (scratch_elems < packed) return DEI2I_ERR_WORKSPACE;
-  if (c->dtype == DT_BF16 && g_use_wgrad_thin) {       // 8-channel input, 7x7 (the stem): halo-resident, windowed B operand
-    int nsplit = 0;
-    hipError_t e = wgrad_thin(g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, num_cu(), &nsplit, st);
-    if (e == hipSuccess)
-      return (int)wgrad_reduce_unpack(scratch, nsplit, (long long)packed, dw_oihw, c->Cout, c->Cin, c->CinS, c->kh * c->kw, accumulate, st);
-    if (e != hipErrorNotSupported) return (int)e;
-  }
-  if (c->dtype == DT_BF16 && g_use_wgrad_halo) {       // stride-1 3x3: (co, ci, 9 taps) block resident in registers
-    int nsplit = 0;
-    hipError_t e = wgrad_halo(g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, num_cu(), &nsplit, g_use_wgrad_halo == 2, st);
-    if (e == hipSuccess)
-      return (int)wgrad_reduce_unpack(scratch, nsplit, (long long)packed, dw_oihw, c->Cout, c->Cin, c->CinS, c->kh * c->kw, accumulate, st);
-    if (e != hipErrorNotSupported) return (int)e;
-  }
-  if (c->dtype == DT_BF16 && g_use_wgrad_v2) {
-    int nsplit = 0;
-    hipError_t e = wgrad_v2(g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, num_cu(), &nsplit, st);
-    if (e == hipSuccess)
-      return (int)wgrad_reduce_unpack(scratch, nsplit, (long long)packed, dw_oihw, c->Cout, c->Cin, c->CinS, c->kh * c->kw, accumulate, st);
-    if (e != hipErrorNotSupported) return (int)e;
-  }
+  const bool bf16 = c->dtype == DT_BF16;
   int nsplit = 0;
-  hipError_t e = wgrad_gemm(c->dtype, g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, &nsplit, st);
+  hipError_t e = hipErrorNotSupported;           // each kernel in turn until one takes the shape
+  if (bf16 && g_opt.wgrad_thin)                  // 8-channel input, 7x7 (the stem): halo-resident, windowed B operand
+    e = wgrad_thin(g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, &nsplit, st);
+  if (e == hipErrorNotSupported && bf16 && g_opt.wgrad_halo)       // stride-1 3x3: (co, ci, 9 taps) block resident in registers
+    e = wgrad_halo(g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, &nsplit, g_opt.wgrad_halo == 2, st);
+  if (e == hipErrorNotSupported && bf16 && g_opt.wgrad_v2)
+    e = wgrad_v2(g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, &nsplit, st);
+  if (e == hipErrorNotSupported) e = wgrad_gemm(c->dtype, g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, &nsplit, st);
   if (e != hipSuccess) return (int)e;
   return (int)wgrad_reduce_unpack(scratch, nsplit, (long long)packed, dw_oihw, c->Cout, c->Cin, c->CinS, c->kh * c->kw, accumulate, st);
 }
@@ -576,15 +506,9 @@ static bool to_pro(const dei2i_conv* c, const dei2i_pro* p, ConvPro& out) {
 static bool halo_fwd_shape_ok(const dei2i_conv* c, int want_pro) {
   if (!valid_conv(c) || c->dtype != DT_BF16) return false;
   if (c->kh == 4 && c->kw == 4 && c->stride == 2 && c->pad == 1 && !want_pro)          // the stride-2 form (conv_halo16.hip S2)
-    return halo16_s2_shape_ok(make_fwd_desc(to_shape(c), c->CinS), c->CoutS, num_cu());
+    return halo16_s2_shape_ok(make_fwd_desc(to_shape(c), c->CinS), c->CoutS);
   if (c->kh != 3 || c->kw != 3 || c->stride != 1 || c->pad != 1) return false;
-  const int Ho = c->H << c->up, Wo = c->W << c->up;
-  if (c->CinS % 64 != 0 || Ho % 8 != 0 || Wo % 32 != 0 || c->CoutS < 64) return false;
-  if ((long long)c->N * c->H * c->W * c->CinS >= (1ll << 31)) return false;
-  if (want_pro && (c->CinS > 512 || Ho < 4 || Wo < 4)) return false;
-  const int tiles_m = c->N * (Ho / 8) * (Wo / 32);
-  const int tn = c->CoutS >= 128 ? (c->CoutS + 127) / 128 : 1;
-  return tiles_m * tn >= num_cu() / 2;
+  return halo_conv_shape_ok(make_fwd_desc(to_shape(c), c->CinS), c->CoutS, want_pro != 0, want_pro != 0);
 }
 
 int dei2i_conv2d_fused_supported(const dei2i_conv* c, int want_pro) { return halo_fwd_shape_ok(c, want_pro) ? 1 : 0; }
@@ -603,39 +527,30 @@ int dei2i_conv2d_fwd_fused(const dei2i_conv* c, const void* x, const void* w_pac
   ConvPro cp;
   const bool has = to_pro(c, pro, cp);
   if (!has) {
-    hipError_t e = halo16_conv(g, x, w_packed, c->Cout, bias, y, c->CoutS, act, num_cu(), (hipStream_t)s, stats);
+    hipError_t e = halo16_conv(g, x, w_packed, c->Cout, bias, y, c->CoutS, act, (hipStream_t)s, stats);
     if (e != hipErrorNotSupported) return (int)e;
   }
-  return (int)halo_conv(g, x, w_packed, c->Cout, bias, y, c->CoutS, act, num_cu(), (hipStream_t)s, nullptr, has ? &cp : nullptr, stats);
+  return (int)halo_conv(g, x, w_packed, c->Cout, bias, y, c->CoutS, act, (hipStream_t)s, nullptr, has ? &cp : nullptr, stats);
 }
 
 /* conv of the upsampled z of a SPADE block, z kept at the SOURCE resolution + the logical frame's ring tensor: the 16 x 32
  * tile kernel only (no fallback: ask first) */
 int dei2i_conv2d_ring_supported(const dei2i_conv* c) {
   if (!halo_fwd_shape_ok(c, 0) || !c->up) return 0;
-  const int Ho = c->H << c->up, Wo = c->W << c->up;
-  if (Ho % 16 != 0 || Wo % 32 != 0 || c->CinS % 32 != 0) return 0;
-  const int tiles_m = c->N * (Ho / 16) * (Wo / 32);
-  const int tn = c->CoutS >= 128 ? (c->CoutS + 127) / 128 : 1;
-  return tiles_m * tn >= (num_cu() * 7) / 8 ? 1 : 0;
+  return halo16_shape_ok(make_fwd_desc(to_shape(c), c->CinS), c->CoutS, false, false, true) ? 1 : 0;
 }
 
 int dei2i_conv2d_fwd_ring(const dei2i_conv* c, const void* z_src, const void* ring, const void* w_packed, const float* bias, int act,
                           void* y, float* stats, dei2i_stream s) {
   if (!z_src || !ring || !w_packed || !y || !dei2i_conv2d_ring_supported(c)) return DEI2I_ERR_BAD_ARG;
   GatherDesc g = make_fwd_desc(to_shape(c), c->CinS);
-  return (int)halo16_conv(g, z_src, w_packed, c->Cout, bias, y, c->CoutS, act, num_cu(), (hipStream_t)s, stats, ring);
+  return (int)halo16_conv(g, z_src, w_packed, c->Cout, bias, y, c->CoutS, act, (hipStream_t)s, stats, ring);
 }
 
 int dei2i_conv2d_wgrad_pro_supported(const dei2i_conv* c) {
   if (!valid_conv(c) || c->dtype != DT_BF16) return 0;
   if (c->kh != 3 || c->kw != 3 || c->stride != 1 || c->pad != 1) return 0;
-  const int Ho = c->H << c->up, Wo = c->W << c->up;
-  if (Ho % 4 != 0 || Wo % 32 != 0 || Ho < 4 || Wo < 4) return 0;
-  if ((long long)c->N * c->H * c->W * c->CinS >= (1ll << 31)) return 0;
-  const int co = c->Cout;
-  if (co <= 64) return ((c->CinS % 128 == 0 && co >= 48) || (c->CinS % 64 == 0 && co <= 32)) ? 1 : 0;
-  return (c->CinS % 64 == 0 && co >= 96) ? 1 : 0;
+  return wgrad_halo_shape_ok(make_fwd_desc(to_shape(c), c->CinS), c->Cout, true) != 0 ? 1 : 0;
 }
 
 int dei2i_conv2d_wgrad_oihw_pro(const dei2i_conv* c, const void* x, const void* dy, float* scratch, size_t scratch_elems,
@@ -649,7 +564,7 @@ int dei2i_conv2d_wgrad_oihw_pro(const dei2i_conv* c, const void* x, const void* 
   ConvPro cp;
   to_pro(c, pro, cp);
   int nsplit = 0;
-  hipError_t e = wgrad_halo(g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, num_cu(), &nsplit, true, st, &cp);
+  hipError_t e = wgrad_halo(g, x, dy, c->Cout, c->CoutS, scratch, scratch_elems, &nsplit, true, st, &cp);
   if (e != hipSuccess) return (int)e;
   return (int)wgrad_reduce_unpack(scratch, nsplit, (long long)packed, dw_oihw, c->Cout, c->Cin, c->CinS, c->kh * c->kw, accumulate, st);
 }
@@ -662,12 +577,11 @@ int dei2i_fold_pad(int dtype, int N, int H, int W, int C, int pad, int pad_mode,
   const size_t total = (size_t)N * H * W * (C / vec);
   const unsigned grid = grid_for(total, 256, 256u * 16u);
   const int reflect = (pad_mode == PAD_REFLECT && pad > 0) ? 1 : 0;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(fold_pad_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dx_ext,
-                       (const bf16_t*)addend, (bf16_t*)dx, N, H, W, C, pad, reflect, up);
-  else
-    hipLaunchKernelGGL(fold_pad_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const float*)dx_ext,
-                       (const float*)addend, (float*)dx, N, H, W, C, pad, reflect, up);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(fold_pad_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)dx_ext, (const T*)addend, (T*)dx, N, H,
+                       W, C, pad, reflect, up);
+  });
   return (int)hipGetLastError();
 }
 

@@ -541,14 +541,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const GatherDesc g, const T*
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static int g_num_cu = 256;
-static int g_use_v2 = 1;
-void set_use_v2(int on) { g_use_v2 = on; }
-static int g_use_halo = 1;
-void set_use_halo(int on) { g_use_halo = on; }
-static int g_use_thin = 1;
-void set_use_thin(int on) { g_use_thin = on; }
-
 template <typename T, int BM, int BN, int WM, int WN>
 static hipError_t launch_gg(const DescPack& pack, const void* src, const void* wgt, int wrows, const float* bias,
                             void* out, float* ws, int ldc, int act, int splits, int slab_rows, int* zs_out, hipStream_t st) {
@@ -559,7 +551,7 @@ static hipError_t launch_gg(const DescPack& pack, const void* src, const void* w
     const GatherDesc& g = pack.d[i];
     tiles_m = std::max(tiles_m, (g.M + BM - 1) / BM);
     Kmax = std::max(Kmax, g.K);
-    flops += 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows;
+    flops += conv_flops(g, wrows);
   }
   if (pack.skip_dead_taps) flops = 0.0;      // reflect-ring launches skip most taps: left out of the executed-FLOP count
   const int tiles_n = (ldc + BN - 1) / BN;
@@ -568,20 +560,10 @@ static hipError_t launch_gg(const DescPack& pack, const void* src, const void* w
   const int zs = (nk + kps - 1) / kps;
   dim3 grid(tiles_m * tiles_n, pack.n, zs);
   const size_t lds = std::max<size_t>(2 * (BM + BN) * 128, (size_t)BM * (BN + 4) * sizeof(float));   // tiles | epilogue stage
-  auto kern = gather_gemm_kernel<T, BM, BN, WM, WN>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  count_launch(K_GATHER_V1);
-  prof_begin(PROF_GATHER_GEMM, flops, st);
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, pack, (const T*)src, (const T*)wgt, wrows, bias, (T*)out,
-                     zs > 1 ? ws : (float*)nullptr, ldc, act, tiles_n, kps, slab_rows);
-  prof_end(PROF_GATHER_GEMM, st);
   *zs_out = zs;
-  return hipGetLastError();
+  return launch_counted(K_GATHER_V1, PROF_GATHER_GEMM, flops, gather_gemm_kernel<T, BM, BN, WM, WN>, grid, dim3(256), lds, st, pack,
+                        (const T*)src, (const T*)wgt, wrows, bias, (T*)out, zs > 1 ? ws : (float*)nullptr, ldc, act, tiles_n, kps,
+                        slab_rows);
 }
 
 template <typename T>
@@ -610,8 +592,8 @@ static hipError_t gather_gemm_t(const DescPack& pack, const void* src, const voi
   const int slab_rows = pack.m_base[pack.n - 1] + pack.d[pack.n - 1].M;
   const size_t slab_elems = (size_t)slab_rows * ldc;
   int splits = 1;
-  if (tiles < g_num_cu && nk >= 4 && ws != nullptr && ws_bytes >= 2 * slab_elems * sizeof(float)) {
-    splits = (2 * g_num_cu + tiles - 1) / tiles;
+  if (tiles < num_cu() && nk >= 4 && ws != nullptr && ws_bytes >= 2 * slab_elems * sizeof(float)) {
+    splits = (2 * num_cu() + tiles - 1) / tiles;
     if (splits > nk / 2) splits = nk / 2;
     const size_t fit = ws_bytes / (slab_elems * sizeof(float));
     if ((size_t)splits > fit) splits = (int)fit;
@@ -659,21 +641,21 @@ hipError_t gather_gemm_multi(int dtype, const GatherDesc* descs, const long long
   if (pack.n == 0) return hipSuccess;
   for (int i = pack.n; i < 4; ++i) { pack.d[i] = pack.d[0]; pack.woff[i] = 0; pack.fd_taps[i] = pack.fd_taps[0]; pack.m_base[i] = 0; }
   if (dtype == DT_BF16) {
-    if (g_use_thin && pack.n == 1) {      // 8-channel inputs (stem, D's first conv, heads dgrad): thin_conv.hip
-      hipError_t e = thin_cin_conv(pack.d[0], src, (const bf16_t*)wgt + pack.woff[0], wrows, bias, out, ldc, act, g_num_cu, st);
+    if (g_opt.thin_conv && pack.n == 1) {      // 8-channel inputs (stem, D's first conv, heads dgrad): thin_conv.hip
+      hipError_t e = thin_cin_conv(pack.d[0], src, (const bf16_t*)wgt + pack.woff[0], wrows, bias, out, ldc, act, st);
       if (e != hipErrorNotSupported) return e;
-      e = thin_cout_conv(pack.d[0], src, (const bf16_t*)wgt + pack.woff[0], wrows, bias, out, ldc, act, g_num_cu, st);
+      e = thin_cout_conv(pack.d[0], src, (const bf16_t*)wgt + pack.woff[0], wrows, bias, out, ldc, act, st);
       if (e != hipErrorNotSupported) return e;
     }
-    if (g_use_halo && pack.n == 1) {      // stride-1 3x3 layers: halo-resident kernels (conv_halo16.hip, conv_halo.hip)
-      hipError_t e = halo16_conv(pack.d[0], src, (const bf16_t*)wgt + pack.woff[0], wrows, bias, out, ldc, act, g_num_cu, st);
+    if (g_opt.halo_conv && pack.n == 1) {      // stride-1 3x3 layers: halo-resident kernels (conv_halo16.hip, conv_halo.hip)
+      hipError_t e = halo16_conv(pack.d[0], src, (const bf16_t*)wgt + pack.woff[0], wrows, bias, out, ldc, act, st);
       if (e != hipErrorNotSupported) return e;
       e = halo_conv(pack.d[0], src, (const bf16_t*)wgt + pack.woff[0],
-                               wrows, bias, out, ldc, act, g_num_cu, st);
+                               wrows, bias, out, ldc, act, st);
       if (e != hipErrorNotSupported) return e;
     }
-    if (g_use_v2) {
-      hipError_t e = gather_gemm_v2(pack, src, wgt, wrows, bias, out, ws, ws_bytes, ldc, act, g_num_cu, st);
+    if (g_opt.gather_gemm_v2) {
+      hipError_t e = gather_gemm_v2(pack, src, wgt, wrows, bias, out, ws, ws_bytes, ldc, act, st);
       if (e != hipErrorNotSupported) return e;
     }
     return gather_gemm_t<bf16_t>(pack, src, wgt, wrows, bias, out, ws, ws_bytes, ldc, act, st);
@@ -695,7 +677,7 @@ static hipError_t launch_wg(const GatherDesc& g, const void* src, const void* dy
   const int tiles_k = (g.K + BN - 1) / BN;
   const int nchunks = (g.M + BR - 1) / BR;
   const int tiles = tiles_c * tiles_k;
-  int splits = (2 * g_num_cu + tiles - 1) / tiles;     // every split costs a slab write + read
+  int splits = (2 * num_cu() + tiles - 1) / tiles;     // every split costs a slab write + read
   if (splits > nchunks / 2) splits = nchunks / 2;
   const long long slab_elems = wgrad_slab_elems(co_rows, g.K);
   if ((size_t)slab_elems * (size_t)splits > capacity_elems) splits = (int)(capacity_elems / (size_t)slab_elems);
@@ -703,20 +685,9 @@ static hipError_t launch_wg(const GatherDesc& g, const void* src, const void* dy
   const int cps = (nchunks + splits - 1) / splits;
   const int zs = (nchunks + cps - 1) / cps;
   const size_t lds = 2 * (size_t)BR * (BM + BN) * sizeof(T);
-  auto kern = wgrad_kernel<T, BM, BN>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
   *nsplit_out = zs;
-  count_launch(K_WGRAD_V1);
-  prof_begin(PROF_WGRAD, 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)co_rows, st);
-  hipLaunchKernelGGL(kern, dim3(tiles, 1, zs), dim3(256), lds, st, g, (const T*)src, (const T*)dy, co_rows, ldy, dw,
-                     tiles_k, cps, slab_elems);
-  prof_end(PROF_WGRAD, st);
-  return hipGetLastError();
+  return launch_counted(K_WGRAD_V1, PROF_WGRAD, conv_flops(g, co_rows), wgrad_kernel<T, BM, BN>, dim3(tiles, 1, zs), dim3(256), lds, st,
+                        g, (const T*)src, (const T*)dy, co_rows, ldy, dw, tiles_k, cps, slab_elems);
 }
 
 hipError_t wgrad_gemm(int dtype, const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* dw,
@@ -732,7 +703,5 @@ hipError_t wgrad_gemm(int dtype, const GatherDesc& g, const void* src, const voi
   if (co_rows > 64) return launch_wg<float, 128, 128>(g, src, dy, co_rows, ldy, dw, capacity_elems, nsplit_out, st);
   return launch_wg<float, 64, 128>(g, src, dy, co_rows, ldy, dw, capacity_elems, nsplit_out, st);
 }
-
-void set_num_cu(int n) { g_num_cu = n > 0 ? n : 256; }
 
 }  // namespace dei2i

@@ -260,31 +260,22 @@ static hipError_t launch_v2(const DescPack& pack, const void* src, const void* w
     const GatherDesc& g = pack.d[i];
     tiles_m = std::max(tiles_m, (g.M + BM - 1) / BM);
     Kmax = std::max(Kmax, g.K);
-    flops += 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows;
+    flops += conv_flops(g, wrows);
   }
   const int tiles_n = (ldc + BN - 1) / BN;
   const int nk = Kmax >> 6;
   const int kps = (nk + splits - 1) / splits;
   const int zs = (nk + kps - 1) / kps;
   const size_t lds = STAGES * (size_t)(BM + BN) * 128 + 16 * BM * sizeof(int);
-  auto kern = gather_gemm_v2_kernel<BM, BN, WM, WN, STAGES>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  count_launch(K_GATHER_V2);
-  prof_begin(PROF_GATHER_GEMM, flops, st);
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, pack.n, zs), dim3(512), lds, st, pack, (const bf16_t*)src,
-                     (const bf16_t*)wgt, wrows, bias, (bf16_t*)out, zs > 1 ? ws : (float*)nullptr, ldc, act, tiles_n, kps);
-  prof_end(PROF_GATHER_GEMM, st);
-  return hipGetLastError();
+  return launch_counted(K_GATHER_V2, PROF_GATHER_GEMM, flops, gather_gemm_v2_kernel<BM, BN, WM, WN, STAGES>,
+                        dim3(tiles_m * tiles_n, pack.n, zs), dim3(512), lds, st, pack, (const bf16_t*)src, (const bf16_t*)wgt, wrows,
+                        bias, (bf16_t*)out, zs > 1 ? ws : (float*)nullptr, ldc, act, tiles_n, kps);
 }
 
 // returns hipErrorNotSupported when the shape does not qualify (caller falls through to the v1 kernel)
 hipError_t gather_gemm_v2(const DescPack& pack, const void* src, const void* wgt, int wrows, const float* bias, void* out,
-                          float* ws, size_t ws_bytes, int ldc, int act, int num_cu, hipStream_t st) {
+                          float* ws, size_t ws_bytes, int ldc, int act, hipStream_t st) {
+  const int num_cu = g_opt.num_cu;
   int tiles256 = 0, tiles192 = 0, nk = 0;
   for (int i = 0; i < pack.n; ++i) {
     const GatherDesc& g = pack.d[i];

@@ -458,36 +458,32 @@ static hipError_t launch_halo(const GatherDesc& g, const void* src, const void* 
             : pro != nullptr     ? halo_conv_kernel<BN, false, true>           // operand-path normalisation
                                  : halo_conv_kernel<BN, false, false>;
   const ConvPro pv = pro != nullptr ? *pro : ConvPro{nullptr, nullptr, 0, 0.f, nullptr, 0};
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
   // (fp8: g describes byte pairs, so Clog is half the channel count)
-  count_launch(dequant != nullptr ? K_HALO_CONV_FP8 : K_HALO_CONV);
-  prof_begin(PROF_HALO_CONV, (dequant != nullptr ? 4.0 : 2.0) * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows, st);
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias,
-                     (bf16_t*)out, ldc, act, tiles_n, dequant, pv, stats);
-  prof_end(PROF_HALO_CONV, st);
-  return hipGetLastError();
+  return launch_counted(dequant != nullptr ? K_HALO_CONV_FP8 : K_HALO_CONV, PROF_HALO_CONV,
+                        (dequant != nullptr ? 2.0 : 1.0) * conv_flops(g, wrows), kern, dim3(tiles_m * tiles_n), dim3(512), lds, st, g,
+                        (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias, (bf16_t*)out, ldc, act, tiles_n, dequant, pv, stats);
+}
+
+// the shape gate of the 8 x 32 tile kernel (pro: operand-path normalisation; pro_ring: with a ring tensor)
+bool halo_conv_shape_ok(const GatherDesc& g, int ldc, bool pro, bool pro_ring) {
+  if (g.sh != 1 || g.sw != 1 || (g.ys != 1 && g.ys != -1) || (g.xs != 1 && g.xs != -1)) return false;
+  if (g.th != 3 || g.tw != 3 || g.wK != g.K || g.wtw != g.tw) return false;       // tap count >= ring depth + 1 (halo issue at tap 1)
+  if (g.Cs % 64 != 0 || g.Ho % HALO_TH != 0 || g.Wo % HALO_TW != 0 || g.M != g.N * g.Ho * g.Wo) return false;
+  if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return false;   // 32-bit offset table
+  if (ldc < 64 || ldc % 8 != 0) return false;
+  if (pro && (g.Cs > 512 || (pro_ring && (g.Hl < 4 || g.Wl < 4)))) return false;
+  const int tiles_m = g.N * (g.Ho / HALO_TH) * (g.Wo / HALO_TW);
+  const int tn = ldc >= 128 ? (ldc + 127) / 128 : 1;
+  return tiles_m * tn >= num_cu() / 2;                                    // small grids: split-K v1 fills the chip better
 }
 
 // returns hipErrorNotSupported when the shape does not qualify (the caller falls through to the gather GEMMs)
 // dequant != nullptr selects the fp8 variant (g describes the e4m3 operands as byte pairs: see the kernel)
 // pro / stats: see the kernel (operand-path normalisation of the input, statistics of the output from the epilogue)
 hipError_t halo_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                     int act, int num_cu, hipStream_t st, const float* dequant, const ConvPro* pro, float* stats) {
-  if (g.sh != 1 || g.sw != 1 || (g.ys != 1 && g.ys != -1) || (g.xs != 1 && g.xs != -1)) return hipErrorNotSupported;
-  if (g.th != 3 || g.tw != 3 || g.wK != g.K || g.wtw != g.tw) return hipErrorNotSupported;       // tap count >= ring depth + 1 (halo issue at tap 1)
-  if (g.Cs % 64 != 0 || g.Ho % HALO_TH != 0 || g.Wo % HALO_TW != 0 || g.M != g.N * g.Ho * g.Wo) return hipErrorNotSupported;
-  if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return hipErrorNotSupported;   // 32-bit offset table
-  if (ldc < 64 || ldc % 8 != 0) return hipErrorNotSupported;
-  const int tiles_m = g.N * (g.Ho / HALO_TH) * (g.Wo / HALO_TW);
-  if (pro != nullptr && (g.Cs > 512 || (pro->ring != nullptr && (g.Hl < 4 || g.Wl < 4)))) return hipErrorNotSupported;
-  if (ldc >= 128) {
-    if (tiles_m * ((ldc + 127) / 128) < num_cu / 2) return hipErrorNotSupported;   // small grids: split-K v1 fills the chip better
-    return launch_halo<128>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st, pro, stats);
-  }
-  if (tiles_m < num_cu / 2) return hipErrorNotSupported;
+                     int act, hipStream_t st, const float* dequant, const ConvPro* pro, float* stats) {
+  if (!halo_conv_shape_ok(g, ldc, pro != nullptr, pro != nullptr && pro->ring != nullptr)) return hipErrorNotSupported;
+  if (ldc >= 128) return launch_halo<128>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st, pro, stats);
   return launch_halo<64>(g, src, wgt, wrows, bias, out, ldc, act, dequant, st, pro, stats);
 }
 

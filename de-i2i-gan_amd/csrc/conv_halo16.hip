@@ -860,35 +860,22 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
 //  built and measured in round 2: equal to or slower than the eight-wave two-phase loop (108 us on the res-block shape with the
 //  DMA pieces staggered per wave, ~equal without): one wave per SIMD has nobody to cover its stalls.  Removed)
 
-int g_halo16 = 1;              // A/B option "halo16": 0 = always the 8 x 32 tile kernel (conv_halo.hip)
-int g_halo16_fold = 1;         // A/B option "halo16_fold": 0 = ring GEMM + finalize + border fold as separate launches
-
-// one instance of the kernel; its dynamic LDS limit is raised on its first launch
+// one instance of the kernel
 template <int BN, int STAGES, bool FOLD, bool PIPE, bool EPIN, bool S2>
 static hipError_t launch_halo16_kernel(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out,
                                        int ldc, int act, hipStream_t st, float* stats, const void* ring, const EpiNorm* en) {
   constexpr size_t loop_lds = 2 * (size_t)H16_HBYTES + (size_t)STAGES * BN * 64 + 4 * H16_GROUPS * 16 * sizeof(int);   // (4 tables: S2)
   constexpr size_t epi_lds = 2 * 256 * (size_t)(BN * 2 + 16) + 4 * BN * sizeof(float) + 8 * (BN / 8) * 32 * sizeof(float);   // tile | corners | reduce scratch
   constexpr size_t lds = std::max(loop_lds, epi_lds);
-  auto kern = halo16_conv_kernel<BN, STAGES, FOLD, PIPE, EPIN, S2>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  count_launch(S2 ? K_HALO16_S2 : K_HALO16_CONV);
   // (profiling families: the pipelined forward instance is a kernel of its own -- bench.py's roofline line --, the FOLD launches
   //  are another, the 64-channel tile and the stride-2 form count with the other conv kernels)
   const ProfFamily fam = FOLD ? PROF_HALO_FOLD : (PIPE ? PROF_HALO_CONV : PROF_GATHER_GEMM);
-  prof_begin(fam, 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows, st);
   const int tiles_m = g.N * (g.Ho / H16_TH) * (g.Wo / H16_TW);
   const int tiles_n = (ldc + BN - 1) / BN;
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias,
-                     (bf16_t*)out, ldc, act, tiles_n, stats, (const bf16_t*)ring,
-                     ring != nullptr ? ring_pixels(g.Hl, g.Wl) : 0, en != nullptr ? *en : EpiNorm{});
-  prof_end(fam, st);
-  return hipGetLastError();
+  return launch_counted(S2 ? K_HALO16_S2 : K_HALO16_CONV, fam, conv_flops(g, wrows), halo16_conv_kernel<BN, STAGES, FOLD, PIPE, EPIN, S2>,
+                        dim3(tiles_m * tiles_n), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias,
+                        (bf16_t*)out, ldc, act, tiles_n, stats, (const bf16_t*)ring, ring != nullptr ? ring_pixels(g.Hl, g.Wl) : 0,
+                        en != nullptr ? *en : EpiNorm{});
 }
 
 // the 3x3 forms, all on the 8-deep weight ring: FOLD (+ EPIN) launches and the 64-channel tile run the two-phase loop, the
@@ -905,55 +892,57 @@ static hipError_t launch_halo16(const GatherDesc& g, const void* src, const void
   return launch_halo16_kernel<BN, 8, false, BN == 128, false, false>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, en);
 }
 
-// returns hipErrorNotSupported when the shape does not qualify (the caller goes on to the 8 x 32 tile kernel)
-// ring: see the kernel (SPADE -> upsample -> conv with z kept at the source resolution); only the 8-wave kernel takes it
-// fold: the launch is the interior input gradient of a reflect-padded 3x3 conv and also folds the frame's ring and corners
-// into the border rows / columns -- see the kernel
-int g_halo16_s2 = 1;           // A/B option "halo16_s2": 0 = the 4x4 stride-2 convs stay on the gather GEMM
-
 // the 4x4 stride-2 forward convs (kernel template S2): reflect or zero padding 1, 64 input channels.  Measured against the LDS-DMA
 // gather GEMM on the step's shapes, operands cold (tools/bench_s2.py): 64 -> 128 @256^2 x16 115 vs 135 us, x32 207 vs 235, D's
 // 64 -> 128 @128^2 x64 109 vs 135 -- but 128 -> 256 @128^2 x16 98 vs 86 and D's 128 -> 256 @64^2 x64 83 vs 80: per k-step this form
 // moves 8 KB of weights + 9 KB of halo (a plane's halo serves 4 taps, the 3x3 kernel's 9), and the gather GEMM's 128-channel
 // k-steps are twice as efficient as its 64-channel ones -- so only the 64-channel inputs are taken.
-bool halo16_s2_shape_ok(const GatherDesc& g, int ldc, int num_cu) {
-  if (!g_halo16_s2 || !g_halo16) return false;
+bool halo16_s2_shape_ok(const GatherDesc& g, int ldc) {
+  if (!g_opt.halo16_s2 || !g_opt.halo16) return false;
   if (g.sh != 2 || g.sw != 2 || g.th != 4 || g.tw != 4 || g.ys != 1 || g.xs != 1 || g.by0 != -1 || g.bx0 != -1 || g.up || g.wK != g.K || g.wtw != 4) return false;
-  if (g.Cs != 64 && g_halo16_s2 != 2) return false;                                        // (option value 2: every channel count, for A/B)
+  if (g.Cs != 64 && g_opt.halo16_s2 != 2) return false;                                        // (option value 2: every channel count, for A/B)
   if (g.Cs % 32 != 0 || g.Cs < 64 || g.Ho % H16_TH != 0 || g.Wo % H16_TW != 0 || g.M != g.N * g.Ho * g.Wo || !g.out_identity) return false;
   if (g.Hl != 2 * g.Ho || g.Wl != 2 * g.Wo) return false;
   if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return false;                   // 32-bit offset table
   if (ldc < 128 || ldc % 8 != 0) return false;                                             // (the 128-channel tile)
   const int tiles_m = g.N * (g.Ho / H16_TH) * (g.Wo / H16_TW);
-  return tiles_m * ((ldc + 127) / 128) >= (num_cu * 7) / 8;
+  return tiles_m * ((ldc + 127) / 128) >= (num_cu() * 7) / 8;
 }
 
 static hipError_t halo16_conv_s2(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out,
-                                 int ldc, int act, int num_cu, hipStream_t st, float* stats) {
-  if (!halo16_s2_shape_ok(g, ldc, num_cu)) return hipErrorNotSupported;
+                                 int ldc, int act, hipStream_t st, float* stats) {
+  if (!halo16_s2_shape_ok(g, ldc)) return hipErrorNotSupported;
   // the 4x4 stride-2 form: two-phase loop, 4-stage weight ring
   return launch_halo16_kernel<128, 4, false, false, false, true>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, nullptr, nullptr);
 }
 
-hipError_t halo16_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                       int act, int num_cu, hipStream_t st, float* stats, const void* ring, bool fold, const EpiNorm* en) {
-  if (g.sh == 2 && g.sw == 2 && !fold && en == nullptr && ring == nullptr)
-    return halo16_conv_s2(g, src, wgt, wrows, bias, out, ldc, act, num_cu, st, stats);
-  if (en != nullptr && (!fold || (en->kind != 1 && en->kind != 2))) return hipErrorNotSupported;
-  if (fold && (!g_halo16_fold || g.ys >= 0 || g.xs >= 0 || g.pad_mode != PAD_ZERO || g.up || g.Ho < 2 * H16_TH || g.Wo < 2 * H16_TW ||
-               bias != nullptr || act != ACT_NONE || stats != nullptr || ring != nullptr))
-    return hipErrorNotSupported;
-  if (!g_halo16) return hipErrorNotSupported;
-  if (g.sh != 1 || g.sw != 1 || (g.ys != 1 && g.ys != -1) || (g.xs != 1 && g.xs != -1)) return hipErrorNotSupported;
-  if (g.th != 3 || g.tw != 3 || g.wK != g.K || g.wtw != g.tw) return hipErrorNotSupported;
-  if (g.Cs % 32 != 0 || g.Ho % H16_TH != 0 || g.Wo % H16_TW != 0 || g.M != g.N * g.Ho * g.Wo) return hipErrorNotSupported;
-  if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return hipErrorNotSupported;   // 32-bit offset table
-  if (ldc < 64 || ldc % 8 != 0) return hipErrorNotSupported;
+// the shape gate of the 3x3 forms (the options "halo16" / "halo16_fold" are the launcher's business)
+// ring: see the kernel (SPADE -> upsample -> conv with z kept at the source resolution); only the 8-wave kernel takes it
+// fold: the launch is the interior input gradient of a reflect-padded 3x3 conv and also folds the frame's ring and corners
+// into the border rows / columns -- see the kernel; epin: with the norm layer's backward reductions in the epilogue
+bool halo16_shape_ok(const GatherDesc& g, int ldc, bool fold, bool epin, bool ring) {
+  if (epin && !fold) return false;
+  if (fold && (g.ys >= 0 || g.xs >= 0 || g.pad_mode != PAD_ZERO || g.up || g.Ho < 2 * H16_TH || g.Wo < 2 * H16_TW || ring)) return false;
+  if (g.sh != 1 || g.sw != 1 || (g.ys != 1 && g.ys != -1) || (g.xs != 1 && g.xs != -1)) return false;
+  if (g.th != 3 || g.tw != 3 || g.wK != g.K || g.wtw != g.tw) return false;
+  if (g.Cs % 32 != 0 || g.Ho % H16_TH != 0 || g.Wo % H16_TW != 0 || g.M != g.N * g.Ho * g.Wo) return false;
+  if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return false;   // 32-bit offset table
+  if (ldc < 64 || ldc % 8 != 0) return false;
   const int tiles_m = g.N * (g.Ho / H16_TH) * (g.Wo / H16_TW);
   const int tn = ldc >= 128 ? (ldc + 127) / 128 : 1;
   // the double-size tile needs a grid that still covers the chip: at least ~7/8 of a round (fewer: the 8 x 32 tiles spread better)
-  if (tiles_m * tn < (num_cu * 7) / 8) return hipErrorNotSupported;
-  if (ring != nullptr && (g.Hl < 4 || g.Wl < 4)) return hipErrorNotSupported;
+  if (tiles_m * tn < (num_cu() * 7) / 8) return false;
+  return !ring || (g.Hl >= 4 && g.Wl >= 4);
+}
+
+// returns hipErrorNotSupported when the shape does not qualify (the caller goes on to the 8 x 32 tile kernel)
+hipError_t halo16_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
+                       int act, hipStream_t st, float* stats, const void* ring, bool fold, const EpiNorm* en) {
+  if (g.sh == 2 && g.sw == 2 && !fold && en == nullptr && ring == nullptr)
+    return halo16_conv_s2(g, src, wgt, wrows, bias, out, ldc, act, st, stats);
+  if (en != nullptr && en->kind != 1 && en->kind != 2) return hipErrorNotSupported;
+  if (fold && (!g_opt.halo16_fold || bias != nullptr || act != ACT_NONE || stats != nullptr)) return hipErrorNotSupported;
+  if (!g_opt.halo16 || !halo16_shape_ok(g, ldc, fold, en != nullptr, ring != nullptr)) return hipErrorNotSupported;
   if (ldc >= 128) return launch_halo16<128>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, fold, en);
   return launch_halo16<64>(g, src, wgt, wrows, bias, out, ldc, act, st, stats, ring, fold, en);
 }

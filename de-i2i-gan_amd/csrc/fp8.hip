@@ -83,18 +83,14 @@ int dei2i_pack_weight_fwd_fp8(const dei2i_conv* c, const float* w_oihw, const fl
 int dei2i_conv2d_fp8_supported(const dei2i_conv* c) {
   GatherDesc g;
   if (!fp8_desc(c, g)) return 0;
-  if (g.Ho % 8 != 0 || g.Wo % 32 != 0 || c->CoutS < 64) return 0;
-  if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return 0;
-  const int tiles_m = g.N * (g.Ho / 8) * (g.Wo / 32);
-  const int tiles = c->CoutS >= 128 ? tiles_m * ((c->CoutS + 127) / 128) : tiles_m;
-  return tiles >= num_cu() / 2 ? 1 : 0;
+  return halo_conv_shape_ok(g, c->CoutS, false, false) ? 1 : 0;
 }
 
 int dei2i_conv2d_fwd_fp8(const dei2i_conv* c, const void* x_e4m3, const void* w_e4m3, const float* bias, const float* dequant,
                          int act, void* y_bf16, dei2i_stream s) {
   GatherDesc g;
   if (!fp8_desc(c, g) || !x_e4m3 || !w_e4m3 || !dequant || !y_bf16) return DEI2I_ERR_BAD_ARG;
-  const hipError_t e = halo_conv(g, x_e4m3, w_e4m3, c->Cout, bias, y_bf16, c->CoutS, act, num_cu(), (hipStream_t)s, dequant);
+  const hipError_t e = halo_conv(g, x_e4m3, w_e4m3, c->Cout, bias, y_bf16, c->CoutS, act, (hipStream_t)s, dequant);
   if (e == hipErrorNotSupported) return DEI2I_ERR_BAD_ARG;      // no fallback: the caller checks dei2i_conv2d_fp8_supported
   return (int)e;
 }

@@ -187,6 +187,68 @@ inline GatherDesc sub_taps_desc(const GatherDesc& g, int ty0, int nty, int tx0, 
   return r;
 }
 
+// The dgrad parity classes of a conv in packed-weight order: f(DgradClass) for every (ay, ax), also those without taps
+// (count 0); returns the element count of the whole packed dgrad weight.
+struct DgradClass {
+  int ay, ax, th, tw;
+  long long off, count;   // class weights [Cin][th*tw][CoutS]: first element and element count in the packed buffer
+};
+template <typename F>
+inline long long for_each_dgrad_class(int Cin, int CoutS, int kh, int kw, int stride, F&& f) {
+  long long off = 0;
+  for (int ay = 0; ay < stride; ++ay)
+    for (int ax = 0; ax < stride; ++ax) {
+      const int th = dgrad_taps(kh, stride, ay), tw = dgrad_taps(kw, stride, ax);
+      const long long count = (long long)Cin * th * tw * CoutS;
+      f(DgradClass{ay, ax, th, tw, off, count});
+      off += count;
+    }
+  return off;
+}
+
+// Reflect ring of a stride-1 dgrad frame ((H + 2p) x (W + 2p), `frame` = its reflect descriptor): top rows, bottom rows,
+// left columns, right columns.
+inline void reflect_ring_descs(const GatherDesc& frame, int H, int W, int p, int kh, int kw, GatherDesc ring[4]) {
+  const int OW = W + 2 * p;
+  ring[0] = sub_rect_desc(frame, 0, p, 0, OW);
+  ring[1] = sub_rect_desc(frame, H + p, p, 0, OW);
+  ring[2] = sub_rect_desc(frame, p, H, 0, p);
+  ring[3] = sub_rect_desc(frame, p, H, W + p, p);
+  if (kh == 2 * p + 1 && kw == 2 * p + 1) {
+    // "same" convs: the top p frame rows only see tap rows 0..p-1 (the others read above dY), the bottom rows only
+    // tap rows kh-p..kh-1, likewise the side columns -- run each rectangle on its live taps (a third of K for 3x3)
+    ring[0] = sub_taps_desc(ring[0], 0, p, 0, kw);
+    ring[1] = sub_taps_desc(ring[1], kh - p, p, 0, kw);
+    ring[2] = sub_taps_desc(ring[2], 0, kh, 0, p);
+    ring[3] = sub_taps_desc(ring[3], 0, kh, kw - p, p);
+  }
+}
+
+// Ring of the (H + 2) x (W + 2) frame of a 4x4 stride-2 pad-1 reflect dgrad (c: the reflect shape), as one-pixel rectangles
+// of the parity classes, each with its class's packed-weight offset.
+inline void s2_ring_descs(const ConvShape& c, int CoutS, GatherDesc rows[4], long long wrows[4], GatherDesc cols[4],
+                          long long wcols[4]) {
+  GatherDesc fr[2][2];
+  long long woff[2][2];
+  for_each_dgrad_class(c.Cin, CoutS, c.kh, c.kw, 2, [&](const DgradClass& k) {
+    fr[k.ay][k.ax] = make_dgrad_desc(c, CoutS, k.ay, k.ax);
+    woff[k.ay][k.ax] = k.off;
+  });
+  // frame rows: hp = 0 is row 0 of the classes ay = 0, hp = H + 1 (odd) the last row of the classes ay = 1; all their columns
+  rows[0] = sub_rect_desc(fr[0][0], 0, 1, 0, fr[0][0].Wo);
+  rows[1] = sub_rect_desc(fr[0][1], 0, 1, 0, fr[0][1].Wo);
+  rows[2] = sub_rect_desc(fr[1][0], fr[1][0].Ho - 1, 1, 0, fr[1][0].Wo);
+  rows[3] = sub_rect_desc(fr[1][1], fr[1][1].Ho - 1, 1, 0, fr[1][1].Wo);
+  wrows[0] = woff[0][0]; wrows[1] = woff[0][1]; wrows[2] = woff[1][0]; wrows[3] = woff[1][1];
+  // frame columns without the corners (they are in the rows): wp = 0 is column 0 of the classes ax = 0 (class ay = 0 without its
+  // row 0, class ay = 1 without its last row), wp = W + 1 the last column of the classes ax = 1
+  cols[0] = sub_rect_desc(fr[0][0], 1, fr[0][0].Ho - 1, 0, 1);
+  cols[1] = sub_rect_desc(fr[1][0], 0, fr[1][0].Ho - 1, 0, 1);
+  cols[2] = sub_rect_desc(fr[0][1], 1, fr[0][1].Ho - 1, fr[0][1].Wo - 1, 1);
+  cols[3] = sub_rect_desc(fr[1][1], 0, fr[1][1].Ho - 1, fr[1][1].Wo - 1, 1);
+  wcols[0] = woff[0][0]; wcols[1] = woff[1][0]; wcols[2] = woff[0][1]; wcols[3] = woff[1][1];
+}
+
 // ---------------------------------------------------------------------------------------------
 // The 2-pixel frame ("ring") of an H x W image: the pixels whose SPADE gamma/beta class is not the interior one when
 // the label map is constant (normalization.py:24-37: two zero-padded 3x3 convs reach 2 pixels in).  The fused

@@ -18,6 +18,46 @@ void count_launch(int kid);
 void prof_begin(int family, double flops, hipStream_t st);
 void prof_end(int family, hipStream_t st);
 
+// The A-B switches of dei2i_set_option (names, values and defaults: include/dei2i_hip.h) and the device's CU count
+// (dei2i_init; 256 until then): the library's one copy.
+struct Options {
+  int gather_gemm_v2 = 1;
+  int wgrad_v2 = 1;
+  int halo_conv = 1;
+  int thin_conv = 1;
+  int halo16 = 1;           // 0 = always the 8 x 32 tile kernel (conv_halo.hip)
+  int halo16_fold = 1;      // 0 = ring GEMM + finalize + border fold as separate launches
+  int halo16_s2 = 1;        // 0 = the 4x4 stride-2 convs stay on the gather GEMM
+  int wgrad_halo = 1;
+  int wgrad_thin = 1;
+  int dgrad_s2_ring = 1;    // stride-2 reflect dgrads decomposed (interior into dx + ring rectangles)
+  int num_cu = 256;
+};
+extern Options g_opt;
+inline int num_cu() { return g_opt.num_cu; }
+
+inline double conv_flops(const GatherDesc& g, int rows) {
+  return 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)rows;
+}
+
+// Raises the kernel's dynamic-LDS limit to at least `bytes` (runtime.hip remembers, per kernel address, the largest value set:
+// a size already covered costs no runtime call).
+hipError_t ensure_dyn_lds(const void* kernel, size_t bytes);
+
+// The launch protocol of the counted kernels, written once: LDS limit, launch counter, profiling bracket, launch, error.
+// A failed attribute call returns before anything is counted or profiled.
+template <typename... KArgs, typename... Args>
+static inline hipError_t launch_counted(int kid, int family, double flops, void (*kern)(KArgs...), dim3 grid, dim3 block,
+                                        size_t lds, hipStream_t st, Args&&... args) {
+  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds);
+  if (e != hipSuccess) return e;
+  count_launch(kid);
+  prof_begin(family, flops, st);
+  hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+  prof_end(family, st);
+  return hipGetLastError();
+}
+
 struct DescPack {
   GatherDesc d[4];
   long long woff[4];      // element offset of each class's packed weights
@@ -28,26 +68,25 @@ struct DescPack {
   int m_base[4];
 };
 
-void set_num_cu(int n);
-void set_use_v2(int on);
+// Every launcher below returns hipErrorNotSupported when the shape does not qualify; each *_shape_ok is the whole shape gate of
+// its kernel, called by the launcher and by the C ABI's *_supported predicates.
 hipError_t gather_gemm_v2(const DescPack& pack, const void* src, const void* wgt, int wrows, const float* bias, void* out,
-                          float* ws, size_t ws_bytes, int ldc, int act, int num_cu, hipStream_t st);
-int num_cu();
-void set_use_halo(int on);
-void set_use_thin(int on);
+                          float* ws, size_t ws_bytes, int ldc, int act, hipStream_t st);
 hipError_t thin_cout_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                          int act, int num_cu, hipStream_t st);
+                          int act, hipStream_t st);
 hipError_t thin_cin_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                         int act, int num_cu, hipStream_t st);
+                         int act, hipStream_t st);
+bool halo_conv_shape_ok(const GatherDesc& g, int ldc, bool pro, bool pro_ring);
 hipError_t halo_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                     int act, int num_cu, hipStream_t st, const float* dequant = nullptr, const ConvPro* pro = nullptr,
+                     int act, hipStream_t st, const float* dequant = nullptr, const ConvPro* pro = nullptr,
                      float* stats = nullptr);
 
 // 16 x 32 pixel tiles, 32-channel slices (conv_halo16.hip): the large-grid 3x3 stride-1 layers
 hipError_t halo16_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                       int act, int num_cu, hipStream_t st, float* stats = nullptr, const void* ring = nullptr, bool fold = false,
+                       int act, hipStream_t st, float* stats = nullptr, const void* ring = nullptr, bool fold = false,
                        const EpiNorm* en = nullptr);
-bool halo16_s2_shape_ok(const GatherDesc& g, int ldc, int num_cu);     // the 4x4 stride-2 form of the 16 x 32 tile kernel takes this conv
+bool halo16_shape_ok(const GatherDesc& g, int ldc, bool fold, bool epin, bool ring);     // the 3x3 forms (options apart)
+bool halo16_s2_shape_ok(const GatherDesc& g, int ldc);     // the 4x4 stride-2 form of the 16 x 32 tile kernel takes this conv
 hipError_t gather_gemm(int dtype, const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias,
                        void* out, float* ws, size_t ws_bytes, int ldc, int act, hipStream_t st);
 hipError_t gather_gemm_multi(int dtype, const GatherDesc* descs, const long long* woffs, int n, const void* src,
@@ -62,12 +101,14 @@ hipError_t wgrad_gemm(int dtype, const GatherDesc& g, const void* src, const voi
                       size_t capacity_elems, int* nsplit_out, hipStream_t st);
 
 hipError_t wgrad_v2(const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* slabs,
-                    size_t slab_capacity_elems, int num_cu, int* nsplit_out, hipStream_t st);
+                    size_t slab_capacity_elems, int* nsplit_out, hipStream_t st);
+// 0: not taken; else the tile it takes -- 1: 64 co x 128 ci, 2: 64 co x 64 ci with the taps over two wave groups, 3: 128 co x 64 ci
+int wgrad_halo_shape_ok(const GatherDesc& g, int co_rows, bool pro_ring);
 hipError_t wgrad_halo(const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* slabs,
-                      size_t slab_capacity_elems, int num_cu, int* nsplit_out, bool force, hipStream_t st,
+                      size_t slab_capacity_elems, int* nsplit_out, bool force, hipStream_t st,
                       const ConvPro* pro = nullptr);
 hipError_t wgrad_thin(const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* slabs,
-                      size_t slab_capacity_elems, int num_cu, int* nsplit_out, hipStream_t st);
+                      size_t slab_capacity_elems, int* nsplit_out, hipStream_t st);
 hipError_t wgrad_reduce_unpack(float* slabs, int nsplit, long long slab_elems, float* dw, int Cout, int Cin, int CinS,
                                int taps, int accumulate, hipStream_t st);
 

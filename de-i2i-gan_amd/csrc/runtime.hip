@@ -1,7 +1,7 @@
 // Library bookkeeping: device query, error strings, in-library HIP-event timing of one kernel family.
 #include <hip/hip_runtime.h>
 #include <mutex>
-#include <string>
+#include <string.h>
 #include <vector>
 
 #include "../../include/dei2i_hip.h"
@@ -9,14 +9,26 @@
 
 namespace dei2i {
 
-extern int g_use_wgrad_v2;
-extern int g_use_wgrad_halo;
-extern int g_use_wgrad_thin;
-extern int g_dgrad_s2_ring;
-extern int g_halo16, g_halo16_fold, g_halo16_s2;
-static int g_cus = 256;
-void set_num_cu_rt(int n) { g_cus = n > 0 ? n : 256; }
-int num_cu() { return g_cus; }
+Options g_opt;
+
+// Dynamic-LDS limits raised so far, keyed by kernel address.  Launches come from the forward thread and from autograd's
+// backward thread, hence the lock; a full table only means that further kernels ask the runtime on every launch.
+struct LdsLimit { const void* kernel; size_t bytes; };
+static LdsLimit g_lds_limits[64];
+static int g_lds_kernels = 0;
+static std::mutex g_lds_mutex;
+
+hipError_t ensure_dyn_lds(const void* kernel, size_t bytes) {
+  std::lock_guard<std::mutex> lock(g_lds_mutex);
+  int i = 0;
+  while (i < g_lds_kernels && g_lds_limits[i].kernel != kernel) ++i;
+  if (i < g_lds_kernels && bytes <= g_lds_limits[i].bytes) return hipSuccess;
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) return e;
+  if (i == g_lds_kernels && g_lds_kernels < 64) g_lds_limits[g_lds_kernels++] = LdsLimit{kernel, 0};
+  if (i < g_lds_kernels) g_lds_limits[i].bytes = bytes;
+  return hipSuccess;
+}
 
 struct ProfState {
   bool on = false;
@@ -33,8 +45,15 @@ static ProfState g_prof[PROF_FAMILIES];
 
 static long long g_launches[K_COUNT];
 void count_launch(int kid) { g_launches[kid]++; }
-static const char* const g_kernel_names[K_COUNT] = {"gather_v1", "gather_v2", "halo_conv", "halo_conv_fp8", "thin_cin", "thin_cout",
-                                                    "wgrad_v1", "wgrad_v2", "wgrad_halo", "wgrad_thin", "halo16_conv", "splitk_finalize", "halo16_s2"};
+static const char* const g_kernel_names[] = {"gather_v1", "gather_v2", "halo_conv", "halo_conv_fp8", "thin_cin", "thin_cout",
+                                             "wgrad_v1", "wgrad_v2", "wgrad_halo", "wgrad_thin", "halo16_conv", "splitk_finalize", "halo16_s2"};
+static_assert(sizeof(g_kernel_names) / sizeof(g_kernel_names[0]) == K_COUNT, "one name per KernelId, in its order");
+
+static const struct { const char* name; int Options::*member; } g_option_table[] = {
+    {"gather_gemm_v2", &Options::gather_gemm_v2}, {"wgrad_v2", &Options::wgrad_v2},     {"halo_conv", &Options::halo_conv},
+    {"thin_conv", &Options::thin_conv},           {"halo16", &Options::halo16},         {"halo16_fold", &Options::halo16_fold},
+    {"halo16_s2", &Options::halo16_s2},           {"wgrad_halo", &Options::wgrad_halo}, {"wgrad_thin", &Options::wgrad_thin},
+    {"dgrad_s2_ring", &Options::dgrad_s2_ring}};
 
 void prof_begin(int family, double flops, hipStream_t st) {
   ProfState& p = g_prof[family];
@@ -73,8 +92,7 @@ int dei2i_init(int device) {
   hipDeviceProp_t prop;
   hipError_t e = hipGetDeviceProperties(&prop, device);
   if (e != hipSuccess) return (int)e;
-  set_num_cu_rt(prop.multiProcessorCount);
-  set_num_cu(prop.multiProcessorCount);
+  g_opt.num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   return 0;
 }
 
@@ -87,16 +105,8 @@ const char* dei2i_error_string(int code) {
 
 int dei2i_set_option(const char* name, int value) {
   if (name == nullptr) return DEI2I_ERR_BAD_ARG;
-  if (std::string(name) == "gather_gemm_v2") { set_use_v2(value); return 0; }
-  if (std::string(name) == "wgrad_v2") { g_use_wgrad_v2 = value; return 0; }
-  if (std::string(name) == "halo_conv") { set_use_halo(value); return 0; }
-  if (std::string(name) == "thin_conv") { set_use_thin(value); return 0; }
-  if (std::string(name) == "halo16") { g_halo16 = value; return 0; }
-  if (std::string(name) == "halo16_fold") { g_halo16_fold = value; return 0; }
-  if (std::string(name) == "halo16_s2") { g_halo16_s2 = value; return 0; }
-  if (std::string(name) == "wgrad_halo") { g_use_wgrad_halo = value; return 0; }
-  if (std::string(name) == "wgrad_thin") { g_use_wgrad_thin = value; return 0; }
-  if (std::string(name) == "dgrad_s2_ring") { g_dgrad_s2_ring = value; return 0; }
+  for (const auto& o : g_option_table)
+    if (strcmp(name, o.name) == 0) { g_opt.*o.member = value; return 0; }
   return DEI2I_ERR_BAD_ARG;
 }
 

@@ -180,37 +180,27 @@ __global__ __launch_bounds__(512) void thin_cin_conv_kernel(const GatherDesc g, 
 
 template <int NKB>
 static hipError_t launch_thin(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                              int act, int ntiles, int num_cu, hipStream_t st) {
+                              int act, int ntiles, hipStream_t st) {
   const int hwd = (TC_TW - 1) * g.sw + g.tw, hht = (TC_TH - 1) * g.sh + g.th;
   const int halo_bytes = ((hwd * hht + 63) / 64) * 1024;
   const size_t lds = 2 * (size_t)halo_bytes + 8 * 64 * TC_SROW;
-  auto kern = thin_cin_conv_kernel<NKB>;
-  static size_t lds_set = 0;
-  if (lds > lds_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    lds_set = lds;
-  }
-  count_launch(K_THIN_CIN);
-  prof_begin(PROF_GATHER_GEMM, 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows, st);
-  hipLaunchKernelGGL(kern, dim3(std::min(ntiles, num_cu)), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias,
-                     (bf16_t*)out, ldc, act, ntiles, halo_bytes);
-  prof_end(PROF_GATHER_GEMM, st);
-  return hipGetLastError();
+  return launch_counted(K_THIN_CIN, PROF_GATHER_GEMM, conv_flops(g, wrows), thin_cin_conv_kernel<NKB>, dim3(std::min(ntiles, num_cu())),
+                        dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias, (bf16_t*)out, ldc, act, ntiles,
+                        halo_bytes);
 }
 
 // returns hipErrorNotSupported when the shape does not qualify (the caller falls through to the gather GEMMs)
 hipError_t thin_cin_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                         int act, int num_cu, hipStream_t st) {
+                         int act, hipStream_t st) {
   if (g.Cs != 8 || wrows > TC_N || ldc > TC_N || ldc % 8 != 0 || g.wK != g.K || g.wtw != g.tw) return hipErrorNotSupported;
   if ((g.ys != 1 && g.ys != -1) || (g.xs != 1 && g.xs != -1) || g.sh < 1 || g.sh > 2 || g.sw != g.sh) return hipErrorNotSupported;
   if (g.Ho % TC_TH != 0 || g.Wo % TC_TW != 0 || g.M != g.N * g.Ho * g.Wo) return hipErrorNotSupported;
   const int ntiles = g.N * (g.Ho / TC_TH) * (g.Wo / TC_TW);
-  if (ntiles < num_cu) return hipErrorNotSupported;
+  if (ntiles < num_cu()) return hipErrorNotSupported;
   const int nkb = (g.th * g.tw + 1) / 2;
-  if (nkb == 25) return launch_thin<25>(g, src, wgt, wrows, bias, out, ldc, act, ntiles, num_cu, st);     // 7x7
-  if (nkb == 8) return launch_thin<8>(g, src, wgt, wrows, bias, out, ldc, act, ntiles, num_cu, st);       // 4x4
-  if (nkb == 5) return launch_thin<5>(g, src, wgt, wrows, bias, out, ldc, act, ntiles, num_cu, st);       // 3x3
+  if (nkb == 25) return launch_thin<25>(g, src, wgt, wrows, bias, out, ldc, act, ntiles, st);     // 7x7
+  if (nkb == 8) return launch_thin<8>(g, src, wgt, wrows, bias, out, ldc, act, ntiles, st);       // 4x4
+  if (nkb == 5) return launch_thin<5>(g, src, wgt, wrows, bias, out, ldc, act, ntiles, st);       // 3x3
   return hipErrorNotSupported;
 }
 
@@ -412,13 +402,13 @@ __global__ __launch_bounds__(512) void thin_cout_conv_kernel(const GatherDesc g,
 
 // returns hipErrorNotSupported when the shape does not qualify (the caller falls through to the gather GEMMs)
 hipError_t thin_cout_conv(const GatherDesc& g, const void* src, const void* wgt, int wrows, const float* bias, void* out, int ldc,
-                          int act, int num_cu, hipStream_t st) {
+                          int act, hipStream_t st) {
   if (g.Cs != 64 || wrows > TO_MAXCO || ldc != 8 || g.wK != g.K || g.wtw != g.tw) return hipErrorNotSupported;
   if ((g.ys != 1 && g.ys != -1) || (g.xs != 1 && g.xs != -1) || g.sh != 1 || g.sw != 1) return hipErrorNotSupported;
   if (g.Ho % TC_TH != 0 || g.Wo % TC_TW != 0 || g.M != g.N * g.Ho * g.Wo) return hipErrorNotSupported;
   if ((long long)g.N * g.Hs * g.Ws * 64 >= (1ll << 31)) return hipErrorNotSupported;
   const int ntiles = g.N * (g.Ho / TC_TH) * (g.Wo / TC_TW);
-  if (ntiles < num_cu) return hipErrorNotSupported;
+  if (ntiles < num_cu()) return hipErrorNotSupported;
   const int hwd = TC_TW + g.tw - 1, hht = TC_TH + g.th - 1;
   const int halo_bytes = 2 * ((hwd * hht + 15) / 16) * 1024;          // two channel planes of 16-pixel groups
   if (2 * ((hwd * hht + 15) / 16) > 8 * TO_MAXG) return hipErrorNotSupported;
@@ -429,18 +419,8 @@ hipError_t thin_cout_conv(const GatherDesc& g, const void* src, const void* wgt,
   const size_t lds = nbuf * (size_t)halo_bytes + wbytes;
   if (lds > 160 * 1024) return hipErrorNotSupported;
   auto kern = wreg ? thin_cout_conv_kernel<true> : thin_cout_conv_kernel<false>;
-  static size_t lds_set[2] = {0, 0};
-  if (lds > lds_set[wreg ? 1 : 0]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    lds_set[wreg ? 1 : 0] = lds;
-  }
-  count_launch(K_THIN_COUT);
-  prof_begin(PROF_GATHER_GEMM, 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)wrows, st);
-  hipLaunchKernelGGL(kern, dim3(std::min(ntiles, num_cu)), dim3(512), lds, st, g, (const bf16_t*)src,
-                     (const bf16_t*)wgt, wrows, bias, (bf16_t*)out, ldc, act, ntiles, halo_bytes, nbuf);
-  prof_end(PROF_GATHER_GEMM, st);
-  return hipGetLastError();
+  return launch_counted(K_THIN_COUT, PROF_GATHER_GEMM, conv_flops(g, wrows), kern, dim3(std::min(ntiles, num_cu())), dim3(512), lds, st,
+                        g, (const bf16_t*)src, (const bf16_t*)wgt, wrows, bias, (bf16_t*)out, ldc, act, ntiles, halo_bytes, nbuf);
 }
 
 }  // namespace dei2i

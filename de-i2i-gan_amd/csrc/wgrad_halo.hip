@@ -401,8 +401,8 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
 
 template <int BCO, int BCI, int NTG>
 static hipError_t launch_wgrad_halo(const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* slabs,
-                                    size_t slab_capacity_elems, int num_cu, int* nsplit_out, bool force, hipStream_t st,
-                                    const ConvPro* pro) {
+                                    size_t slab_capacity_elems, int* nsplit_out, bool force, hipStream_t st, const ConvPro* pro) {
+  const int num_cu = g_opt.num_cu;
   const int nslices = g.Cs / BCI, tiles_c = (co_rows + BCO - 1) / BCO;
   const int combos = nslices * tiles_c;
   const int ntiles = g.N * (g.Ho / HW_TH) * (g.Wo / HW_TW);
@@ -417,39 +417,34 @@ static hipError_t launch_wgrad_halo(const GatherDesc& g, const void* src, const 
   const int zs = (ntiles + tps - 1) / tps;
   const size_t lds = 2 * (size_t)(128 * BCO * 2 + HW_HPAD * BCI * 2) + (pro != nullptr ? 2 * BCI * sizeof(float) : 0);
   auto kern = pro != nullptr ? wgrad_halo_kernel<BCO, BCI, NTG, true> : wgrad_halo_kernel<BCO, BCI, NTG, false>;
-  static bool attr_done[2] = {false, false};                    // (per template instance of this launcher)
-  const int which = pro != nullptr ? 1 : 0;
-  if (!attr_done[which]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_done[which] = true;
-  }
   const ConvPro pv = pro != nullptr ? *pro : ConvPro{nullptr, nullptr, 0, 0.f, nullptr, 0};
-  count_launch(K_WGRAD_HALO);
-  prof_begin(PROF_WGRAD, 2.0 * (double)g.M * 9.0 * (double)g.Clog * (double)co_rows, st);
-  hipLaunchKernelGGL(kern, dim3(zs, combos), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs,
-                     nslices, tps, slab_elems, pv);
-  prof_end(PROF_WGRAD, st);
   *nsplit_out = zs;
-  return hipGetLastError();
+  return launch_counted(K_WGRAD_HALO, PROF_WGRAD, conv_flops(g, co_rows), kern, dim3(zs, combos), dim3(512), lds, st, g,
+                        (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, nslices, tps, slab_elems, pv);
+}
+
+// the shape gate and tile selection of the kernel (pro_ring: operand-path normalisation with a ring tensor)
+int wgrad_halo_shape_ok(const GatherDesc& g, int co_rows, bool pro_ring) {
+  if (pro_ring && (g.Hl < 4 || g.Wl < 4)) return 0;
+  if (g.sh != 1 || g.sw != 1 || g.ys != 1 || g.xs != 1 || g.th != 3 || g.tw != 3) return 0;
+  if (g.Ho % HW_TH != 0 || g.Wo % HW_TW != 0) return 0;
+  if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return 0;
+  if (co_rows <= 64) {
+    if (g.Cs % 128 == 0 && co_rows >= 48) return 1;
+    return g.Cs % 64 == 0 && co_rows <= 32 ? 2 : 0;        // thin heads: the work is the input stream; taps split over two wave groups
+  }
+  return g.Cs % 64 == 0 && co_rows >= 96 ? 3 : 0;
 }
 
 // returns hipErrorNotSupported when the shape does not qualify (the caller falls through to wgrad_v2 / v1)
 hipError_t wgrad_halo(const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* slabs,
-                      size_t slab_capacity_elems, int num_cu, int* nsplit_out, bool force, hipStream_t st, const ConvPro* pro) {
-  if (pro != nullptr && pro->ring != nullptr && (g.Hl < 4 || g.Wl < 4)) return hipErrorNotSupported;
-  if (g.sh != 1 || g.sw != 1 || g.ys != 1 || g.xs != 1 || g.th != 3 || g.tw != 3) return hipErrorNotSupported;
-  if (g.Ho % HW_TH != 0 || g.Wo % HW_TW != 0) return hipErrorNotSupported;
-  if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return hipErrorNotSupported;
-  if (co_rows <= 64) {
-    if (g.Cs % 128 == 0 && co_rows >= 48)
-      return launch_wgrad_halo<64, 128, 1>(g, src, dy, co_rows, ldy, slabs, slab_capacity_elems, num_cu, nsplit_out, force, st, pro);
-    if (g.Cs % 64 == 0 && co_rows <= 32)        // thin heads: the work is the input stream; taps split over two wave groups
-      return launch_wgrad_halo<64, 64, 2>(g, src, dy, co_rows, ldy, slabs, slab_capacity_elems, num_cu, nsplit_out, force, st, pro);
-    return hipErrorNotSupported;
+                      size_t slab_capacity_elems, int* nsplit_out, bool force, hipStream_t st, const ConvPro* pro) {
+  switch (wgrad_halo_shape_ok(g, co_rows, pro != nullptr && pro->ring != nullptr)) {
+    case 1: return launch_wgrad_halo<64, 128, 1>(g, src, dy, co_rows, ldy, slabs, slab_capacity_elems, nsplit_out, force, st, pro);
+    case 2: return launch_wgrad_halo<64, 64, 2>(g, src, dy, co_rows, ldy, slabs, slab_capacity_elems, nsplit_out, force, st, pro);
+    case 3: return launch_wgrad_halo<128, 64, 1>(g, src, dy, co_rows, ldy, slabs, slab_capacity_elems, nsplit_out, force, st, pro);
   }
-  if (g.Cs % 64 != 0 || co_rows < 96) return hipErrorNotSupported;
-  return launch_wgrad_halo<128, 64, 1>(g, src, dy, co_rows, ldy, slabs, slab_capacity_elems, num_cu, nsplit_out, force, st, pro);
+  return hipErrorNotSupported;
 }
 
 }  // namespace dei2i

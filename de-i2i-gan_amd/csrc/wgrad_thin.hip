@@ -174,14 +174,14 @@ __global__ __launch_bounds__(512) void wgrad_thin_kernel(const GatherDesc g, con
 
 // returns hipErrorNotSupported when the shape does not qualify (the caller falls through to the other wgrad kernels)
 hipError_t wgrad_thin(const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* slabs,
-                      size_t slab_capacity_elems, int num_cu, int* nsplit_out, hipStream_t st) {
+                      size_t slab_capacity_elems, int* nsplit_out, hipStream_t st) {
   if (g.Cs != 8 || g.sh != 1 || g.sw != 1 || g.ys != 1 || g.xs != 1 || g.up != 0 || g.th != 7 || g.tw != 7)
     return hipErrorNotSupported;
   if (g.Ho % WT_TH != 0 || g.Wo % WT_TW != 0 || co_rows > WT_BCO || ldy < 8) return hipErrorNotSupported;
   if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return hipErrorNotSupported;
   const int ntiles = g.N * (g.Ho / WT_TH) * (g.Wo / WT_TW);
   if (ntiles < 64) return hipErrorNotSupported;
-  int splits = std::min(2 * num_cu, ntiles / 4);   // 44 KB of LDS per workgroup
+  int splits = std::min(2 * num_cu(), ntiles / 4);   // 44 KB of LDS per workgroup
   const long long slab_elems = wgrad_slab_elems(co_rows, g.K);
   if ((size_t)slab_elems * splits > slab_capacity_elems) splits = (int)(slab_capacity_elems / (size_t)slab_elems);
   if (splits < 1) return hipErrorNotSupported;
@@ -189,20 +189,9 @@ hipError_t wgrad_thin(const GatherDesc& g, const void* src, const void* dy, int 
   const int zs = (ntiles + tps - 1) / tps;
   constexpr int HPIX = (WT_TH + 6) * (WT_TW + 6);
   const size_t lds = 2 * (size_t)(WT_A_BYTES + ((HPIX + 4 + 63) / 64) * 1024);
-  auto kern = wgrad_thin_kernel<7, 7>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  count_launch(K_WGRAD_THIN);
-  prof_begin(PROF_WGRAD, 2.0 * (double)g.M * 49.0 * (double)g.Clog * (double)co_rows, st);
-  hipLaunchKernelGGL(kern, dim3(zs), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, tps,
-                     slab_elems);
-  prof_end(PROF_WGRAD, st);
   *nsplit_out = zs;
-  return hipGetLastError();
+  return launch_counted(K_WGRAD_THIN, PROF_WGRAD, conv_flops(g, co_rows), wgrad_thin_kernel<7, 7>, dim3(zs), dim3(512), lds, st, g,
+                        (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, tps, slab_elems);
 }
 
 }  // namespace dei2i

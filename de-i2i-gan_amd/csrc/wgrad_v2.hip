@@ -222,48 +222,25 @@ __global__ __launch_bounds__(256) void wgrad_reduce_unpack_kernel(const float* _
 }
 
 hipError_t wgrad_v2(const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* slabs,
-                    size_t slab_capacity_elems, int num_cu, int* nsplit_out, hipStream_t st) {
+                    size_t slab_capacity_elems, int* nsplit_out, hipStream_t st) {
   if (g.Cs % 128 != 0 || co_rows < 96 || g.M < 4096) return hipErrorNotSupported;
   const int BM = co_rows >= 192 ? 256 : 128;
   constexpr int BN = 128, BR = 64;
   const int tiles_c = (co_rows + BM - 1) / BM, tiles_k = (g.K + BN - 1) / BN;
   const int tiles = tiles_c * tiles_k;
   const int nchunks = (g.M + BR - 1) / BR;
-  int splits = std::max(1, num_cu / tiles);                  // one workgroup per CU (144 KB LDS), a single round
+  int splits = std::max(1, num_cu() / tiles);                  // one workgroup per CU (144 KB LDS), a single round
   if (splits > nchunks / 8) splits = std::max(1, nchunks / 8);
   const long long slab_elems = wgrad_slab_elems(co_rows, g.K);
   if ((size_t)slab_elems * splits > slab_capacity_elems) splits = (int)(slab_capacity_elems / (size_t)slab_elems);
   if (splits < 1) return hipErrorNotSupported;
   const int cps = (nchunks + splits - 1) / splits;
   const int zs = (nchunks + cps - 1) / cps;
-  count_launch(K_WGRAD_V2);
-  prof_begin(PROF_WGRAD, 2.0 * (double)g.M * (double)(g.th * g.tw) * (double)g.Clog * (double)co_rows, st);
-  if (BM == 256) {
-    const size_t lds = 3 * (size_t)(64 * 512 + 64 * 256);
-    auto kern = wgrad_v2_kernel<256>;
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles, 1, zs), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy,
-                       slabs, tiles_k, cps, slab_elems);
-  } else {
-    const size_t lds = 3 * (size_t)(64 * 256 + 64 * 256);
-    auto kern = wgrad_v2_kernel<128>;
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles, 1, zs), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy,
-                       slabs, tiles_k, cps, slab_elems);
-  }
-  prof_end(PROF_WGRAD, st);
   *nsplit_out = zs;
-  return hipGetLastError();
+  const size_t lds = 3 * (size_t)(64 * 2 * BM + 64 * 256);
+  return launch_counted(K_WGRAD_V2, PROF_WGRAD, conv_flops(g, co_rows), BM == 256 ? wgrad_v2_kernel<256> : wgrad_v2_kernel<128>,
+                        dim3(tiles, 1, zs), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, tiles_k,
+                        cps, slab_elems);
 }
 
 // first level of a two-level slab sum, used when the (co, channel-block) grid alone cannot fill the chip (thin layers

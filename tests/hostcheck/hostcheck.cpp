@@ -56,18 +56,12 @@ void hc_pack_fwd(const int* p, const float* w, float* packed) {
 
 long long hc_pack_dgrad(const int* p, const float* w, float* packed) {
   const int Cin = p[3], Cout = p[4], CoutS = p[6], kh = p[7], kw = p[8], s = p[9];
-  long long off = 0;
-  for (int ay = 0; ay < s; ++ay)
-    for (int ax = 0; ax < s; ++ax) {
-      const int th = dgrad_taps(kh, s, ay), tw = dgrad_taps(kw, s, ax);
-      const long long total = (long long)Cin * th * tw * CoutS;
-      for (long long i = 0; i < total; ++i) {
-        const long long si = packed_dgrad_src(i, Cout, Cin, CoutS, kh, kw, s, ay, ax, th, tw);
-        packed[off + i] = si >= 0 ? w[si] : 0.f;
-      }
-      off += total;
+  return for_each_dgrad_class(Cin, CoutS, kh, kw, s, [&](const DgradClass& k) {
+    for (long long i = 0; i < k.count; ++i) {
+      const long long si = packed_dgrad_src(i, Cout, Cin, CoutS, kh, kw, s, k.ay, k.ax, k.th, k.tw);
+      packed[k.off + i] = si >= 0 ? w[si] : 0.f;
     }
-  return off;
+  });
 }
 
 void hc_conv_fwd(const int* p, const float* x, const float* wpacked, float* y) {
@@ -77,14 +71,10 @@ void hc_conv_fwd(const int* p, const float* x, const float* wpacked, float* y) {
 
 void hc_conv_dgrad(const int* p, const float* dy, const float* wd_packed, float* dx_ext) {
   ConvShape s = shape_of(p);
-  long long off = 0;
-  for (int ay = 0; ay < s.stride; ++ay)
-    for (int ax = 0; ax < s.stride; ++ax) {
-      GatherDesc g = make_dgrad_desc(s, p[6], ay, ax);
-      const long long welems = (long long)s.Cin * g.th * g.tw * p[6];
-      if (g.M > 0) run_gather_gemm(g, dy, wd_packed + off, s.Cin, dx_ext, p[5]);
-      off += welems;
-    }
+  for_each_dgrad_class(s.Cin, p[6], s.kh, s.kw, s.stride, [&](const DgradClass& k) {
+    GatherDesc g = make_dgrad_desc(s, p[6], k.ay, k.ax);
+    if (g.M > 0) run_gather_gemm(g, dy, wd_packed + k.off, s.Cin, dx_ext, p[5]);
+  });
 }
 
 // wgrad through the forward descriptor: dw[co][k] = sum_m dy[m][co] * gather(x)[m][k]
@@ -137,14 +127,8 @@ long long hc_conv_dgrad_decomposed(const int* p, const float* dy, const float* w
   const GatherDesc interior = make_dgrad_desc(z, CoutS, 0, 0);
   run_gather_gemm(interior, dy, wd, CinS, dx, CinS);
   const int OH = s.H + 2 * pad, OW = s.W + 2 * pad;
-  GatherDesc ring[4] = {sub_rect_desc(frame, 0, pad, 0, OW), sub_rect_desc(frame, s.H + pad, pad, 0, OW),
-                        sub_rect_desc(frame, pad, s.H, 0, pad), sub_rect_desc(frame, pad, s.H, s.W + pad, pad)};
-  if (s.kh == 2 * pad + 1 && s.kw == 2 * pad + 1) {           // live taps only, as dei2i_conv2d_dgrad_input does
-    ring[0] = sub_taps_desc(ring[0], 0, pad, 0, s.kw);
-    ring[1] = sub_taps_desc(ring[1], s.kh - pad, pad, 0, s.kw);
-    ring[2] = sub_taps_desc(ring[2], 0, s.kh, 0, pad);
-    ring[3] = sub_taps_desc(ring[3], 0, s.kh, s.kw - pad, pad);
-  }
+  GatherDesc ring[4];
+  reflect_ring_descs(frame, s.H, s.W, pad, s.kh, s.kw, ring);      // the builder dei2i_conv2d_dgrad_input uses
   long long written = 0;
   for (int k = 0; k < 4; ++k) {
     run_gather_gemm(ring[k], dy, wd, CinS, ext, CinS);
@@ -185,28 +169,15 @@ long long hc_conv_dgrad_decomposed(const int* p, const float* dy, const float* w
 long long hc_conv_dgrad_decomposed_s2(const int* p, const float* dy, const float* wd, float* ext, float* dx) {
   ConvShape s = shape_of(p);
   const int CinS = p[5], CoutS = p[6];
-  GatherDesc fr[2][2];
-  long long woff[2][2], off = 0;
-  for (int ay = 0; ay < 2; ++ay)
-    for (int ax = 0; ax < 2; ++ax) {
-      fr[ay][ax] = make_dgrad_desc(s, CoutS, ay, ax);
-      woff[ay][ax] = off;
-      off += (long long)s.Cin * dgrad_taps(s.kh, 2, ay) * dgrad_taps(s.kw, 2, ax) * CoutS;
-    }
   ConvShape z = s;
   z.pad_mode = PAD_ZERO;
-  for (int ay = 0; ay < 2; ++ay)
-    for (int ax = 0; ax < 2; ++ax) {
-      const GatherDesc g = make_dgrad_desc(z, CoutS, ay, ax);
-      if (g.M > 0) run_gather_gemm(g, dy, wd + woff[ay][ax], s.Cin, dx, CinS);
-    }
-  const GatherDesc rects[8] = {sub_rect_desc(fr[0][0], 0, 1, 0, fr[0][0].Wo), sub_rect_desc(fr[0][1], 0, 1, 0, fr[0][1].Wo),
-                               sub_rect_desc(fr[1][0], fr[1][0].Ho - 1, 1, 0, fr[1][0].Wo),
-                               sub_rect_desc(fr[1][1], fr[1][1].Ho - 1, 1, 0, fr[1][1].Wo),
-                               sub_rect_desc(fr[0][0], 1, fr[0][0].Ho - 1, 0, 1), sub_rect_desc(fr[1][0], 0, fr[1][0].Ho - 1, 0, 1),
-                               sub_rect_desc(fr[0][1], 1, fr[0][1].Ho - 1, fr[0][1].Wo - 1, 1),
-                               sub_rect_desc(fr[1][1], 0, fr[1][1].Ho - 1, fr[1][1].Wo - 1, 1)};
-  const long long woffs[8] = {woff[0][0], woff[0][1], woff[1][0], woff[1][1], woff[0][0], woff[1][0], woff[0][1], woff[1][1]};
+  for_each_dgrad_class(s.Cin, CoutS, s.kh, s.kw, 2, [&](const DgradClass& k) {
+    const GatherDesc g = make_dgrad_desc(z, CoutS, k.ay, k.ax);
+    if (g.M > 0) run_gather_gemm(g, dy, wd + k.off, s.Cin, dx, CinS);
+  });
+  GatherDesc rects[8];
+  long long woffs[8];
+  s2_ring_descs(s, CoutS, rects, woffs, rects + 4, woffs + 4);     // the builder dei2i_conv2d_dgrad_input uses
   long long written = 0;
   for (int k = 0; k < 8; ++k) {
     run_gather_gemm(rects[k], dy, wd + woffs[k], s.Cin, ext, CinS);

@@ -50,13 +50,13 @@ def cdiv(a, b):
 
 # ---- the gates, with the expressions of the source -------------------------------------------------------------------------------
 def n_halo16(tiles_per_image, ldc):
-    """halo16_conv / halo16_s2_shape_ok: tiles_m * tn >= num_cu * 7 / 8 (16 x 32 tiles; tn counts 128-channel tiles from 128 channels on)"""
+    """halo16_shape_ok / halo16_s2_shape_ok: tiles_m * tn >= num_cu * 7 / 8 (16 x 32 tiles; tn counts 128-channel tiles from 128 channels on)"""
     tn = cdiv(ldc, 128) if ldc >= 128 else 1
     return lambda cu: cdiv((cu * 7) // 8, tiles_per_image * tn)
 
 
 def n_halo8(tiles_per_image, ldc):
-    """halo_conv: tiles_m * ceil(ldc / 128) >= num_cu / 2 from 128 channels on, tiles_m >= num_cu / 2 below (8 x 32 tiles)"""
+    """halo_conv_shape_ok: tiles_m * ceil(ldc / 128) >= num_cu / 2 from 128 channels on, tiles_m >= num_cu / 2 below (8 x 32 tiles)"""
     tn = cdiv(ldc, 128) if ldc >= 128 else 1
     return lambda cu: cdiv(cu // 2, tiles_per_image * tn)
 

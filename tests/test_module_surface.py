@@ -54,6 +54,33 @@ def test_library_exports_every_declared_symbol():
     assert lib.dei2i_version() >= 100
 
 
+def test_option_table_and_kernel_names():
+    """dei2i_set_option takes every documented name (and only names), dei2i_kernel_name has one distinct name per counter."""
+    from ctypes import c_int64
+    from de_i2i_gan_amd import _lib
+    header = (REPO / "include" / "dei2i_hip.h").read_text()
+    bad_arg = int(re.search(r"#define DEI2I_ERR_BAD_ARG \((-?\d+)\)", header).group(1))
+    doc = header[header.index("/* A-B switches"):header.index("int dei2i_set_option")]
+    names = re.findall(r'"([a-z0-9_]+)"', doc)
+    assert len(names) == len(set(names)) == 10, names
+    lib = _lib.load()
+    for name in names:
+        try:
+            assert lib.dei2i_set_option(name.encode(), 0) == 0, name
+        finally:
+            assert lib.dei2i_set_option(name.encode(), 1) == 0, name          # 1 = on, the default of every switch
+    assert lib.dei2i_set_option(None, 1) == bad_arg
+    assert lib.dei2i_set_option(b"no_such_option", 1) == bad_arg
+    assert lib.dei2i_set_option(b"halo16 ", 1) == bad_arg
+    buf = (c_int64 * 64)()
+    count = lib.dei2i_launch_counts(buf, 64)
+    assert 0 < count <= 64
+    kernel_names = [lib.dei2i_kernel_name(i) for i in range(count)]
+    assert all(n is not None and len(n) > 0 for n in kernel_names), kernel_names
+    assert len(set(kernel_names)) == count, kernel_names
+    assert lib.dei2i_kernel_name(count) is None and lib.dei2i_kernel_name(-1) is None
+
+
 def test_ops_refuse_cpu_tensors():
     from de_i2i_gan_amd import ops
     with pytest.raises(RuntimeError, match="no CPU fallback"):
