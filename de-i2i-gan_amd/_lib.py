@@ -1,7 +1,7 @@
 """ctypes binding of libdei2i_hip.so (C ABI: include/dei2i_hip.h).  Fails loudly when the library is missing."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdei2i_hip.so")
@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libdei2i_hip.so")
 BF16, F32 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 PAD_ZERO, PAD_REFLECT = 0, 1
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT, DIFFAUG_MAX_RUNS = 1, 2, 4, 16
 PROF_GATHER_GEMM, PROF_WGRAD, PROF_HALO_CONV, PROF_HALO_FOLD = 0, 1, 2, 3
 
 
@@ -121,6 +122,7 @@ SIGNATURES = {
     "dei2i_ema_lerp": (c_int, [_P, c_int, c_int64, c_float, _P]),
     "dei2i_diffaug_partial_floats": (c_size_t, [c_int]),
     "dei2i_diffaug": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "dei2i_diffaug_draw": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, c_int, c_int, _P, _P]),
     "dei2i_prof_enable": (c_int, [c_int, c_int]),
     "dei2i_prof_collect": (c_int, [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
     "dei2i_prof_collect_timed": (c_int, [c_int, POINTER(c_int64), POINTER(c_double)]),

@@ -9,6 +9,10 @@
 // mode 0: forward with beta; mode 1: the forward's linear part (beta = 0: the adjoint's own gradient); mode 2: adjoint.
 // One launch reduces each sample to <= 64 fixed-order partial sums (only when the run has color: mean_chw), a second applies the
 // operator; the apply kernel sums the partials in a fixed order itself -- no atomics, bit-reproducible.
+//
+// dei2i_diffaug_draw fills the record table on the device: Philox4x32-10 keyed by a seed, counted by (call, run, global row), the
+// call count one word of device memory that the launch itself advances -- an eager step and a replay of a captured step draw the
+// same parameters, and every replay draws new ones.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dei2i_hip.h"
@@ -149,6 +153,80 @@ __global__ __launch_bounds__(kThreads) void diffaug_apply_kernel(const float* __
   }
 }
 
+// ---- device-drawn records ------------------------------------------------------------------------------------------
+struct Philox4 {
+  uint32_t x0, x1, x2, x3;
+};
+
+// Philox4x32-10 (Salmon et al. 2011, Random123): ten rounds, the key bumped by the Weyl constants between rounds
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += W0;
+    k1 += W1;
+  }
+  return Philox4{c0, c1, c2, c3};
+}
+
+// the grid of torch.rand: 24 bits, [0, 1)
+__device__ __forceinline__ float unit_float(uint32_t x) {
+#pragma clang fp contract(off)
+  return (float)(x >> 8) * 0x1p-24f;
+}
+
+// what the host works out once per call: the integer ranges of utils.diffaug.draw_params
+struct DrawGeom {
+  int max_y, max_x;          // translation: ty in [-max_y, max_y], tx in [-max_x, max_x]
+  int range_cy, range_cx;    // cutout centre: cy in [0, range_cy), cx in [0, range_cx)
+  int half_ch, half_cw;      // top = cy - half_ch, left = cx - half_cw
+};
+
+// One workgroup strides over the runs x N records.  flags: 3 bits per run (DEI2I_DIFFAUG_COLOR / _TRANSLATION / _CUTOUT).  Every
+// thread reads the call count, then thread 0 stores count + 1 behind the barrier: one launch, no atomics.  Contraction is off:
+// the arithmetic has no multiply-add, so a numpy reference reproduces the table bit for bit.
+__global__ __launch_bounds__(kThreads) void diffaug_draw_kernel(unsigned long long seed, unsigned long long* __restrict__ counter,
+                                                                int runs, unsigned long long flags, int N, unsigned row0,
+                                                                DrawGeom g, dei2i_diffaug_rec* __restrict__ tab) {
+#pragma clang fp contract(off)
+  const unsigned long long call = *counter;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), c0 = (uint32_t)call, c1 = (uint32_t)(call >> 32);
+  for (int i = threadIdx.x; i < runs * N; i += kThreads) {
+    const int run = i / N, n = i - run * N;
+    const unsigned f = (unsigned)(flags >> (3 * run)) & 7u;
+    const uint32_t row = row0 + (uint32_t)n;
+    dei2i_diffaug_rec r = {1.f, 0.f, 0.f, 0.f, 0, 0, 0, 0};
+    if (f & DEI2I_DIFFAUG_COLOR) {
+      const Philox4 x = philox4x32_10(c0, c1, (uint32_t)run, row, k0, k1);
+      const float rb = unit_float(x.x0), rs = unit_float(x.x1), rc = unit_float(x.x2);
+      const float ks = 2.f * rs, kc = rc + 0.5f;
+      r.a = kc * ks;
+      r.b = kc * (1.f - ks);
+      r.k = 1.f - kc;
+      r.beta = rb - 0.5f;
+    }
+    if (f & (DEI2I_DIFFAUG_TRANSLATION | DEI2I_DIFFAUG_CUTOUT)) {
+      const Philox4 x = philox4x32_10(c0, c1, (uint32_t)run | (1u << 16), row, k0, k1);
+      if (f & DEI2I_DIFFAUG_TRANSLATION) {
+        r.ty = -g.max_y + (int)__umulhi(x.x0, (uint32_t)(2 * g.max_y + 1));
+        r.tx = -g.max_x + (int)__umulhi(x.x1, (uint32_t)(2 * g.max_x + 1));
+      }
+      if (f & DEI2I_DIFFAUG_CUTOUT) {
+        r.top = (int)__umulhi(x.x2, (uint32_t)g.range_cy) - g.half_ch;
+        r.left = (int)__umulhi(x.x3, (uint32_t)g.range_cx) - g.half_cw;
+      }
+    }
+    tab[i] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) *counter = call + 1;
+}
+
 void chunking(int N, int H, int* rpc, int* chunks) {
   int want = (1024 + N - 1) / N;               // ~4 blocks per CU over the batch
   want = want < 1 ? 1 : (want > kMaxChunks ? kMaxChunks : want);
@@ -180,5 +258,25 @@ extern "C" int dei2i_diffaug(int mode, int N, int C, int H, int W, int ch, int c
   const long long items = (long long)H * (vec ? W / 4 : W);
   hipLaunchKernelGGL(diffaug_apply_kernel, dim3((unsigned)((items + kThreads - 1) / kThreads), (unsigned)N), dim3(kThreads), 0, st, src,
                      tab, partial, chunks, C, H, W, ch, cw, mode, color, vec, dst);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dei2i_diffaug_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
+                                  dei2i_diffaug_rec* tab, dei2i_stream s) {
+  if (!counter_dev || !tab || runs <= 0 || runs > DEI2I_DIFFAUG_MAX_RUNS || N <= 0 || row0 < 0 || H <= 0 || W <= 0) return DEI2I_ERR_BAD_ARG;
+  if ((long long)row0 + N > (1ll << 31) || (long long)runs * N >= (1ll << 24) || H > (1 << 24) || W > (1 << 24)) return DEI2I_ERR_BAD_ARG;
+  if ((run_flags >> (3 * runs)) != 0) return DEI2I_ERR_BAD_ARG;
+  for (int r = 0; r < runs; ++r)
+    if (((run_flags >> (3 * r)) & 7u) == 0) return DEI2I_ERR_BAD_ARG;          // (a run holds at least one policy)
+  const int ch = (int)(H * 0.5 + 0.5), cw = (int)(W * 0.5 + 0.5);
+  DrawGeom g;
+  g.max_y = (int)(H * 0.125 + 0.5);
+  g.max_x = (int)(W * 0.125 + 0.5);
+  g.range_cy = H + (1 - ch % 2);
+  g.range_cx = W + (1 - cw % 2);
+  g.half_ch = ch / 2;
+  g.half_cw = cw / 2;
+  hipLaunchKernelGGL(diffaug_draw_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)s, (unsigned long long)seed,
+                     reinterpret_cast<unsigned long long*>(counter_dev), runs, (unsigned long long)run_flags, N, (unsigned)row0, g, tab);
   return (int)hipGetLastError();
 }

@@ -41,6 +41,21 @@ class DefectGanModel(BaseModel):
             self.clf_loss_type = opt.clf_loss_type
         if hasattr(opt, "mask_token_type"):              # learnable mask token of the MAE stage (defectgan_model.py:31-32)
             self.mask_token = MaskToken(opt).to(opt.device, non_blocking=True)
+        # opt.diff_aug_rng: "host" (or absent) draws DiffAugment's parameters from the global CPU RNG like the reference; "device"
+        # draws them on the GPU from a counter-based generator (ops.DiffAugRng), which a captured step (opt.graph_step) can replay.
+        # The generator is no network: checkpoints do not carry it (the reference's carry no RNG state either) and it outlives
+        # checkpoint loads and released graphs.
+        self.diffaug_rng = None
+        where = getattr(opt, "diff_aug_rng", None) or "host"
+        if where == "device":
+            if torch.device(opt.device).type != "cuda":
+                raise ValueError(f"diff_aug_rng='device' draws on the GPU; opt.device is {opt.device}")
+            seed = getattr(opt, "diff_aug_seed", None)
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            self.diffaug_rng = ops.DiffAugRng(seed, opt.device)
+        elif where != "host":
+            raise ValueError(f"|diff_aug_rng {where}| is invalid (host | device)")
 
     def __call__(self, mode, data, labels, df_data=None, img_only=False, mask=None):
         data, labels = data.to(self.opt.device, non_blocking=True), labels.to(self.opt.device, non_blocking=True)
@@ -86,6 +101,13 @@ class DefectGanModel(BaseModel):
     @staticmethod
     def _mean(terms):
         return torch.stack(terms).mean()
+
+    def _diff_augment(self, x, policy):
+        """DiffAugment on one batch the discriminator sees: the torch-op policy functions with host draws, or (diff_aug_rng
+        'device') the fused kernels on a device-drawn table"""
+        if self.diffaug_rng is None or not policy:
+            return diff_augment(x, policy)
+        return ops.diff_augment(x if x.dtype == torch.float32 else x.float(), policy, rng=self.diffaug_rng)
 
     def _netD_batched(self, *images):
         """netD(x) for several image batches in ONE pass over their concatenation.  The discriminator has no batch
@@ -308,7 +330,7 @@ class DefectGanModel(BaseModel):
                 fakes_src, fakes_cls = self.netD(fakes)
             else:
                 (fake_defects_src, fake_defects_cls), (fake_normals_src, fake_normals_cls) = \
-                    self._netD_batched(diff_augment(fake_defects, policy), diff_augment(fake_normals, policy))
+                    self._netD_batched(self._diff_augment(fake_defects, policy), self._diff_augment(fake_normals, policy))
         finally:
             for p in d_params:
                 p.requires_grad_(True)
@@ -369,8 +391,8 @@ class DefectGanModel(BaseModel):
                 fakes, _ = self.netG(torch.cat([bg_data, df_data], 0), both_labels, feats)
                 fake_defects, fake_normals = fakes.split([bg_data.shape[0], df_data.shape[0]])
         policy = getattr(self.opt, "diff_aug", "")            # defectgan_model.py:266-270: fakes first, then the real batches
-        fake_defects, fake_normals = diff_augment(fake_defects.detach(), policy), diff_augment(fake_normals.detach(), policy)
-        df_data, bg_data = diff_augment(df_data, policy), diff_augment(bg_data, policy)
+        fake_defects, fake_normals = self._diff_augment(fake_defects.detach(), policy), self._diff_augment(fake_normals.detach(), policy)
+        df_data, bg_data = self._diff_augment(df_data, policy), self._diff_augment(bg_data, policy)
         (fake_defects_src, _), (fake_normals_src, _), (real_defects_src, real_defects_cls), \
             (real_normals_src, real_normals_cls) = self._netD_batched(fake_defects, fake_normals, df_data, bg_data)
         gan_loss = [self._cal_loss(fake_defects_src, 0.0, "bce"), self._cal_loss(fake_normals_src, 0.0, "bce"),

@@ -3,6 +3,10 @@
 Internal activations are NHWC tensors of the compute dtype (bf16, or f32 in parity mode) whose last dimension is the
 channel count padded to a 16-byte vector.  NCHW fp32 appears only at the module boundary (inputs, outputs,
 parameters, gradients, state_dict), as in the reference.  Every op requires a GPU tensor; there is no fallback.
+
+Random numbers: ``NoiseInjection`` draws with torch's device RNG; ``diff_augment`` draws its per-sample parameters from the global
+CPU RNG and uploads them (the reference's draws), or, given a ``DiffAugRng``, on the device from a counter-based generator whose
+call count lives in device memory -- the form a captured graph can replay.
 """
 from __future__ import annotations
 
@@ -1955,21 +1959,79 @@ class diffaug_sharded:
         return False
 
 
-def diff_augment(x, policy=""):
-    """DiffAugment(x, policy) of utils/diffaug.py on an NCHW fp32 GPU image batch: the same draws from the global CPU RNG, one upload
-    of the parameter table per call, one or two launches per canonical-order policy run.  ``policy == ""`` returns ``x`` itself.
+# Device-drawn parameters.  The host path above draws from the global CPU RNG and uploads per call, which a captured step would
+# freeze into every replay.  ``DiffAugRng`` is a counter-based generator instead (Philox4x32-10, csrc/diffaug.hip
+# dei2i_diffaug_draw): the seed travels in the kernel arguments, the call count is one word of device memory that every draw launch
+# advances itself, and a record is a pure function of (seed, call, run, global row) -- an eager call and a replay of its capture
+# draw the same table, every replay a new one, and a rank's rows are the slice of the global batch's table without any broadcast.
+class DiffAugRng:
+    """The seed and the device call counter of ``diff_augment(..., rng=...)``.  The counter is allocated here, outside any capture,
+    and must outlive every graph that recorded a draw on it.  ``state()`` / ``set_state()`` synchronise: not for use inside a step."""
+
+    def __init__(self, seed: int, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"DiffAugRng draws on the GPU; device {self.device} is not one (there is no CPU fallback)")
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)      # (the bits of one unsigned 64-bit word)
+        self.device = self.counter.device                    # (with its index)
+
+    def state(self):
+        """-> (seed, number of draw launches so far)"""
+        return self.seed, int(self.counter.item()) & (2 ** 64 - 1)
+
+    def set_state(self, state):
+        seed, calls = state
+        calls = int(calls) & (2 ** 64 - 1)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        torch.cuda.synchronize(self.device)                  # (draws queued on any stream read the old count)
+        self.counter.fill_(calls - 2 ** 64 if calls >= 2 ** 63 else calls)
+        torch.cuda.synchronize(self.device)
+
+
+def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0):
+    """One dei2i_diffaug_draw launch on the current stream: -> (tab, runs), ``tab`` a device int32 (len(runs), n, 8) table of struct
+    dei2i_diffaug_rec for global rows [row0, row0 + n), ``runs`` the (has_color, cut_h, cut_w) list of utils.diffaug.draw_params.
+    Nothing is read from the host RNG and nothing is uploaded."""
+    from .utils.diffaug import REC_FIELDS, policy_runs
+    names = policy_runs(policy)
+    if not 0 < len(names) <= L.DIFFAUG_MAX_RUNS:
+        raise ValueError(f"diff_augment with a device RNG takes 1..{L.DIFFAUG_MAX_RUNS} canonical-order runs; {policy!r} has {len(names)}")
+    bit = {"color": L.DIFFAUG_COLOR, "translation": L.DIFFAUG_TRANSLATION, "cutout": L.DIFFAUG_CUTOUT}
+    flags, runs = 0, []
+    for r, run in enumerate(names):
+        flags |= sum(bit[name] for name in run) << (3 * r)
+        cut = "cutout" in run
+        runs.append(("color" in run, int(h * 0.5 + 0.5) if cut else 0, int(w * 0.5 + 0.5) if cut else 0))
+    tab = torch.empty((len(names), n, REC_FIELDS), dtype=torch.int32, device=rng.device)
+    lib = _lib_for(tab)
+    L.check(lib.dei2i_diffaug_draw(rng.seed, _p(rng.counter), len(names), flags, n, int(row0), h, w, _p(tab), _stream()), "diffaug_draw")
+    return tab, runs
+
+
+def diff_augment(x, policy="", rng=None):
+    """DiffAugment(x, policy) of utils/diffaug.py on an NCHW fp32 GPU image batch, one or two launches per canonical-order policy
+    run.  ``policy == ""`` returns ``x`` itself.  ``rng=None``: the same draws from the global CPU RNG as utils/diffaug.py, one
+    upload of the parameter table per call.  ``rng`` a ``DiffAugRng``: the table is drawn on the device by one more launch
+    (``diffaug_draw``) -- the CPU RNG is not touched, nothing is uploaded, and the call can be captured into a graph.
     Inside ``diffaug_sharded`` ``x`` is one rank's rows of the global batch (above)."""
     if not policy:
         return x
-    from .utils.diffaug import draw_params
     _require_gpu(x, "diff_augment")
     if x.dim() != 4 or x.dtype != torch.float32:
         raise TypeError("diff_augment expects an NCHW fp32 image batch")
     n, _, h, w = x.shape
-    rec, runs = draw_params(policy, n, h, w, shard=diffaug_shard)
-    host = torch.empty(rec.shape, dtype=torch.int32, pin_memory=True)
-    host.copy_(torch.from_numpy(rec))
-    tab = host.to(x.device, non_blocking=True)
+    if rng is not None:
+        if rng.device != x.device:
+            raise ValueError(f"diff_augment: the DiffAugRng lives on {rng.device}, the images on {x.device}")
+        tab, runs = diffaug_draw(rng, policy, n, h, w, row0=diffaug_shard[0] * n if diffaug_shard is not None else 0)
+        host = None
+    else:
+        from .utils.diffaug import draw_params
+        rec, runs = draw_params(policy, n, h, w, shard=diffaug_shard)
+        host = torch.empty(rec.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(torch.from_numpy(rec))
+        tab = host.to(x.device, non_blocking=True)
     for i, run in enumerate(runs):
         x = _DiffAug.apply(x, tab[i], run, 0, host)
     return x

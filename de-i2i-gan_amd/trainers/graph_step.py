@@ -9,7 +9,11 @@ exists before the capture), then captures the graph the iteration needs -- D onl
 
 A call whose inputs differ in shape, dtype or device from the captured ones runs eagerly on the current stream and keeps the
 graphs.  ``release_graphs()`` drops them; a checkpoint load, a change of ``opt.compute_dtype`` and ``attach_ddp`` do so too.
-What the capture cannot honour raises ``NotImplementedError`` (``unsupported``)."""
+What the capture cannot honour raises ``NotImplementedError`` (``unsupported``).
+
+``opt.diff_aug`` is captured when its parameters are drawn on the device (``opt.diff_aug_rng = "device"``: ops.DiffAugRng, whose
+call counter lives in device memory and advances inside the draw launch, so every replay draws what the eager call would have
+drawn); with host draws, which a capture would freeze into every replay, it is refused."""
 import torch
 
 from .. import ops
@@ -31,8 +35,9 @@ def capture_stream(device):
 def unsupported(trainer):
     """-> the first option the captured step cannot honour (None: all supported)"""
     opt = trainer.opt
-    if getattr(opt, "diff_aug", ""):
-        return "diff_aug (its parameters are drawn on the host and uploaded per call)"
+    if getattr(opt, "diff_aug", "") and getattr(trainer.model, "diffaug_rng", None) is None:
+        return ("diff_aug with host draws (its parameters are drawn from the CPU RNG and uploaded per call; build the trainer with "
+                "diff_aug_rng='device' to draw them on the GPU)")
     if opt.style_norm_block_type == "sean":
         return "style_norm_block_type='sean' (it draws style embeddings with the host's random.choices)"
     if opt.style_norm_block_type != "spade":

@@ -7,7 +7,12 @@ NCHW fp32 images.  The policy functions below are plain torch ops and define the
 them); ``ops.diff_augment`` is the same map as fused HIP kernels (csrc/diffaug.hip), differentiable to any order, whose
 host half is ``draw_params``.  The per-sample random numbers are drawn with the global torch RNG ON THE HOST in the
 reference's order -- a run seeded like the reference's CPU path sees the reference's augmentations -- and uploaded (a few
-values per sample)."""
+values per sample).
+
+``opt.diff_aug_rng = "device"`` (opt-in) takes neither half: the defectGAN model then calls ``ops.diff_augment(x, policy,
+rng=ops.DiffAugRng)``, whose table is filled on the device by a counter-based generator with the formulas of ``draw_params``
+(csrc/diffaug.hip dei2i_diffaug_draw) -- the same distributions, not the reference's draws, and nothing a graph capture would
+freeze.  ``policy_runs`` serves both."""
 import numpy as np
 import torch
 

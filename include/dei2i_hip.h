@@ -283,6 +283,20 @@ typedef struct dei2i_diffaug_rec {
 size_t dei2i_diffaug_partial_floats(int N);
 int dei2i_diffaug(int mode, int N, int C, int H, int W, int ch, int cw, int color, const float* src, const dei2i_diffaug_rec* tab,
                   float* partial, float* dst, dei2i_stream s);
+/* Fill tab[run][n] (runs x N records, n in [0, N)) on the device, as utils.diffaug.draw_params fills it on the host, from
+ * Philox4x32-10: key = seed, counter words = (call low 32, call high 32, run | block << 16, row0 + n), call = *counter_dev as the
+ * launch finds it; block 0 gives rb, rs, rc (x0..x2, float = (x >> 8) * 2^-24), block 1 ty, tx, cy, cx (x0..x3, integer in
+ * [lo, lo + range) = lo + mulhi(x, range)).  run_flags: 3 bits per run, run r at bits [3r, 3r + 3), the policies the run holds; a
+ * field whose policy is absent holds the identity.  One launch of one workgroup; it leaves *counter_dev (one 64-bit word of device
+ * memory) greater by exactly 1 -- launches that share a counter must be ordered on one stream (or one captured graph).  The draw is
+ * a pure function of (seed, call, run, row0 + n): rows [row0, row0 + N) of a call are that slice of the same call made for the
+ * whole batch. */
+#define DEI2I_DIFFAUG_COLOR 1
+#define DEI2I_DIFFAUG_TRANSLATION 2
+#define DEI2I_DIFFAUG_CUTOUT 4
+#define DEI2I_DIFFAUG_MAX_RUNS 16
+int dei2i_diffaug_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
+                       dei2i_diffaug_rec* tab, dei2i_stream s);
 
 /* ---- spectral normalisation of a conv weight (--use_spectral; torch.nn.utils.spectral_norm semantics, one power
  * iteration per training-mode forward) ----  W = weight_orig as a (Cout, K) fp32 matrix, u (Cout) / v (K) the module's

@@ -1,0 +1,100 @@
+"""defectGAN step time with the recipe options, eager against ``opt.graph_step``, in one process: one JSON line.
+
+Setup: the trainer of ``bench.py``'s defaults (256x256, batch 16, bf16, its synthetic batch and seed) with the given option set,
+once per requested mode.  After the warm-up (which, in graph mode, covers the eager warm-up calls and the capture) ``--steps``
+steps are enqueued back to back with nothing awaited, an event recorded after each: ``ms_per_step`` is the median distance of
+consecutive events (the rate the device finishes steps at, whichever of host and GPU bounds it), ``host_enqueue_ms`` the median
+host time of a ``step()`` call, ``wall_ms_per_step`` the whole timed region divided by the steps.
+
+    python tools/bench_graph_step.py --use-spectral --add-noise --diff-aug color,translation,cutout --diff-aug-rng device \\
+        [--mode eager --mode graph] [--steps 20] [--warmup 8]
+
+``--diff-aug-rng host`` draws DiffAugment's parameters on the host like the reference (graph mode refuses it), ``device`` on the
+GPU (``ops.DiffAugRng``)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+
+
+def run(opts, mode, device):
+    from de_i2i_gan_amd.trainers.defectgan_trainer import DefectGanTrainer
+    opt = bench.make_opt(opts, device)
+    opt.diff_aug = opts.diff_aug
+    if opts.diff_aug_rng is not None:
+        opt.diff_aug_rng = opts.diff_aug_rng
+        opt.diff_aug_seed = opts.diff_aug_seed
+    if mode == "graph":
+        opt.graph_step, opt.graph_warmup = True, 3
+    torch.manual_seed(123)
+    tr = DefectGanTrainer(opt)
+    bg, lab, df = (t.to(device) for t in bench.synthetic_batch(opts.batch, opts.image_size, seed=7))
+    for _ in range(opts.warmup):
+        tr.step(bg, lab, df)
+    torch.cuda.synchronize()
+    events = [torch.cuda.Event(enable_timing=True) for _ in range(opts.steps + 1)]
+    host = []
+    events[0].record()
+    t_start = time.perf_counter()
+    for i in range(opts.steps):
+        t0 = time.perf_counter()
+        tr.step(bg, lab, df)
+        host.append(1e3 * (time.perf_counter() - t0))
+        events[i + 1].record()
+    torch.cuda.synchronize()
+    wall = 1e3 * (time.perf_counter() - t_start) / opts.steps
+    gaps = [events[i].elapsed_time(events[i + 1]) for i in range(opts.steps)]
+    tr.flush_losses()
+    res = {"mode": mode, "ms_per_step": round(statistics.median(gaps), 3), "ms_min": round(min(gaps), 3), "ms_max": round(max(gaps), 3),
+           "wall_ms_per_step": round(wall, 3), "host_enqueue_ms": round(statistics.median(host), 3),
+           "graphs": len(tr._graphs.graphs) if tr._graphs is not None else 0,
+           "d_gan_last": round(tr.losses["gan"]["D"][-1], 6)}
+    tr.release_graphs()
+    del tr
+    torch.cuda.empty_cache()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 20: the figure is a median)")
+    ap.add_argument("--warmup", type=int, default=8, help="untimed steps before them (graph mode: 3 eager calls and the capture are among them)")
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--image-size", type=int, default=256)
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--use-spectral", dest="use_spectral", action="store_true")
+    ap.add_argument("--add-noise", dest="add_noise", action="store_true")
+    ap.add_argument("--diff-aug", dest="diff_aug", default="", metavar="POLICY", help="e.g. color,translation,cutout ('' = none)")
+    ap.add_argument("--diff-aug-rng", dest="diff_aug_rng", default=None, choices=["host", "device"])
+    ap.add_argument("--diff-aug-seed", dest="diff_aug_seed", type=int, default=1234)
+    ap.add_argument("--mode", action="append", default=None, choices=["eager", "graph"], help="repeatable; default: eager, then graph")
+    opts = ap.parse_args()
+    if opts.steps < 20:
+        ap.error("--steps must be >= 20")
+    if opts.warmup < 5:
+        ap.error("--warmup must be >= 5 (graph mode warms up and captures inside it)")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_graph_step.py needs a GPU (the HIP path has no CPU fallback)")
+    torch.cuda.set_device(0)
+    runs = []
+    for mode in (opts.mode or ["eager", "graph"]):
+        res = run(opts, mode, "cuda:0")
+        runs.append(res)
+        print("[bench_graph_step]", json.dumps(res), file=sys.stderr, flush=True)
+    print(json.dumps({"workload": "defectGAN DefectGanTrainer.step", "device": torch.cuda.get_device_name(0), "image_size": opts.image_size,
+                      "batch": opts.batch, "dtype": opts.dtype, "use_spectral": opts.use_spectral, "add_noise": opts.add_noise,
+                      "diff_aug": opts.diff_aug, "diff_aug_rng": opts.diff_aug_rng or "host", "steps": opts.steps,
+                      "warmup": opts.warmup, "runs": runs}))
+
+
+if __name__ == "__main__":
+    main()
