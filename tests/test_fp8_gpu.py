@@ -10,7 +10,8 @@ reference by test_model_gpu.py) -- "parity unpinned by the reference", tolerance
     K = 9*Cin term dot product of independently rounded operands averages that down: measured 3-4 % of the output rms
     against the bf16 kernel on the same bf16 inputs; bound 6 %;
   * the train step (256x256, default widths, reference init): step-1 losses within 3 % of the bf16 mode, full-gradient
-    cosine > 0.97, two steps finite."""
+    cosine > 0.97, two steps finite.
+(The bit-exact checks of the weight pack and of the fp8 kernel on ternary e4m3 data: test_conv_fused_exact_gpu.py.)"""
 from ctypes import byref
 
 import numpy as np

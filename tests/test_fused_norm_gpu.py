@@ -7,7 +7,7 @@
 
 Checked (a) against the oracle's functions in float64 on bf16-rounded operands, and (b) against this build's own unfused
 formulation (ops.fuse_norm = False) on the same inputs, where everything except the position of one bf16 rounding is
-the same arithmetic."""
+the same arithmetic.  (The bit-exact checks of these entry points on dyadic data at their seams: test_conv_fused_exact_gpu.py.)"""
 import math
 
 import pytest
