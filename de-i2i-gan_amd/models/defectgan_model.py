@@ -56,6 +56,19 @@ class DefectGanModel(BaseModel):
             self.diffaug_rng = ops.DiffAugRng(seed, opt.device)
         elif where != "host":
             raise ValueError(f"|diff_aug_rng {where}| is invalid (host | device)")
+        # opt.mask_rng: the same choice for the MAE stage's patch masks ("host": utils/masks.py on the CPU RNG, the reference's masks;
+        # "device": ops.mask_draw on a second generator, seeded by opt.mask_seed), under the same rules.
+        self.mask_rng = None
+        where = getattr(opt, "mask_rng", None) or "host"
+        if where == "device":
+            if torch.device(opt.device).type != "cuda":
+                raise ValueError(f"mask_rng='device' draws on the GPU; opt.device is {opt.device}")
+            seed = getattr(opt, "mask_seed", None)
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            self.mask_rng = ops.DeviceRng(seed, opt.device)
+        elif where != "host":
+            raise ValueError(f"|mask_rng {where}| is invalid (host | device)")
 
     def __call__(self, mode, data, labels, df_data=None, img_only=False, mask=None):
         data, labels = data.to(self.opt.device, non_blocking=True), labels.to(self.opt.device, non_blocking=True)
@@ -132,27 +145,40 @@ class DefectGanModel(BaseModel):
 
     # ---- MAE-GAN pre-training stage (defectgan_model.py:106-171, 361-383) ----------------------------------------
     def _repair_mask(self, imgs, labels, mask=None):
-        """Draw a shifted patch mask (host RNG, like the reference), fill the masked pixels with the mask token and
-        let the generator repair the image."""
+        """Draw a shifted patch mask (host RNG, like the reference; mask_rng 'device': on the GPU, one draw launch and one fused
+        fill launch), fill the masked pixels with the mask token and let the generator repair the image."""
+        filled = None
+        sync = ops.bn_sync.current          # data-parallel with sync_bn: the GLOBAL batch's draw on every rank, this rank's rows of it
         if mask is not None:
             masks = self._upload_mask(mask)
+        elif self.mask_rng is not None:
+            if self.mask_rng.device != imgs.device:
+                raise ValueError(f"mask_rng: the generator lives on {self.mask_rng.device}, the images on {imgs.device}")
+            n, _, h, w = imgs.shape
+            shift, keep = ops.mask_draw(self.mask_rng, n, h, w, self.opt.patch_size, self.opt.mask_ratio,
+                                        row0=sync.rank * n if sync is not None else 0)
+            filled, masks = self.mask_token.fill(imgs if imgs.dtype == torch.float32 else imgs.float(), keep, shift, self.opt.patch_size)
+            self.last_mask = masks          # (for inspection; under graph_step a buffer of the graph that every replay rewrites)
         else:       # the reference's RNG draws on the host (utils/util.py:61-71); the expansion to pixels on the device
-            sync = ops.bn_sync.current          # data-parallel with sync_bn: the GLOBAL batch's draw on every rank, this rank's rows of it
             n, world = imgs.size(0), sync.world if sync is not None else 1
             row0, col0, keep = draw_shifted_mask((n * world,) + tuple(imgs.size()[1:]), self.opt.patch_size, self.opt.mask_ratio)
             if world > 1:
                 keep = keep[sync.rank * n:(sync.rank + 1) * n]
             masks = expand_shifted_mask(self._upload_mask(keep), row0, col0, self.opt.patch_size, imgs.size(2), imgs.size(3))
+        if filled is None:
+            filled = self.mask_token(imgs, masks)
+        # (the tables are dropped and rebuilt on every call, whatever the parameter stamps say: a captured step -- graph_step.py --
+        #  records the same launches an eager one makes)
         self.netG.clear_spade_cache()
         if self.opt.style_norm_block_type == "sean":             # defectgan_model.py:370-372
-            predicted, _ = self.netG(self.mask_token(imgs, masks), labels, self._get_style_embeds(labels))
+            predicted, _ = self.netG(filled, labels, self._get_style_embeds(labels))
         elif self.opt.style_norm_block_type == "adain":          # :377-379
-            predicted, _ = self.netG(self.mask_token(imgs, masks), labels, self.netE(imgs, labels))
+            predicted, _ = self.netG(filled, labels, self.netE(imgs, labels))
         else:
             seg = self._expand_seg(labels)
             if seg.shape[2:] == (1, 1):
                 self.netG.prime_spade((seg,))                # every SPADE module's class table in the batched launches (label_path.hip)
-            predicted, _ = self.netG(self.mask_token(imgs, masks), seg)
+            predicted, _ = self.netG(filled, seg)
         return predicted, masks
 
     def _upload_mask(self, masks):

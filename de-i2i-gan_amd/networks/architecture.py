@@ -700,3 +700,15 @@ class MaskToken(nn.Module):
             mean = kept.mean(dim=(2, 3)) / self.mask_ratio
             token = self.mask_token = mean.reshape(mean.size(0), mean.size(1), 1, 1)
         return kept + token * (1 - masks)
+
+    def fill(self, imgs, keep, shift, patch):
+        """``forward`` on a device-side patch mask (ops.mask_draw's keep bits and shifts): -> (filled, masks), the same values as
+        ``forward(imgs, masks)`` with ``masks = expand_shifted_mask(keep, *shift, patch, H, W)``, the expansion and the fill in one
+        launch (csrc/mask.hip; the token's gradient in one more).  'mean' takes the kernel's zero fill and pixel mask and then
+        ``forward``'s own ops on them, all on the device."""
+        if self.mask_token_type == "mean":
+            kept, masks = ops.mask_fill(imgs, keep, shift, patch)
+            mean = kept.mean(dim=(2, 3)) / self.mask_ratio
+            self.mask_token = mean.reshape(mean.size(0), mean.size(1), 1, 1)
+            return kept + self.mask_token * (1 - masks), masks
+        return ops.mask_fill(imgs, keep, shift, patch, token=None if self.mask_token_type == "zero" else self.mask_token)

@@ -6,7 +6,8 @@ parameters, gradients, state_dict), as in the reference.  Every op requires a GP
 
 Random numbers: ``NoiseInjection`` draws with torch's device RNG; ``diff_augment`` draws its per-sample parameters from the global
 CPU RNG and uploads them (the reference's draws), or, given a ``DiffAugRng``, on the device from a counter-based generator whose
-call count lives in device memory -- the form a captured graph can replay.
+call count lives in device memory -- the form a captured graph can replay.  The MAE stage's patch masks have the same two sources
+(utils/masks.py on the host; ``mask_draw`` with a ``DeviceRng`` of its own).
 """
 from __future__ import annotations
 
@@ -1964,14 +1965,15 @@ class diffaug_sharded:
 # dei2i_diffaug_draw): the seed travels in the kernel arguments, the call count is one word of device memory that every draw launch
 # advances itself, and a record is a pure function of (seed, call, run, global row) -- an eager call and a replay of its capture
 # draw the same table, every replay a new one, and a rank's rows are the slice of the global batch's table without any broadcast.
-class DiffAugRng:
-    """The seed and the device call counter of ``diff_augment(..., rng=...)``.  The counter is allocated here, outside any capture,
-    and must outlive every graph that recorded a draw on it.  ``state()`` / ``set_state()`` synchronise: not for use inside a step."""
+class DeviceRng:
+    """The seed and the device call counter of ``diff_augment(..., rng=...)`` and of ``mask_draw`` (one instance each: a draw launch
+    of either advances its own counter).  The counter is allocated here, outside any capture, and must outlive every graph that
+    recorded a draw on it.  ``state()`` / ``set_state()`` synchronise: not for use inside a step."""
 
     def __init__(self, seed: int, device):
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise ValueError(f"DiffAugRng draws on the GPU; device {self.device} is not one (there is no CPU fallback)")
+            raise ValueError(f"DeviceRng draws on the GPU; device {self.device} is not one (there is no CPU fallback)")
         self.seed = int(seed) & (2 ** 64 - 1)
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)      # (the bits of one unsigned 64-bit word)
         self.device = self.counter.device                    # (with its index)
@@ -1987,6 +1989,9 @@ class DiffAugRng:
         torch.cuda.synchronize(self.device)                  # (draws queued on any stream read the old count)
         self.counter.fill_(calls - 2 ** 64 if calls >= 2 ** 63 else calls)
         torch.cuda.synchronize(self.device)
+
+
+DiffAugRng = DeviceRng          # (the name it was introduced under)
 
 
 def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0):
@@ -2035,6 +2040,100 @@ def diff_augment(x, policy="", rng=None):
     for i, run in enumerate(runs):
         x = _DiffAug.apply(x, tab[i], run, 0, host)
     return x
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Device-drawn shifted patch masks of the MAE stage and the mask-token fill (csrc/mask.hip).  utils/masks.py draws the row shift,
+# the column shift and the per-patch keep bits from the CPU RNG and uploads them; ``mask_draw`` draws them on the device from a
+# ``DeviceRng`` instead (the counter-word layout: include/dei2i_hip.h) and ``mask_fill`` expands and applies them in one launch that
+# reads the shifts from device memory -- both can be captured into a graph, and every replay masks other patches.
+# --------------------------------------------------------------------------------------------------------------
+def mask_draw(rng: DeviceRng, n, h, w, patch, mask_ratio, row0=0):
+    """One dei2i_mask_draw launch on the current stream: -> (shift, keep), ``shift`` a device int32 (2,) tensor (row shift, column
+    shift, each in [0, patch)), ``keep`` a device uint8 (n, 1, h/patch + 1, w/patch + 1) tensor (1 = patch kept, with probability
+    1 - mask_ratio) for global rows [row0, row0 + n).  Nothing is read from the host RNG and nothing is uploaded."""
+    n, h, w, patch = int(n), int(h), int(w), int(patch)
+    if patch <= 0 or h % patch or w % patch:
+        raise ValueError(f"mask_draw: {h}x{w} is not a whole number of {patch}x{patch} patches")
+    gh, gw = h // patch + 1, w // patch + 1
+    shift = torch.empty(2, dtype=torch.int32, device=rng.device)
+    keep = torch.empty((n, 1, gh, gw), dtype=torch.uint8, device=rng.device)
+    lib = _lib_for(keep)
+    L.check(lib.dei2i_mask_draw(rng.seed, _p(rng.counter), n, int(row0), gh, gw, patch, 1.0 - float(mask_ratio), _p(shift), _p(keep),
+                                _stream()), "mask_draw")
+    return shift, keep
+
+
+def _mask_geometry(imgs, keep, shift, patch, what):
+    if not imgs.is_cuda:
+        raise ValueError(f"{what}: the images are on {imgs.device}; the HIP kernels need a GPU tensor (there is no CPU fallback)")
+    if imgs.dim() != 4 or imgs.dtype != torch.float32:
+        raise TypeError(f"{what} expects an NCHW fp32 image batch")
+    n, _, h, w = imgs.shape
+    patch = int(patch)
+    if patch <= 0 or h % patch or w % patch:
+        raise ValueError(f"{what}: {h}x{w} is not a whole number of {patch}x{patch} patches")
+    if keep.device != imgs.device or shift.device != imgs.device:
+        raise ValueError(f"{what}: keep is on {keep.device}, shift on {shift.device}, the images on {imgs.device}")
+    if keep.dtype != torch.uint8 or tuple(keep.shape) != (n, 1, h // patch + 1, w // patch + 1):
+        raise ValueError(f"{what}: keep must be uint8 {(n, 1, h // patch + 1, w // patch + 1)}, not {keep.dtype} {tuple(keep.shape)}")
+    if shift.dtype != torch.int32 or tuple(shift.shape) != (2,):
+        raise ValueError(f"{what}: shift must be int32 (2,), not {shift.dtype} {tuple(shift.shape)}")
+    return patch
+
+
+class _MaskFill(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, imgs, token, keep, shift, patch):
+        imgs, keep, shift = imgs.contiguous(), keep.contiguous(), shift.contiguous()
+        n, c, h, w = imgs.shape
+        filled = torch.empty_like(imgs)
+        mask = torch.empty((n, 1, h, w), dtype=torch.float32, device=imgs.device)
+        strides = None
+        if token is not None:
+            view = token.detach().expand(n, c, h, w)       # (stride 0 on every broadcast dim)
+            strides = (ctypes.c_int64 * 4)(*view.stride())
+        lib = _lib_for(imgs)
+        L.check(lib.dei2i_mask_fill(n, c, h, w, patch, _p(shift), _p(keep), _p(imgs), _p(token), strides, _p(filled), _p(mask),
+                                    _stream()), "mask_fill")
+        ctx.keep, ctx.shift, ctx.patch = keep, shift, patch
+        ctx.token_shape = None if token is None else tuple(token.shape)
+        ctx.save_for_backward(mask)
+        ctx.mark_non_differentiable(mask)
+        return filled, mask
+
+    @staticmethod
+    def backward(ctx, g, _g_mask):
+        g_imgs = g_token = None
+        if ctx.needs_input_grad[0]:            # (the images are data: nothing on the hot path asks)
+            g_imgs = g * ctx.saved_tensors[0]
+        if ctx.token_shape is not None and ctx.needs_input_grad[1]:
+            g = g.contiguous()
+            n, c, h, w = g.shape
+            full = torch.empty((1, c, h, w), dtype=torch.float32, device=g.device)
+            lib = _lib_for(g)
+            L.check(lib.dei2i_mask_fill_bwd(n, c, h, w, ctx.patch, _p(ctx.shift), _p(ctx.keep), _p(g), _p(full), _stream()),
+                    "mask_fill_bwd")
+            shape = (1,) * (4 - len(ctx.token_shape)) + ctx.token_shape
+            dims = [d for d in range(1, 4) if shape[d] == 1 and full.shape[d] != 1]
+            g_token = (torch.sum(full, dim=dims, keepdim=True) if dims else full).reshape(ctx.token_shape)
+        return g_imgs, g_token, None, None, None
+
+
+def mask_fill(imgs, keep, shift, patch, token=None):
+    """``MaskToken`` on a device-side patch mask in one launch: -> (filled, mask), ``mask`` the (N,1,H,W) fp32 pixel mask
+    ``utils.masks.expand_shifted_mask(keep, shift[0], shift[1], patch, H, W)`` and ``filled = imgs`` where it is 1, ``token`` (a
+    tensor that broadcasts to one image (1,C,H,W); None: zero) where it is 0.  ``keep`` (N,1,H/patch+1,W/patch+1) uint8 and ``shift``
+    (2,) int32 are plain device tensors (``mask_draw`` makes them; the shifts are read on the device).  Differentiable in ``token``
+    (deterministic: the batch is summed in ascending order) and, with a torch op, in ``imgs``."""
+    patch = _mask_geometry(imgs, keep, shift, patch, "mask_fill")
+    if token is not None:
+        if token.device != imgs.device or token.dtype != torch.float32:
+            raise ValueError(f"mask_fill: the token is {token.dtype} on {token.device}, the images fp32 on {imgs.device}")
+        if token.dim() > 4 or (token.dim() == 4 and token.shape[0] != 1):
+            raise ValueError(f"mask_fill: a token of shape {tuple(token.shape)} does not broadcast to one image")
+        torch.broadcast_shapes(tuple(token.shape), (1,) + tuple(imgs.shape[1:]))       # (raises when it does not)
+    return _MaskFill.apply(imgs, token, keep, shift, patch)
 
 
 # --------------------------------------------------------------------------------------------------------------

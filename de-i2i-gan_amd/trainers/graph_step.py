@@ -1,7 +1,8 @@
-"""``opt.graph_step``: the defectGAN D step, and the D step + G step, replayed from captured HIP graphs.
+"""``opt.graph_step``: the D step, and the D step + G step, of the defectGAN stage and of the MAE pre-training stage replayed from
+captured HIP graphs.
 
 The eager step enqueues ~750 kernels through ~2 000 autograd-Function applies; the host, not the GPU, bounds it.  In graph mode
-``DefectGanTrainer.step`` runs eagerly for ``opt.graph_warmup`` calls (on the stream the capture will use, so every workspace
+the trainer's ``step`` runs eagerly for ``opt.graph_warmup`` calls (on the stream the capture will use, so every workspace
 exists before the capture), then captures the graph the iteration needs -- D only, or D + G (``num_critics > 1`` replays both)
 -- and from then on copies the inputs into static device buffers, replays, and does the host bookkeeping the replay cannot:
 ``iters``, each optimizer's ``state["step"]`` and the rows of its device hyper-parameter table (optim.FusedAdam), the
@@ -13,7 +14,9 @@ What the capture cannot honour raises ``NotImplementedError`` (``unsupported``).
 
 ``opt.diff_aug`` is captured when its parameters are drawn on the device (``opt.diff_aug_rng = "device"``: ops.DiffAugRng, whose
 call counter lives in device memory and advances inside the draw launch, so every replay draws what the eager call would have
-drawn); with host draws, which a capture would freeze into every replay, it is refused."""
+drawn); with host draws, which a capture would freeze into every replay, it is refused.  The MAE stage's patch masks follow the
+same rule (``opt.mask_rng = "device"``: ops.mask_draw / ops.mask_fill; host-drawn masks are refused), and so does its
+``opt.grad_scaler``, whose overflow check reads the device once per update."""
 import torch
 
 from .. import ops
@@ -35,6 +38,12 @@ def capture_stream(device):
 def unsupported(trainer):
     """-> the first option the captured step cannot honour (None: all supported)"""
     opt = trainer.opt
+    if getattr(trainer, "draws_masks", False) and getattr(trainer.model, "mask_rng", None) is None:
+        return ("MAETrainer with host-drawn masks (its masks are made on the host and uploaded per update; build the trainer with "
+                "mask_rng='device' to draw them on the GPU)")
+    scaler = getattr(trainer, "scaler", None)
+    if scaler is not None and scaler.is_enabled():
+        return "grad_scaler=True (its overflow check is a host sync per update)"
     if getattr(opt, "diff_aug", "") and getattr(trainer.model, "diffaug_rng", None) is None:
         return ("diff_aug with host draws (its parameters are drawn from the CPU RNG and uploaded per call; build the trainer with "
                 "diff_aug_rng='device' to draw them on the GPU)")
@@ -66,7 +75,7 @@ class GraphStep:
         self.tr = trainer
         self.calls = 0                   # graph-mode calls since the last release (the first graph_warmup of them are eager)
         self.graphs = {}                 # with_g -> _Captured
-        self.sig = None                  # (shape, dtype, device) of the three inputs the graphs were captured for
+        self.sig = None                  # (shape, dtype, device) of the step's inputs the graphs were captured for
         self.static = None               # their device buffers
         self.stamp = None                # (model load serial, compute_dtype) at capture
 
@@ -81,14 +90,14 @@ class GraphStep:
         return (getattr(self.tr.model, "load_serial", 0), getattr(self.tr.opt, "compute_dtype", "bf16"))
 
     # ---- the step ------------------------------------------------------------------------------------------------------
-    def step(self, bg_data, df_labels, df_data):
+    def step(self, *inputs):
+        """``inputs``: the trainer's own ``step`` arguments (three tensors for the defectGAN stage, two for the MAE stage)"""
         tr = self.tr
         why = unsupported(tr)
         if why is not None:
             raise NotImplementedError(f"graph_step does not support {why}")
         if self.stamp is not None and self.stamp != self._stamp():
             self.release()
-        inputs = (bg_data, df_labels, df_data)
         sig = tuple((tuple(t.shape), t.dtype, t.device) for t in inputs)
         if self.calls < int(getattr(tr.opt, "graph_warmup", 3)):
             self.calls += 1
@@ -137,6 +146,12 @@ class GraphStep:
             self.tr._eager_step(*inputs)
         cur.wait_stream(st)
 
+    def _trained_modules(self):
+        """the networks, and the MAE stage's mask token (a module of the model that is no network: the G optimizer trains it)"""
+        model = self.tr.model
+        token = getattr(model, "mask_token", None)
+        return list(model.networks.values()) + ([token] if isinstance(token, torch.nn.Module) else [])
+
     def _capture(self, with_g):
         """Record one D (+ G) step on the static inputs.  Every decision the host takes while recording is frozen into the graph,
         so the recording must take the decisions every replay needs: every packed weight copy is rebuilt (all stamps moved),
@@ -146,7 +161,7 @@ class GraphStep:
         for o in tr.optimizers.values():
             o.graph_take_plan()
             o.graph_reserve()
-        for net in tr.model.networks.values():
+        for net in self._trained_modules():
             for p in net.parameters():
                 p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1
         if hasattr(tr.model, "_label_sets"):
@@ -169,5 +184,5 @@ class GraphStep:
         keep += [w for w in ops._workspaces.values() if all(w is not k for k in keep)]
         plans = {name: o.graph_take_plan() for name, o in tr.optimizers.items()}
         plans = {name: plan for name, plan in plans.items() if plan}
-        grads = [(p, p.grad) for net in tr.model.networks.values() for p in net.parameters()]
+        grads = [(p, p.grad) for net in self._trained_modules() for p in net.parameters()]
         return _Captured(graph, with_g, plans, grads, keys, losses, keep)

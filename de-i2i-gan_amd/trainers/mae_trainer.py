@@ -21,6 +21,8 @@ from .base_trainer import BaseTrainer
 
 
 class MAETrainer(BaseTrainer):
+    draws_masks = True           # every update draws a patch mask (graph_step captures it only when opt.mask_rng = "device")
+
     def __init__(self, opt, data_types=("fusion",)):
         super().__init__(opt)
         assert len(opt.loss_weight) == 3, f"length of loss weights must be 3, not {len(opt.loss_weight)}"
@@ -80,9 +82,18 @@ class MAETrainer(BaseTrainer):
         self._record([("gan", "D"), ("clf", "D")], [gan_loss, clf_loss])
 
     def step(self, data, labels):
-        """One iteration of the reference's loop (mae_trainer.py:92-99)."""
+        """One iteration of the reference's loop (mae_trainer.py:92-99).  ``opt.graph_step``: replayed from a captured graph after
+        ``opt.graph_warmup`` eager calls (trainers/graph_step.py); that needs device-drawn masks (``opt.mask_rng = "device"``) and
+        refuses ``opt.grad_scaler``."""
         if self.graph_step:
-            raise NotImplementedError("graph_step does not support MAETrainer (its masks are made on the host and uploaded per update)")
+            if self._graphs is None:
+                from .graph_step import GraphStep
+                self._graphs = GraphStep(self)
+            self._graphs.step(data, labels)
+            return
+        self._eager_step(data, labels)
+
+    def _eager_step(self, data, labels):
         self.iters += 1
         self._train_discriminator_once(data, labels)
         if self.iters % self.opt.num_critics == 0:

@@ -298,6 +298,32 @@ int dei2i_diffaug(int mode, int N, int C, int H, int W, int ch, int cw, int colo
 int dei2i_diffaug_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
                        dei2i_diffaug_rec* tab, dei2i_stream s);
 
+/* ---- device-drawn shifted patch masks of the MAE stage (utils/masks.py) and the mask-token fill (csrc/mask.hip) ----
+ * The patch grid of an H x W image is GH x GW = (H / patch + 1) x (W / patch + 1) (H, W multiples of patch); pixel (i, j) of row n
+ * is kept when keep[n][(i + rs) / patch][(j + cs) / patch] != 0, (rs, cs) = shift[0], shift[1] in [0, patch).
+ *
+ * dei2i_mask_draw fills shift_dev[2] (int32) and keep_dev[N * GH * GW] (one byte per patch, 1 = kept) for global rows
+ * [row0, row0 + N) from Philox4x32-10: key = seed, counter words = (call low 32, call high 32, c2, c3), call = *counter_dev as the
+ * launch finds it.  Shifts: c2 = 0xC0000000, c3 = 0, rs = mulhi(x0, patch), cs = mulhi(x1, patch) -- the same for every row.
+ * Keep bits: patch t = gi * GW + gj of row n takes word x[t % 4] of c2 = 0x80000000 | t / 4, c3 = row0 + n;
+ * kept = (x >> 8) * 2^-24 < keep_prob (keep_prob = 1 - mask_ratio as fp32).  Bit 31 of c2 keeps these streams apart from
+ * dei2i_diffaug_draw's (run | block << 16) under a shared seed.  One launch of one workgroup; it leaves *counter_dev greater by
+ * exactly 1 (the ordering rule of dei2i_diffaug_draw holds).  BAD_ARG: null pointers, N, GH, GW, patch <= 0, row0 < 0,
+ * row0 + N > 2^31, GH * GW >= 2^26, keep_prob outside [0, 1].
+ *
+ * dei2i_mask_fill: filled[n,c,i,j] = kept ? imgs[n,c,i,j] : token[n*ts[0] + c*ts[1] + i*ts[2] + j*ts[3]] on fp32 NCHW; the token is
+ * addressed by element strides (0 on a broadcast dim), a null token fills with 0.  mask_out (nullable) receives the (N,1,H,W) fp32
+ * mask.  The shifts are read from device memory; a patch index they carry off the grid is clamped to it.
+ *
+ * dei2i_mask_fill_bwd: grad_full[c,i,j] (C * H * W floats) = sum over n, in ascending order, of grad_out[n,c,i,j] at the masked
+ * pixels: the token's gradient before its reduction over the token's broadcast dims.  Deterministic (no atomics). */
+int dei2i_mask_draw(uint64_t seed, uint64_t* counter_dev, int N, int row0, int GH, int GW, int patch, float keep_prob,
+                    int* shift_dev, unsigned char* keep_dev, dei2i_stream s);
+int dei2i_mask_fill(int N, int C, int H, int W, int patch, const int* shift_dev, const unsigned char* keep_dev, const float* imgs,
+                    const float* token, const int64_t* token_strides, float* filled, float* mask_out, dei2i_stream s);
+int dei2i_mask_fill_bwd(int N, int C, int H, int W, int patch, const int* shift_dev, const unsigned char* keep_dev,
+                        const float* grad_out, float* grad_full, dei2i_stream s);
+
 /* ---- spectral normalisation of a conv weight (--use_spectral; torch.nn.utils.spectral_norm semantics, one power
  * iteration per training-mode forward) ----  W = weight_orig as a (Cout, K) fp32 matrix, u (Cout) / v (K) the module's
  * buffers (updated in place when iterate != 0); u_used / v_used receive the vectors sigma was computed with (the backward

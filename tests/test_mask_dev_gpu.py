@@ -1,0 +1,318 @@
+"""Device-drawn patch masks and the fused mask-token fill (csrc/mask.hip: dei2i_mask_draw, dei2i_mask_fill, dei2i_mask_fill_bwd;
+ops.mask_draw, ops.mask_fill, MaskToken.fill).
+
+Everything is compared bit for bit; nothing needs a tolerance.  The draw is checked against a numpy Philox4x32-10 written from the
+counter-word layout of include/dei2i_hip.h (its only float arithmetic, (x >> 8) * 2^-24 < keep_prob, is exact in fp32), the fill
+against ``MaskToken.forward`` on ``expand_shifted_mask`` of the same hand-made keep bits and shifts (kept pixels are x * 1 + t * 0,
+masked ones x * 0 + t * 1: no rounding), the token gradient against a float64 sum of integer-valued gradients (|g| <= 8, N <= 3:
+every fp32 partial sum is an exact integer far below 2^24)."""
+import ctypes
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import make_opt
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SEED = 0x5DEECE66D1234567
+BAD_ARG = -2                       # include/dei2i_hip.h: DEI2I_ERR_BAD_ARG
+M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+LOW = np.uint64(0xFFFFFFFF)
+
+
+# ---- the reference ---------------------------------------------------------------------------------------------------------
+def philox4x32_10(ctr, key):
+    """ctr: four uint32 arrays (or scalars), key: two uint32 scalars -> four uint32 arrays (Salmon et al. 2011)"""
+    c = list(np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) & LOW for v in ctr]))
+    k0, k1 = np.uint64(key[0]), np.uint64(key[1])
+    for _ in range(10):
+        p0, p1 = np.uint64(M0) * c[0], np.uint64(M1) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & LOW, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & LOW]
+        k0, k1 = (k0 + np.uint64(W0)) & LOW, (k1 + np.uint64(W1)) & LOW
+    return [v.astype(np.uint32) for v in c]
+
+
+def draw_reference(seed, call, n, row0, h, w, patch, mask_ratio):
+    """-> (shift int32 (2,), keep uint8 (n, 1, GH, GW)) as include/dei2i_hip.h lays the counter words out"""
+    key = (seed & 0xFFFFFFFF, seed >> 32)
+    c0, c1 = call & 0xFFFFFFFF, call >> 32
+    x = philox4x32_10((c0, c1, 0xC0000000, 0), key)
+    shift = np.array([(int(x[0]) * patch) >> 32, (int(x[1]) * patch) >> 32], dtype=np.int32)
+    gh, gw = h // patch + 1, w // patch + 1
+    t = np.arange(gh * gw, dtype=np.uint64)
+    rows = np.arange(row0, row0 + n, dtype=np.uint64)
+    words = np.stack(philox4x32_10((c0, c1, np.uint64(0x80000000) | (t[None, :] // np.uint64(4)), rows[:, None]), key), -1)   # (n, P, 4)
+    word = np.take_along_axis(words, (t % np.uint64(4)).astype(np.int64)[None, :, None].repeat(n, 0), -1)[..., 0]
+    unit = (word >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    keep = (unit < np.float32(1.0 - mask_ratio)).astype(np.uint8)
+    return shift, keep.reshape(n, 1, gh, gw)
+
+
+def test_reference_philox_reproduces_a_random123_known_answer():
+    got = philox4x32_10((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0))
+    assert tuple(int(v) for v in got) == (0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1)
+
+
+# ---- 1. the draw -----------------------------------------------------------------------------------------------------------
+SHAPES = [(1, 8, 8, 8), (3, 12, 20, 4), (2, 9, 9, 1), (5, 64, 64, 8), (300, 8, 8, 4)]
+
+
+def _same(got, want):
+    shift, keep = got
+    assert shift.dtype == torch.int32 and keep.dtype == torch.uint8 and tuple(keep.shape) == want[1].shape
+    assert torch.equal(shift.cpu(), torch.from_numpy(want[0])), (shift.tolist(), want[0].tolist())
+    assert torch.equal(keep.cpu(), torch.from_numpy(want[1]))
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_draw_matches_the_numpy_reference_and_counts_one_per_launch(shape):
+    from de_i2i_gan_amd import ops
+    n, h, w, patch = shape
+    rng = ops.DeviceRng(SEED, DEV)
+    first = ops.mask_draw(rng, n, h, w, patch, 0.75)
+    assert rng.state() == (SEED, 1)
+    second = ops.mask_draw(rng, n, h, w, patch, 0.75)
+    assert rng.state() == (SEED, 2)
+    _same(first, draw_reference(SEED, 0, n, 0, h, w, patch, 0.75))
+    _same(second, draw_reference(SEED, 1, n, 0, h, w, patch, 0.75))
+    assert not torch.equal(first[1], second[1])
+    assert 0 <= int(first[0].min()) and int(first[0].max()) < patch
+    rng.set_state((SEED, 2 ** 32 - 1))                    # the next launch carries into the high counter word
+    _same(ops.mask_draw(rng, n, h, w, patch, 0.75), draw_reference(SEED, 2 ** 32 - 1, n, 0, h, w, patch, 0.75))
+    assert rng.state() == (SEED, 2 ** 32)
+    _same(ops.mask_draw(rng, n, h, w, patch, 0.75), draw_reference(SEED, 2 ** 32, n, 0, h, w, patch, 0.75))
+    for ratio, value in ((0.0, 1), (1.0, 0)):            # all kept, none kept
+        shift, keep = ops.mask_draw(rng, n, h, w, patch, ratio)
+        assert bool((keep == value).all())
+    assert rng.state() == (SEED, 2 ** 32 + 3)
+
+
+def test_rows_are_a_slice_of_the_whole_batch():
+    from de_i2i_gan_amd import ops
+    rng = ops.DeviceRng(SEED, DEV)
+    rng.set_state((SEED, 7))
+    shift, whole = ops.mask_draw(rng, 5, 64, 64, 8, 0.75)
+    rng.set_state((SEED, 7))
+    part_shift, part = ops.mask_draw(rng, 3, 64, 64, 8, 0.75, row0=2)
+    assert torch.equal(part, whole[2:5]) and torch.equal(part_shift, shift)
+    _same((part_shift, part), draw_reference(SEED, 7, 3, 2, 64, 64, 8, 0.75))
+    assert 0.15 < whole.float().mean().item() < 0.35      # 405 Bernoulli(0.25) patches: 4.6 sigma either way
+
+
+# ---- 2. the fill -----------------------------------------------------------------------------------------------------------
+S, C = 16, 3                          # MaskToken's position / full tokens are image_size x image_size
+FILL = [(n, S, w, p) for n in (1, 3) for w, p in ((20, 4), (18, 2))]      # W = 20: the float4 path; W = 18: the scalar path
+KINDS = ["zero", "scalar", "vector", "position", "full"]
+
+
+def _token(kind, h, w):
+    """a token of the kind's shape (MaskToken.SHAPES, at h x w) with non-zero values, distinct per element"""
+    shape = {"scalar": (1, 1, 1, 1), "vector": (1, C, 1, 1), "position": (1, 1, h, w), "full": (1, C, h, w)}[kind]
+    count = int(np.prod(shape))
+    return (torch.arange(1, count + 1, dtype=torch.float32) / 8 + 100).reshape(shape).to(DEV)
+
+
+def _keep_cases(n, h, w, p):
+    gh, gw = h // p + 1, w // p + 1
+    g = torch.Generator().manual_seed(5)
+    return {"random": (torch.rand(n, 1, gh, gw, generator=g) < 0.4).to(torch.uint8).to(DEV),
+            "all_kept": torch.ones(n, 1, gh, gw, dtype=torch.uint8, device=DEV),
+            "all_masked": torch.zeros(n, 1, gh, gw, dtype=torch.uint8, device=DEV)}
+
+
+def _images(n, h, w, offset):
+    """(n, C, h, w) fp32; offset: the storage starts one float past an aligned address, so the float4 path must be refused"""
+    g = torch.Generator().manual_seed(9)
+    flat = (torch.rand(n * C * h * w + 1, generator=g) * 2 - 1).to(DEV)
+    return flat[1:].view(n, C, h, w) if offset else flat[:-1].view(n, C, h, w)
+
+
+def _reference_fill(kind, imgs, keep, shift, p, token):
+    from de_i2i_gan_amd.networks.architecture import MaskToken
+    from de_i2i_gan_amd.utils.masks import expand_shifted_mask
+    h, w = imgs.shape[2:]
+    masks = expand_shifted_mask(keep.float(), shift[0], shift[1], p, h, w)
+    mt = MaskToken.__new__(MaskToken)
+    torch.nn.Module.__init__(mt)
+    mt.mask_token_type, mt.mask_ratio, mt.mask_token = kind, 0.75, 0 if token is None else token
+    return mt.forward(imgs, masks), masks
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape", FILL, ids=lambda s: "x".join(map(str, s)))
+def test_fill_equals_mask_token_on_the_expanded_mask(shape, kind):
+    from de_i2i_gan_amd import ops
+    n, h, w, p = shape
+    token = None if kind == "zero" else _token(kind, h, w)
+    for offset in (False, True):
+        imgs = _images(n, h, w, offset)
+        assert (imgs.data_ptr() % 16 != 0) == offset
+        for name, keep in _keep_cases(n, h, w, p).items():
+            for shift in ((0, 0), (p - 1, p - 1), (0, p - 1)):
+                want, want_mask = _reference_fill(kind, imgs, keep, shift, p, token)
+                filled, mask = ops.mask_fill(imgs, keep, torch.tensor(shift, dtype=torch.int32, device=DEV), p, token=token)
+                assert torch.equal(mask, want_mask), (name, shift, offset)
+                assert torch.equal(filled, want), (name, shift, offset)
+                if name == "all_kept":
+                    assert torch.equal(filled, imgs)
+                if name == "all_masked" and token is not None:
+                    assert torch.equal(filled, token.expand_as(imgs))
+
+
+def _mae_model(kind, dtype="f32", **over):
+    from de_i2i_gan_amd.models.defectgan_model import DefectGanModel
+    c = dict(image_size=32, batch=3, num_layers=3, ngf=8, ndf=8, hidden_nc=16)
+    return DefectGanModel(make_opt(c, DEV, dtype, mask_token_type=kind, mask_ratio=0.75, patch_size=4, mask_rng="device", mask_seed=99,
+                                   **over))
+
+
+def test_mean_token_through_the_module_equals_forward():
+    """'mean' takes the kernel's zero fill and pixel mask, then MaskToken.forward's own ops"""
+    model = _mae_model("mean")
+    imgs = _images(3, 32, 32, False)
+    for name, keep in _keep_cases(3, 32, 32, 4).items():
+        for shift in ((0, 0), (3, 3), (0, 3)):
+            want, want_mask = _reference_fill("mean", imgs, keep, shift, 4, None)
+            filled, mask = model.mask_token.fill(imgs, keep, torch.tensor(shift, dtype=torch.int32, device=DEV), 4)
+            assert torch.equal(mask, want_mask) and torch.equal(filled, want), (name, shift)
+
+
+def test_model_path_draws_once_and_fills_what_the_reference_ops_give():
+    """DefectGanModel._repair_mask with mask_rng='device': one draw per call, the generator sees MaskToken.forward's image"""
+    from de_i2i_gan_amd import ops
+    model = _mae_model("position")
+    with torch.no_grad():
+        model.mask_token.mask_token.copy_(_token("position", 32, 32))
+    imgs = _images(3, 32, 32, False)
+    labels = torch.eye(6, device=DEV)[[1, 2, 3]]
+    seen = []
+    model.netG.register_forward_pre_hook(lambda mod, args: seen.append(args[0].detach().clone()))
+    host_state = torch.get_rng_state()
+    model.netG.eval()
+    with torch.no_grad():
+        _, masks = model._repair_mask(imgs, labels)
+    assert torch.equal(torch.get_rng_state(), host_state) and model.mask_rng.state() == (99, 1)
+    shift, keep = draw_reference(99, 0, 3, 0, 32, 32, 4, 0.75)
+    want, want_mask = _reference_fill("position", imgs, torch.from_numpy(keep).to(DEV), shift.tolist(), 4, model.mask_token.mask_token)
+    assert torch.equal(masks, want_mask) and torch.equal(model.last_mask, want_mask)
+    assert len(seen) == 1 and torch.equal(seen[0], want)
+    other = ops.DeviceRng(99, DEV)
+    assert torch.equal(ops.mask_draw(other, 3, 32, 32, 4, 0.75)[1].cpu(), torch.from_numpy(keep))
+
+
+# ---- 3. the token gradient -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS[1:])
+@pytest.mark.parametrize("shape", FILL, ids=lambda s: "x".join(map(str, s)))
+def test_token_gradient_is_exact_on_integers_and_repeatable(shape, kind):
+    from de_i2i_gan_amd import ops
+    from de_i2i_gan_amd.utils.masks import expand_shifted_mask
+    n, h, w, p = shape
+    g = torch.Generator().manual_seed(3)
+    flat = torch.randint(-8, 9, (n * C * h * w + 1,), generator=g).float().to(DEV)
+    for offset in (False, True):
+        imgs = _images(n, h, w, offset)
+        grad_out = flat[1:].view(n, C, h, w) if offset else flat[:-1].view(n, C, h, w)
+        for name, keep in _keep_cases(n, h, w, p).items():
+            for shift in ((0, 0), (p - 1, p - 1), (0, p - 1)):
+                masks = expand_shifted_mask(keep.float(), shift[0], shift[1], p, h, w)
+                full = (grad_out.double() * (1 - masks.double())).sum(0, keepdim=True)
+                token = _token(kind, h, w)
+                dims = [d for d in (1, 2, 3) if token.shape[d] == 1]
+                want = (full.sum(dim=dims, keepdim=True) if dims else full).float()
+                got = []
+                for _ in range(2):
+                    t = token.clone().requires_grad_(True)
+                    filled, _ = ops.mask_fill(imgs, keep, torch.tensor(shift, dtype=torch.int32, device=DEV), p, token=t)
+                    filled.backward(grad_out)
+                    got.append(t.grad)
+                assert got[0].shape == token.shape and torch.equal(got[0], want), (name, shift, offset)
+                assert torch.equal(got[0], got[1])
+                if name == "all_kept":
+                    assert not got[0].any()
+
+
+def test_image_gradient_is_the_masked_gradient():
+    from de_i2i_gan_amd import ops
+    imgs = _images(3, S, 20, False).clone().requires_grad_(True)
+    keep = _keep_cases(3, S, 20, 4)["random"]
+    filled, mask = ops.mask_fill(imgs, keep, torch.tensor([1, 2], dtype=torch.int32, device=DEV), 4, token=_token("vector", S, 20))
+    grad_out = torch.ones_like(filled) * 3
+    filled.backward(grad_out)
+    assert torch.equal(imgs.grad, grad_out * mask) and not mask.requires_grad
+
+
+# ---- 4. refusals -----------------------------------------------------------------------------------------------------------
+def test_bad_arguments_are_refused():
+    from de_i2i_gan_amd import ops
+    rng = ops.DeviceRng(SEED, DEV)
+    shift = torch.zeros(2, dtype=torch.int32, device=DEV)
+    keep = torch.ones(2, 1, 3, 3, dtype=torch.uint8, device=DEV)
+    imgs = torch.zeros(2, 3, 8, 8, device=DEV)
+    out = torch.empty_like(imgs)
+    lib = ops._lib_for(imgs)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    st = ops._stream()
+
+    def draw(counter=p(rng.counter), n=2, row0=0, gh=3, gw=3, patch=4, prob=0.25, sh=p(shift), kp=p(keep)):
+        return lib.dei2i_mask_draw(SEED, counter, n, row0, gh, gw, patch, prob, sh, kp, st)
+
+    assert draw() == 0
+    for bad in (dict(counter=None), dict(sh=None), dict(kp=None), dict(n=0), dict(row0=-1), dict(gh=0), dict(gw=0), dict(patch=0),
+                dict(prob=-0.5), dict(prob=1.5), dict(prob=float("nan")), dict(n=2, row0=2 ** 31 - 1), dict(gh=2 ** 13, gw=2 ** 13)):
+        assert draw(**bad) == BAD_ARG, bad
+    assert rng.state() == (SEED, 1)                       # the refused calls launched nothing
+
+    def fill(n=2, c=3, h=8, w=8, patch=4, sh=p(shift), kp=p(keep), src=p(imgs), dst=p(out)):
+        return lib.dei2i_mask_fill(n, c, h, w, patch, sh, kp, src, None, None, dst, None, st)
+
+    assert fill() == 0
+    for bad in (dict(n=0), dict(c=0), dict(h=0), dict(w=0), dict(patch=0), dict(h=6), dict(w=10), dict(sh=None), dict(kp=None), dict(src=None),
+                dict(dst=None)):
+        assert fill(**bad) == BAD_ARG, bad
+    assert lib.dei2i_mask_fill(2, 3, 8, 8, 4, p(shift), p(keep), p(imgs), p(out), None, p(out), None, st) == BAD_ARG     # token, no strides
+    assert lib.dei2i_mask_fill_bwd(2, 3, 8, 8, 4, p(shift), p(keep), p(imgs), p(out), st) == 0
+    assert lib.dei2i_mask_fill_bwd(2, 3, 8, 6, 4, p(shift), p(keep), p(imgs), p(out), st) == BAD_ARG
+    assert lib.dei2i_mask_fill_bwd(2, 3, 8, 8, 4, p(shift), p(keep), None, p(out), st) == BAD_ARG
+    torch.cuda.synchronize()
+
+    with pytest.raises(ValueError, match="patches"):
+        ops.mask_draw(rng, 2, 10, 8, 4, 0.75)
+    with pytest.raises(ValueError, match="patches"):
+        ops.mask_fill(torch.zeros(2, 3, 8, 10, device=DEV), keep, shift, 4)
+    with pytest.raises(ValueError, match="no CPU fallback"):
+        ops.mask_fill(imgs.cpu(), keep, shift, 4)
+    with pytest.raises(ValueError):
+        ops.mask_fill(imgs, keep.cpu(), shift, 4)
+    with pytest.raises(ValueError):
+        ops.mask_fill(imgs, keep, shift.cpu(), 4)
+    with pytest.raises(ValueError):
+        ops.mask_fill(imgs, keep[:, :, :2], shift, 4)
+    with pytest.raises(ValueError):
+        ops.mask_fill(imgs, keep, shift, 4, token=torch.ones(2, 3, 1, 1, device=DEV))
+    with pytest.raises(ValueError):
+        ops.DeviceRng(1, "cpu")
+    assert ops.DiffAugRng is ops.DeviceRng
+    assert rng.state() == (SEED, 1)
+
+
+def test_model_refuses_an_rng_on_another_device_and_unknown_values():
+    from de_i2i_gan_amd.models.defectgan_model import DefectGanModel
+    c = dict(image_size=32, batch=2, num_layers=3, ngf=8, ndf=8, hidden_nc=16)
+    mae = dict(mask_token_type="scalar", mask_ratio=0.75, patch_size=4)
+    with pytest.raises(ValueError, match="mask_rng"):
+        DefectGanModel(make_opt(c, "cpu", "f32", mask_rng="device", **mae))
+    with pytest.raises(ValueError, match="mask_rng"):
+        DefectGanModel(make_opt(c, DEV, "f32", mask_rng="gpu", **mae))
+    assert DefectGanModel(make_opt(c, DEV, "f32", mask_rng="host", **mae)).mask_rng is None
+    torch.manual_seed(11)
+    a = DefectGanModel(make_opt(c, DEV, "f32", mask_rng="device", **mae)).mask_rng.state()
+    torch.manual_seed(11)
+    b = DefectGanModel(make_opt(c, DEV, "f32", mask_rng="device", mask_seed=None, **mae)).mask_rng.state()
+    assert a == b and a[1] == 0 and 0 <= a[0] < 2 ** 63          # one draw from the host RNG at construction
+    model = _mae_model("scalar")
+    model.mask_rng = SimpleNamespace(device=torch.device("cuda", 1), seed=1, counter=model.mask_rng.counter)
+    with pytest.raises(ValueError, match="mask_rng"):
+        model._repair_mask(torch.zeros(2, 3, 32, 32, device=DEV), torch.eye(6, device=DEV)[[1, 2]])

@@ -1,4 +1,5 @@
-"""defectGAN step time with the recipe options, eager against ``opt.graph_step``, in one process: one JSON line.
+"""defectGAN (or, ``--stage mae``, MAE pre-training) step time with the recipe options, eager against ``opt.graph_step``, in one
+process: one JSON line.
 
 Setup: the trainer of ``bench.py``'s defaults (256x256, batch 16, bf16, its synthetic batch and seed) with the given option set,
 once per requested mode.  After the warm-up (which, in graph mode, covers the eager warm-up calls and the capture) ``--steps``
@@ -9,8 +10,12 @@ host time of a ``step()`` call, ``wall_ms_per_step`` the whole timed region divi
     python tools/bench_graph_step.py --use-spectral --add-noise --diff-aug color,translation,cutout --diff-aug-rng device \\
         [--mode eager --mode graph] [--steps 20] [--warmup 8]
 
+    python tools/bench_graph_step.py --stage mae --mask-rng device [--mode eager --mode graph]
+
 ``--diff-aug-rng host`` draws DiffAugment's parameters on the host like the reference (graph mode refuses it), ``device`` on the
-GPU (``ops.DiffAugRng``)."""
+GPU (``ops.DiffAugRng``).  ``--stage mae`` runs ``MAETrainer`` (bench.py's MAE option set) on the background batch and its labels;
+``--mask-rng host`` draws its patch masks on the host like the reference (graph mode refuses it), ``device`` on the GPU
+(``ops.mask_draw``)."""
 import argparse
 import json
 import os
@@ -28,18 +33,24 @@ import bench  # noqa: E402
 
 def run(opts, mode, device):
     from de_i2i_gan_amd.trainers.defectgan_trainer import DefectGanTrainer
+    from de_i2i_gan_amd.trainers.mae_trainer import MAETrainer
+    mae = opts.stage == "mae"
     opt = bench.make_opt(opts, device)
     opt.diff_aug = opts.diff_aug
     if opts.diff_aug_rng is not None:
         opt.diff_aug_rng = opts.diff_aug_rng
         opt.diff_aug_seed = opts.diff_aug_seed
+    if opts.mask_rng is not None:
+        opt.mask_rng = opts.mask_rng
+        opt.mask_seed = opts.mask_seed
     if mode == "graph":
         opt.graph_step, opt.graph_warmup = True, 3
     torch.manual_seed(123)
-    tr = DefectGanTrainer(opt)
+    tr = (MAETrainer if mae else DefectGanTrainer)(opt)
     bg, lab, df = (t.to(device) for t in bench.synthetic_batch(opts.batch, opts.image_size, seed=7))
+    inputs = (bg, lab) if mae else (bg, lab, df)
     for _ in range(opts.warmup):
-        tr.step(bg, lab, df)
+        tr.step(*inputs)
     torch.cuda.synchronize()
     events = [torch.cuda.Event(enable_timing=True) for _ in range(opts.steps + 1)]
     host = []
@@ -47,7 +58,7 @@ def run(opts, mode, device):
     t_start = time.perf_counter()
     for i in range(opts.steps):
         t0 = time.perf_counter()
-        tr.step(bg, lab, df)
+        tr.step(*inputs)
         host.append(1e3 * (time.perf_counter() - t0))
         events[i + 1].record()
     torch.cuda.synchronize()
@@ -71,6 +82,9 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--image-size", type=int, default=256)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--stage", default="defectgan", choices=["defectgan", "mae"], help="mae: MAETrainer.step on (bg, labels)")
+    ap.add_argument("--mask-rng", dest="mask_rng", default=None, choices=["host", "device"], help="--stage mae: where the masks are drawn")
+    ap.add_argument("--mask-seed", dest="mask_seed", type=int, default=4321)
     ap.add_argument("--use-spectral", dest="use_spectral", action="store_true")
     ap.add_argument("--add-noise", dest="add_noise", action="store_true")
     ap.add_argument("--diff-aug", dest="diff_aug", default="", metavar="POLICY", help="e.g. color,translation,cutout ('' = none)")
@@ -90,9 +104,9 @@ def main():
         res = run(opts, mode, "cuda:0")
         runs.append(res)
         print("[bench_graph_step]", json.dumps(res), file=sys.stderr, flush=True)
-    print(json.dumps({"workload": "defectGAN DefectGanTrainer.step", "device": torch.cuda.get_device_name(0), "image_size": opts.image_size,
+    print(json.dumps({"workload": "MAE-GAN MAETrainer.step" if opts.stage == "mae" else "defectGAN DefectGanTrainer.step", "device": torch.cuda.get_device_name(0), "image_size": opts.image_size,
                       "batch": opts.batch, "dtype": opts.dtype, "use_spectral": opts.use_spectral, "add_noise": opts.add_noise,
-                      "diff_aug": opts.diff_aug, "diff_aug_rng": opts.diff_aug_rng or "host", "steps": opts.steps,
+                      "diff_aug": opts.diff_aug, "diff_aug_rng": opts.diff_aug_rng or "host", "mask_rng": opts.mask_rng or "host", "steps": opts.steps,
                       "warmup": opts.warmup, "runs": runs}))
 
 
