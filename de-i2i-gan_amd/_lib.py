@@ -102,6 +102,10 @@ SIGNATURES = {
     "dei2i_bce_logits_bwd": (c_int, [c_size_t, _P, _P, c_float, _P, _P, _P]),
     "dei2i_l1_fwd": (c_int, [c_size_t, _P, _P, _P, _P]),
     "dei2i_l1_bwd": (c_int, [c_size_t, _P, _P, _P, _P, _P, _P]),
+    "dei2i_mse_fwd": (c_int, [c_size_t, _P, _P, c_float, _P, _P]),
+    "dei2i_mse_bwd": (c_int, [c_size_t, _P, _P, c_float, _P, _P, _P, _P]),
+    "dei2i_cce_logits_fwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P]),
+    "dei2i_cce_logits_bwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P]),
     "dei2i_noise_fwd": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P, _P]),
     "dei2i_noise_bwd": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P, c_int, _P]),
     "dei2i_spectral_scratch_floats": (c_size_t, [c_int, c_int]),

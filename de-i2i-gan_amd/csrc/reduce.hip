@@ -1,5 +1,6 @@
 // Reduction kernels: per-channel moments (BatchNorm / InstanceNorm statistics), the two-pass backward of
-// BatchNorm and SPADE(InstanceNorm), bias-gradient column sums, and the scalar losses (BCE-with-logits, L1).
+// BatchNorm and SPADE(InstanceNorm), bias-gradient column sums, and the scalar losses (BCE-with-logits, L1, MSE, and the
+// cross entropy over a class dimension).
 //
 // Common shape: an NHWC tensor is viewed as (rows, C); a 256-thread workgroup owns a contiguous row range,
 // thread t owns the 16-byte channel vector (t % cv) and walks rows (t / cv), (t / cv) + 256/cv, ...  Per-thread
@@ -711,6 +712,97 @@ __global__ void l1_bwd_kernel(const float* __restrict__ a, const float* __restri
   }
 }
 
+__global__ __launch_bounds__(256) void mse_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, float bconst,
+                                                      size_t n, float* __restrict__ out) {
+  __shared__ float smem[4];
+  float acc = 0.f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float d = a[i] - (b != nullptr ? b[i] : bconst);
+    acc = fmaf(d, d, acc);
+  }
+  const float s = block_sum_256(acc, smem);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+__global__ void mse_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, float bconst, size_t n, float inv_n,
+                               const float* __restrict__ gout, float* __restrict__ da, float* __restrict__ db) {
+  const float go = 2.f * (gout[0] * inv_n);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float g = (a[i] - (b != nullptr ? b[i] : bconst)) * go;
+    if (da != nullptr) da[i] = g;
+    if (db != nullptr) db[i] = -g;
+  }
+}
+
+// ---- cross entropy over the class dimension (the `cce` kind of base_model.py:68-80; the reference
+//      tree is not part of this repository, so the function is stated here: F.cross_entropy(x, target) with a float target of x's
+//      shape (rows, classes) and mean reduction -- for one-hot rows the class-index form gives the same number) ----
+//   loss = 1/rows * sum_r sum_c t[r][c] * (lse_r - x[r][c]),  lse_r = m_r + log sum_c exp(x[r][c] - m_r),  m_r = max_c x[r][c]
+// One wavefront per row, four rows per workgroup, the workgroups stride over the row quads; lane l owns classes l, l + 64, ...
+// and the wave meets through xor shuffles (a fixed tree: the same bits on every run).  A row's term is summed as
+// sum_c t * (m - x) + S * log(sum exp), S = sum_c t: every addend is >= 0 for t >= 0, nothing cancels at |x| ~ 1e4.
+// No cap on `classes`: the lanes loop.
+DEI2I_D float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// -> m_r and sum_c exp(x - m_r) of one row, in every lane
+DEI2I_D void cce_row_softmax(const float* __restrict__ xr, int classes, int lane, float& m, float& sum) {
+  float mx = -INFINITY;
+  for (int c = lane; c < classes; c += 64) mx = fmaxf(mx, xr[c]);
+  m = wave_max(mx);
+  float se = 0.f;
+  for (int c = lane; c < classes; c += 64) se += expf(xr[c] - m);
+  sum = wave_sum(se);
+}
+
+__global__ __launch_bounds__(256) void cce_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t, size_t rows,
+                                                      int classes, float* __restrict__ out) {
+  __shared__ float smem[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float acc = 0.f;                                     // this wave's rows, in row order (the same value in every lane)
+  for (size_t r = (size_t)blockIdx.x * 4 + wave; r < rows; r += (size_t)gridDim.x * 4) {
+    const float* __restrict__ xr = x + r * (size_t)classes;
+    const float* __restrict__ tr = t + r * (size_t)classes;
+    float m, sum;
+    cce_row_softmax(xr, classes, lane, m, sum);
+    float ts = 0.f, td = 0.f;
+    for (int c = lane; c < classes; c += 64) {
+      const float tv = tr[c];
+      ts += tv;
+      td = fmaf(tv, m - xr[c], td);
+    }
+    ts = wave_sum(ts);
+    td = wave_sum(td);
+    acc += fmaf(ts, logf(sum), td);
+  }
+  __syncthreads();
+  if (lane == 0) smem[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = smem[0] + smem[1] + smem[2] + smem[3];      // partial; loss_finalize_kernel sums them in order
+}
+
+// dx[r][c] = gout/rows * (S_r * softmax_r[c] - t[r][c]), softmax as exp(x - m) / sum exp(x - m) (not through a difference of logs)
+__global__ __launch_bounds__(256) void cce_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, size_t rows,
+                                                      int classes, float inv_rows, const float* __restrict__ gout,
+                                                      float* __restrict__ dx) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float go = gout[0] * inv_rows;
+  for (size_t r = (size_t)blockIdx.x * 4 + wave; r < rows; r += (size_t)gridDim.x * 4) {
+    const float* __restrict__ xr = x + r * (size_t)classes;
+    const float* __restrict__ tr = t + r * (size_t)classes;
+    float m, sum;
+    cce_row_softmax(xr, classes, lane, m, sum);
+    float ts = 0.f;
+    for (int c = lane; c < classes; c += 64) ts += tr[c];
+    ts = wave_sum(ts);
+    const float inv = 1.f / sum;
+    for (int c = lane; c < classes; c += 64) dx[r * (size_t)classes + c] = (ts * (expf(xr[c] - m) * inv) - tr[c]) * go;
+  }
+}
+
 // ---- fused conv + norm + act support (BASELINE.json configs[1]) ------------------------------
 // out = act(a[c]*x + b[c]) (+ res) like affine_act_kernel (elementwise.hip), AND the per-channel sum / sum of squares of
 // the stored (rounded) output in the moments_partial record layout: the InstanceNorm / BatchNorm that follows needs no
@@ -1139,6 +1231,47 @@ int dei2i_l1_bwd(size_t n, const float* a, const float* b, const float* gout, fl
   if (n == 0 || !a || !gout) return DEI2I_ERR_BAD_ARG;
   hipLaunchKernelGGL(l1_bwd_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, (hipStream_t)s, a, b, n, 1.f / (float)n, gout,
                      da, db);
+  return (int)hipGetLastError();
+}
+
+int dei2i_mse_fwd(size_t n, const float* a, const float* b, float bconst, float* out, dei2i_stream s) {
+  if (n == 0 || !a || !out) return DEI2I_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)s;
+  float* part = nullptr;
+  if (hipGetSymbolAddress((void**)&part, HIP_SYMBOL(g_loss_partials)) != hipSuccess) return DEI2I_ERR_BAD_ARG;
+  const unsigned nb = grid_for(n, 256, 1024);
+  hipLaunchKernelGGL(mse_fwd_kernel, dim3(nb), dim3(256), 0, st, a, b, bconst, n, part);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)nb, 1.f / (float)n, out, 0);
+  return (int)hipGetLastError();
+}
+
+int dei2i_mse_bwd(size_t n, const float* a, const float* b, float bconst, const float* gout, float* da, float* db,
+                  dei2i_stream s) {
+  if (n == 0 || !a || !gout) return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(mse_bwd_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, (hipStream_t)s, a, b, bconst, n, 1.f / (float)n,
+                     gout, da, db);
+  return (int)hipGetLastError();
+}
+
+// four rows (one per wavefront) per workgroup, at most 1024 workgroups: one partial each in g_loss_partials
+static inline unsigned cce_blocks(size_t rows) { return grid_for(rows, 4, 1024); }
+
+int dei2i_cce_logits_fwd(size_t rows, int classes, const float* x, const float* target, float* out, dei2i_stream s) {
+  if (rows == 0 || classes <= 0 || !x || !target || !out) return DEI2I_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)s;
+  float* part = nullptr;
+  if (hipGetSymbolAddress((void**)&part, HIP_SYMBOL(g_loss_partials)) != hipSuccess) return DEI2I_ERR_BAD_ARG;
+  const unsigned nb = cce_blocks(rows);
+  hipLaunchKernelGGL(cce_fwd_kernel, dim3(nb), dim3(256), 0, st, x, target, rows, classes, part);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)nb, 1.f / (float)rows, out, 0);
+  return (int)hipGetLastError();
+}
+
+int dei2i_cce_logits_bwd(size_t rows, int classes, const float* x, const float* target, const float* gout, float* dx,
+                         dei2i_stream s) {
+  if (rows == 0 || classes <= 0 || !x || !target || !gout || !dx) return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(cce_bwd_kernel, dim3(cce_blocks(rows)), dim3(256), 0, (hipStream_t)s, x, target, rows, classes,
+                     1.f / (float)rows, gout, dx);
   return (int)hipGetLastError();
 }
 

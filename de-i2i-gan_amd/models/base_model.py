@@ -6,7 +6,8 @@ import torch.nn
 from .. import ops
 from ..networks import load_network, save_network
 
-_LOSSES = {"bce": ops.bce_logits, "bce_logits": ops.bce_logits, "l1": ops.l1}      # the two the hot path uses, as HIP ops
+# the helper's four kinds as HIP ops: bce and l1 are what the hot path itself names; cce / mse arrive as opt.clf_loss_type
+_LOSSES = {"bce": ops.bce_logits, "bce_logits": ops.bce_logits, "cce": ops.cce_logits, "l1": ops.l1, "mse": ops.mse}
 
 
 class BaseModel:
@@ -58,10 +59,11 @@ class BaseModel:
         return "".join(blocks)
 
     def _cal_loss(self, logits, targets, loss_type):
-        """base_model.py:68-80 -- mean-reduced; `targets` may be a python constant (all-ones / all-zeros labels)."""
+        """base_model.py:68-80 -- mean-reduced; `targets` may be a python constant (all-ones / all-zeros labels) for bce and mse;
+        cce takes class weights of the logits' shape (one-hot rows: the class-index form)."""
         fn = _LOSSES.get(loss_type)
         if fn is None:
-            raise ValueError(f"loss_type: {loss_type} is not on the MI355X hot path (bce | l1)")
+            raise ValueError(f"loss_type: {loss_type} is not on the MI355X hot path (bce | cce | l1 | mse)")
         return fn(logits, targets)
 
     def update_per_epoch(self, epoch):

@@ -363,7 +363,8 @@ class DefectGanModel(BaseModel):
         if whole:
             # Every loss group of the reference is a mean of per-pass means over equally sized halves of what the paired passes hold
             # as ONE tensor: the mean over the whole tensor is the same number (to the rounding of a differently ordered fp32 sum),
-            # without slicing the passes' outputs apart (a zero fill, a copy and an add per slice in backward).
+            # without slicing the passes' outputs apart (a zero fill, a copy and an add per slice in backward).  That holds for every
+            # clf_loss_type: bce and mse are means over elements, cce a mean over rows, and the halves have as many of either.
             gan_loss = self._cal_loss(fakes_src, 1.0, "bce")
             clf_loss = self._cal_loss(fakes_cls, head_labels.view_as(fakes_cls), self.clf_loss_type)
             rec_loss = self._cal_loss(recovers, reals, "l1")              # [recover_normals | recover_defects] vs [bg | df]

@@ -2270,3 +2270,73 @@ class _L1(torch.autograd.Function):
 def l1(a, b=None):
     """l1_loss(a, b), mean; ``b=None`` means zeros (sd_con, defectgan_model.py:231-236)."""
     return _L1.apply(a, b)
+
+
+class _Mse(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, bconst: float):
+        _require_gpu(a, "mse")
+        a = a.contiguous().float()
+        bb = None if b is None else b.contiguous().float()
+        if bb is not None and bb.numel() != a.numel():
+            raise ValueError("mse: target size mismatch")
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+        lib = _lib_for(a)
+        L.check(lib.dei2i_mse_fwd(a.numel(), _p(a), _p(bb), bconst, _p(out), _stream()), "mse_fwd")
+        ctx.bconst = bconst
+        ctx.save_for_backward(a, bb)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, bb = ctx.saved_tensors
+        g = g.contiguous().float()
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(bb) if (bb is not None and ctx.needs_input_grad[1]) else None
+        if da is None and db is None:
+            return None, None, None
+        lib = _lib_for(a)
+        L.check(lib.dei2i_mse_bwd(a.numel(), _p(a), _p(bb), ctx.bconst, _p(g), _p(da), _p(db), _stream()), "mse_bwd")
+        return da, db, None
+
+
+def mse(a, b=0.0):
+    """mse_loss(a, b), mean.  ``b`` is a tensor (it gets its gradient when it requires one) or a python number."""
+    if b is None or isinstance(b, (int, float)):
+        return _Mse.apply(a, None, float(b or 0.0))
+    return _Mse.apply(a, b, 0.0)
+
+
+class _CceLogits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, target):
+        _require_gpu(x, "cce_logits")
+        if x.dim() < 2 or any(d != 1 for d in x.shape[2:]) or x.numel() == 0:
+            raise ValueError(f"cce_logits: logits of shape {tuple(x.shape)}; expected (N, C) or (N, C, 1, ..., 1)")
+        rows, classes = x.shape[0], x.shape[1]
+        if target.numel() != x.numel():
+            raise ValueError("cce_logits: target size mismatch")
+        x = x.contiguous().float()
+        t = target.detach().contiguous().float()
+        out = torch.empty((), dtype=torch.float32, device=x.device)      # written (not accumulated) by the finalize kernel
+        lib = _lib_for(x)
+        L.check(lib.dei2i_cce_logits_fwd(rows, classes, _p(x), _p(t), _p(out), _stream()), "cce_fwd")
+        ctx.save_for_backward(x, t)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t = ctx.saved_tensors
+        g = g.contiguous().float()
+        dx = torch.empty_like(x)
+        lib = _lib_for(x)
+        L.check(lib.dei2i_cce_logits_bwd(x.shape[0], x.shape[1], _p(x), _p(t), _p(g), _p(dx), _stream()), "cce_bwd")
+        return dx, None
+
+
+def cce_logits(x, target):
+    """cross_entropy(x, target), mean over the rows: ``x`` is (N, C) or (N, C, 1, ..., 1), ``target`` a tensor of as many elements
+    holding class weights (one-hot rows: the class-index form; multi-hot and all-zero rows are legal).  No gradient goes to the target."""
+    if not isinstance(target, torch.Tensor):
+        raise ValueError("cce_logits: the target is a tensor of class weights, one row per sample")
+    return _CceLogits.apply(x, target)

@@ -225,6 +225,23 @@ int dei2i_bce_logits_bwd(size_t n, const float* x, const float* target, float tc
 /* mean |a - b| ; b == NULL -> 0; out[0] = loss.  backward: da = sign(a-b)*gout/n, db = -da (either may be NULL) */
 int dei2i_l1_fwd(size_t n, const float* a, const float* b, float* out, dei2i_stream s);
 int dei2i_l1_bwd(size_t n, const float* a, const float* b, const float* gout, float* da, float* db, dei2i_stream s);
+/* mean (a - b)^2 ; b == NULL -> the constant `bconst`; out[0] = loss (ordered block partials, like the two above).
+ * backward: da = 2*(a-b)*gout/n, db = -da (either may be NULL) */
+int dei2i_mse_fwd(size_t n, const float* a, const float* b, float bconst, float* out, dei2i_stream s);
+int dei2i_mse_bwd(size_t n, const float* a, const float* b, float bconst, const float* gout, float* da, float* db,
+                  dei2i_stream s);
+/* The `cce` kind of the same helper (the reference tree is not part of this repository, so the
+ * function is stated here): torch.nn.functional.cross_entropy(x, target), mean reduction, x (rows, classes) with the class
+ * dimension last and contiguous, target a float tensor of the same shape (class weights):
+ *   out[0] = 1/rows * sum_r sum_c t[r][c] * (lse_r - x[r][c]),  lse_r = m_r + log sum_c exp(x[r][c] - m_r),  m_r = max_c x[r][c]
+ * For one-hot rows this is the class-index form; multi-hot and all-zero rows are legal (a row weighs S_r = sum_c t[r][c]).
+ * The row maximum is subtracted before exp (logits of magnitude 1e4 give finite results); ordered partials + finalize, no
+ * atomics: out[0] is written, needs no zero fill, and two runs give the same bits.  `classes` has no cap (one wavefront per
+ * row, its lanes loop over the classes).
+ * backward: dx[r][c] = gout/rows * (S_r * softmax_r[c] - t[r][c]); the target gets no gradient. */
+int dei2i_cce_logits_fwd(size_t rows, int classes, const float* x, const float* target, float* out, dei2i_stream s);
+int dei2i_cce_logits_bwd(size_t rows, int classes, const float* x, const float* target, const float* gout, float* dx,
+                         dei2i_stream s);
 
 /* ---- NoiseInjection (models/networks/architecture.py:374-389, the 'constant' weight the blocks use) ----
  * x, out, dy: NHWC activations viewed as [rows = N*H*W][C] in the compute dtype (C a multiple of 8 for bf16, 4 for fp32);
