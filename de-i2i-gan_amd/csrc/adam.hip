@@ -11,6 +11,21 @@
 
 namespace dei2i {
 
+// One element's update, shared by the float4 loop and the scalar loop of adam_kernel so that an element gets the same bits
+// whichever loop reaches it (the tail of a tensor, a tensor that is not 16-byte aligned).  Left to the compiler, the two loops
+// were contracted into different fused multiply-adds; here every rounding is written out and contraction is off.
+template <bool COUPLED>
+DEI2I_D void adam_update(float& p, const float g, float& m, float& v, const float one_minus_b1, const float beta2,
+                         const float one_minus_b2, const float eps, const float inv_c2, const float step_size,
+                         const float grad_scale, const float keep, const float wd) {
+#pragma clang fp contract(off)
+  const float gv = COUPLED ? fmaf(g, grad_scale, wd * p) : g * grad_scale;
+  m = fmaf(one_minus_b1, COUPLED ? gv - m : fmaf(g, grad_scale, -m), m);
+  v = COUPLED ? fmaf(beta2, v, gv * (one_minus_b2 * gv)) : fmaf(gv, one_minus_b2 * gv, beta2 * v);
+  const float denom = fmaf(sqrtf(v), inv_c2, eps);
+  p = fmaf(p, keep, -(step_size * (m / denom)));
+}
+
 // DEV: (lr, bias_c1, bias_c2_sqrt, keep) are row `*index` of the device array `hyper` (`rows` rows of 4 floats) instead of the
 // kernel arguments of the same names -- what a captured graph replays with per-step values; the rest of the math is shared.
 template <bool COUPLED, bool DEV>
@@ -29,6 +44,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const dei2i_adam_rec* __restr
   }
   const float step_size = lr / bias_c1;
   const float inv_c2 = 1.f / bias_c2_sqrt;
+  const float a1 = 1.f - beta1, a2 = 1.f - beta2;
   const int64_t n = rec.n;
   const int64_t n4 = ((reinterpret_cast<uintptr_t>(rec.p) | reinterpret_cast<uintptr_t>(rec.g) |
                        reinterpret_cast<uintptr_t>(rec.m) | reinterpret_cast<uintptr_t>(rec.v)) & 15) == 0 ? n / 4 : 0;
@@ -40,24 +56,18 @@ __global__ __launch_bounds__(256) void adam_kernel(const dei2i_adam_rec* __restr
     float4 v = reinterpret_cast<float4*>(rec.v)[i];
     float* pp = &p.x; const float* gp = &g.x; float* mp = &m.x; float* vp = &v.x;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gv = COUPLED ? gp[e] * grad_scale + wd * pp[e] : gp[e] * grad_scale;
-      mp[e] = mp[e] + (1.f - beta1) * (gv - mp[e]);
-      vp[e] = beta2 * vp[e] + (1.f - beta2) * gv * gv;
-      const float denom = sqrtf(vp[e]) * inv_c2 + eps;
-      pp[e] = pp[e] * keep - step_size * (mp[e] / denom);
-    }
+    for (int e = 0; e < 4; ++e)
+      adam_update<COUPLED>(pp[e], gp[e], mp[e], vp[e], a1, beta2, a2, eps, inv_c2, step_size, grad_scale, keep, wd);
     reinterpret_cast<float4*>(rec.p)[i] = p;
     reinterpret_cast<float4*>(rec.m)[i] = m;
     reinterpret_cast<float4*>(rec.v)[i] = v;
   }
   for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float gv = COUPLED ? rec.g[i] * grad_scale + wd * rec.p[i] : rec.g[i] * grad_scale;
-    const float m = rec.m[i] + (1.f - beta1) * (gv - rec.m[i]);
-    const float v = beta2 * rec.v[i] + (1.f - beta2) * gv * gv;
+    float p = rec.p[i], m = rec.m[i], v = rec.v[i];
+    adam_update<COUPLED>(p, rec.g[i], m, v, a1, beta2, a2, eps, inv_c2, step_size, grad_scale, keep, wd);
     rec.m[i] = m;
     rec.v[i] = v;
-    rec.p[i] = rec.p[i] * keep - step_size * (m / (sqrtf(v) * inv_c2 + eps));
+    rec.p[i] = p;
   }
 }
 

@@ -333,7 +333,7 @@ int dei2i_nchw_to_nhwc(int dtype, int N, int C, int H, int W, int Cs, const floa
 }
 
 int dei2i_nhwc_to_nchw(int dtype, int N, int C, int H, int W, int Cs, const void* src, float* dst, dei2i_stream s) {
-  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || Cs < C || !src || !dst) return DEI2I_ERR_BAD_ARG;
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || Cs < C || Cs % vec_of(dtype) || !src || !dst) return DEI2I_ERR_BAD_ARG;
   const size_t total = (size_t)N * C * H * W;
   by_dtype(dtype, [&](auto t) {
     using T = decltype(t);

@@ -105,7 +105,8 @@ int dei2i_conv2d_fwd_fp8(const dei2i_conv* c, const void* x_e4m3, const void* w_
 int dei2i_fold_pad(int dtype, int N, int H, int W, int C, int pad, int pad_mode, int up, const void* dx_ext,
                    const void* addend, void* dx, dei2i_stream s);
 
-/* ---- layout at the module boundary (NCHW fp32 <-> NHWC compute dtype) ---- */
+/* ---- layout at the module boundary (NCHW fp32 <-> NHWC compute dtype) ----
+ * Cs: the NHWC channel stride, >= C and a multiple of the 16-byte vector (8 in bf16, 4 in f32) in all three. */
 int dei2i_nchw_to_nhwc(int dtype, int N, int C, int H, int W, int Cs, const float* src, void* dst, dei2i_stream s);
 int dei2i_nhwc_to_nchw(int dtype, int N, int C, int H, int W, int Cs, const void* src, float* dst, dei2i_stream s);
 /* same as nchw_to_nhwc with F.interpolate(mode='nearest') from (hs,ws) to (H,W) fused (SPADE label map,
