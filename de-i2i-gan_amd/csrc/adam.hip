@@ -108,14 +108,29 @@ __global__ __launch_bounds__(256) void ema_lerp_kernel(const dei2i_adam_rec* __r
 
 using namespace dei2i;
 
+// The grid of a multi-tensor launch: y = the table's rows; x = 256-thread workgroups for the longest tensor at `per_thread`
+// elements a thread, between 1 and `cap` (the kernels stride over what is left).
+static dim3 table_grid(int64_t max_n, int per_thread, int64_t cap, int count) {
+  int64_t bx = (max_n / per_thread + 255) / 256;
+  if (bx < 1) bx = 1;
+  if (bx > cap) bx = cap;
+  return dim3((unsigned)bx, (unsigned)count);
+}
+
+template <bool COUPLED, bool DEV>
+static int adam_launch(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2, float eps,
+                       float bias_c1, float bias_c2_sqrt, float grad_scale, float keep, float wd, const float* hyper_dev,
+                       const int* index_dev, int rows, dei2i_stream s) {
+  hipLaunchKernelGGL((adam_kernel<COUPLED, DEV>), table_grid(max_n, 4, 512, count), dim3(256), 0, (hipStream_t)s, table_dev, lr,
+                     beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, keep, wd, hyper_dev, index_dev, rows);
+  return (int)hipGetLastError();
+}
+
 extern "C" int dei2i_sgd_rmsprop_step(const dei2i_adam_rec* table_dev, int count, int64_t max_n, int kind, float lr, float alpha,
                                       float eps, float grad_scale, dei2i_stream s) {
   if (!table_dev || count <= 0 || max_n <= 0 || (kind != 0 && kind != 1)) return DEI2I_ERR_BAD_ARG;
-  int64_t bx = (max_n + 255) / 256;
-  if (bx < 1) bx = 1;
-  if (bx > 2048) bx = 2048;
-  hipLaunchKernelGGL(sgd_rmsprop_kernel, dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, kind, lr, alpha, eps,
-                     grad_scale);
+  hipLaunchKernelGGL(sgd_rmsprop_kernel, table_grid(max_n, 1, 2048, count), dim3(256), 0, (hipStream_t)s, table_dev, kind, lr, alpha,
+                     eps, grad_scale);
   return (int)hipGetLastError();
 }
 
@@ -123,51 +138,32 @@ extern "C" int dei2i_adam_step(const dei2i_adam_rec* table_dev, int count, int64
                                float eps, float bias_c1, float bias_c2_sqrt, float grad_scale, float decoupled_decay,
                                dei2i_stream s) {
   if (!table_dev || count <= 0 || max_n <= 0) return DEI2I_ERR_BAD_ARG;
-  int64_t bx = (max_n / 4 + 255) / 256;
-  if (bx < 1) bx = 1;
-  if (bx > 512) bx = 512;
-  hipLaunchKernelGGL((adam_kernel<false, false>), dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, lr,
-                     beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, 1.f - lr * decoupled_decay, 0.f, nullptr, nullptr, 0);
-  return (int)hipGetLastError();
+  return adam_launch<false, false>(table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale,
+                                   1.f - lr * decoupled_decay, 0.f, nullptr, nullptr, 0, s);
 }
 
 extern "C" int dei2i_adam_step_l2(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2,
                                   float eps, float bias_c1, float bias_c2_sqrt, float grad_scale, float weight_decay, dei2i_stream s) {
   if (!table_dev || count <= 0 || max_n <= 0) return DEI2I_ERR_BAD_ARG;
-  int64_t bx = (max_n / 4 + 255) / 256;
-  if (bx < 1) bx = 1;
-  if (bx > 512) bx = 512;
-  hipLaunchKernelGGL((adam_kernel<true, false>), dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, lr,
-                     beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, 1.f, weight_decay, nullptr, nullptr, 0);
-  return (int)hipGetLastError();
+  return adam_launch<true, false>(table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, 1.f,
+                                  weight_decay, nullptr, nullptr, 0, s);
 }
 
-static int adam_dev_launch(bool coupled, const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev,
-                           const int* index_dev, int rows, float beta1, float beta2, float eps, float grad_scale, float weight_decay,
-                           dei2i_stream s) {
-  if (!table_dev || count <= 0 || max_n <= 0 || !hyper_dev || !index_dev || rows <= 0) return DEI2I_ERR_BAD_ARG;
-  int64_t bx = (max_n / 4 + 255) / 256;
-  if (bx < 1) bx = 1;
-  if (bx > 512) bx = 512;
-  if (coupled)
-    hipLaunchKernelGGL((adam_kernel<true, true>), dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, 0.f,
-                       beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, weight_decay, hyper_dev, index_dev, rows);
-  else
-    hipLaunchKernelGGL((adam_kernel<false, true>), dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, 0.f,
-                       beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, 0.f, hyper_dev, index_dev, rows);
-  return (int)hipGetLastError();
-}
-
+// (the _dev forms: lr, the bias corrections and `keep` come from `hyper_dev`; the kernel arguments of those names are not read)
 extern "C" int dei2i_adam_step_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev,
                                    const int* index_dev, int rows, float beta1, float beta2, float eps, float grad_scale,
                                    dei2i_stream s) {
-  return adam_dev_launch(false, table_dev, count, max_n, hyper_dev, index_dev, rows, beta1, beta2, eps, grad_scale, 0.f, s);
+  if (!table_dev || count <= 0 || max_n <= 0 || !hyper_dev || !index_dev || rows <= 0) return DEI2I_ERR_BAD_ARG;
+  return adam_launch<false, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, 0.f, hyper_dev,
+                                  index_dev, rows, s);
 }
 
 extern "C" int dei2i_adam_step_l2_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev,
                                       const int* index_dev, int rows, float beta1, float beta2, float eps, float grad_scale,
                                       float weight_decay, dei2i_stream s) {
-  return adam_dev_launch(true, table_dev, count, max_n, hyper_dev, index_dev, rows, beta1, beta2, eps, grad_scale, weight_decay, s);
+  if (!table_dev || count <= 0 || max_n <= 0 || !hyper_dev || !index_dev || rows <= 0) return DEI2I_ERR_BAD_ARG;
+  return adam_launch<true, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, weight_decay,
+                                 hyper_dev, index_dev, rows, s);
 }
 
 __global__ void index_advance_kernel(int* index) { *index += 1; }
@@ -180,9 +176,6 @@ extern "C" int dei2i_index_advance(int* index_dev, dei2i_stream s) {
 
 extern "C" int dei2i_ema_lerp(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float weight, dei2i_stream s) {
   if (!table_dev || count <= 0 || max_n <= 0) return DEI2I_ERR_BAD_ARG;
-  int64_t bx = (max_n + 255) / 256;
-  if (bx < 1) bx = 1;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(ema_lerp_kernel, dim3((unsigned)bx, (unsigned)count), dim3(256), 0, (hipStream_t)s, table_dev, weight);
+  hipLaunchKernelGGL(ema_lerp_kernel, table_grid(max_n, 1, 1024, count), dim3(256), 0, (hipStream_t)s, table_dev, weight);
   return (int)hipGetLastError();
 }

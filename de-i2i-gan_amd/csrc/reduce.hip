@@ -625,16 +625,60 @@ DEI2I_D float block_sum_256(float v, float* smem) {
   return smem[0] + smem[1] + smem[2] + smem[3];
 }
 
-__global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t, float tconst,
-                                                      size_t n, float inv_n, float* __restrict__ out) {
+// The element-wise kinds: the mean over i of term(a[i], b[i]).  The second operand is the tensor `b` or, where `b` is null, the
+// constant `bconst` (0 for a kind that takes none).  A kind supplies its term, what the upstream gradient times 1/n is scaled
+// by, and the term's derivative in `a` times that; GRAD_B: `b` can get a gradient (the negated one).
+struct BceLoss {
+  static constexpr bool HAS_CONST = true, GRAD_B = false;
+  static DEI2I_D void add(float& acc, float xv, float tv) { acc += fmaxf(xv, 0.f) - xv * tv + log1pf(expf(-fabsf(xv))); }
+  static DEI2I_D float scale(float go) { return go; }
+  static DEI2I_D float grad(float xv, float tv, float go) { return (1.f / (1.f + expf(-xv)) - tv) * go; }
+};
+
+struct L1Loss {
+  static constexpr bool HAS_CONST = false, GRAD_B = true;
+  static DEI2I_D void add(float& acc, float av, float bv) {
+    const float d = av - bv;
+    acc += fabsf(d);
+  }
+  static DEI2I_D float scale(float go) { return go; }
+  static DEI2I_D float grad(float av, float bv, float go) {
+    const float d = av - bv;
+    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    return sgn * go;
+  }
+};
+
+struct MseLoss {
+  static constexpr bool HAS_CONST = true, GRAD_B = true;
+  static DEI2I_D void add(float& acc, float av, float bv) {
+    const float d = av - bv;
+    acc = fmaf(d, d, acc);
+  }
+  static DEI2I_D float scale(float go) { return 2.f * go; }
+  static DEI2I_D float grad(float av, float bv, float go) { return (av - bv) * go; }
+};
+
+template <typename K>
+__global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, float bconst,
+                                                       size_t n, float* __restrict__ out) {
   __shared__ float smem[4];
   float acc = 0.f;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float xv = x[i], tv = t != nullptr ? t[i] : tconst;
-    acc += fmaxf(xv, 0.f) - xv * tv + log1pf(expf(-fabsf(xv)));
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    K::add(acc, a[i], b != nullptr ? b[i] : (K::HAS_CONST ? bconst : 0.f));
   const float s = block_sum_256(acc, smem);
   if (threadIdx.x == 0) out[blockIdx.x] = s;          // partial; loss_finalize_kernel sums them in order
+}
+
+template <typename K>
+__global__ void loss_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, float bconst, size_t n, float inv_n,
+                                const float* __restrict__ gout, float* __restrict__ da, float* __restrict__ db) {
+  const float go = K::scale(gout[0] * inv_n);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float g = K::grad(a[i], b != nullptr ? b[i] : (K::HAS_CONST ? bconst : 0.f), go);
+    if (!K::GRAD_B || da != nullptr) da[i] = g;        // (without GRAD_B `da` is the one output: never null)
+    if (K::GRAD_B && db != nullptr) db[i] = -g;
+  }
 }
 
 // out[0] = inv_n * sum of the block partials, in index order (deterministic: no atomics, and `out` needs no zero fill)
@@ -680,58 +724,6 @@ __global__ __launch_bounds__(256) void noise_bwd_kernel(const T* __restrict__ dy
   }
   const float s = block_sum_256(acc, smem);
   if (threadIdx.x == 0) part[blockIdx.x] = s;          // loss_finalize_kernel sums the partials in index order
-}
-
-__global__ void bce_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, float tconst, size_t n, float inv_n,
-                               const float* __restrict__ gout, float* __restrict__ dx) {
-  const float go = gout[0] * inv_n;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float xv = x[i], tv = t != nullptr ? t[i] : tconst;
-    dx[i] = (1.f / (1.f + expf(-xv)) - tv) * go;
-  }
-}
-
-__global__ __launch_bounds__(256) void l1_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n,
-                                                     float inv_n, float* __restrict__ out) {
-  __shared__ float smem[4];
-  float acc = 0.f;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    acc += fabsf(a[i] - (b != nullptr ? b[i] : 0.f));
-  const float s = block_sum_256(acc, smem);
-  if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
-
-__global__ void l1_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n, float inv_n,
-                              const float* __restrict__ gout, float* __restrict__ da, float* __restrict__ db) {
-  const float go = gout[0] * inv_n;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float d = a[i] - (b != nullptr ? b[i] : 0.f);
-    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-    if (da != nullptr) da[i] = sgn * go;
-    if (db != nullptr) db[i] = -sgn * go;
-  }
-}
-
-__global__ __launch_bounds__(256) void mse_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, float bconst,
-                                                      size_t n, float* __restrict__ out) {
-  __shared__ float smem[4];
-  float acc = 0.f;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float d = a[i] - (b != nullptr ? b[i] : bconst);
-    acc = fmaf(d, d, acc);
-  }
-  const float s = block_sum_256(acc, smem);
-  if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
-
-__global__ void mse_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, float bconst, size_t n, float inv_n,
-                               const float* __restrict__ gout, float* __restrict__ da, float* __restrict__ db) {
-  const float go = 2.f * (gout[0] * inv_n);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float g = (a[i] - (b != nullptr ? b[i] : bconst)) * go;
-    if (da != nullptr) da[i] = g;
-    if (db != nullptr) db[i] = -g;
-  }
 }
 
 // ---- cross entropy over the class dimension (the `cce` kind of base_model.py:68-80; the reference
@@ -936,6 +928,24 @@ static inline bool cv_ok(int dtype, int C) {
   return C > 0 && C % vec == 0 && C / vec <= 256;
 }
 static inline size_t combine_lds(int dtype, int nv) { return (size_t)nv * vec_of(dtype) * 256 * sizeof(float); }
+
+// block partials of the scalar losses: one stream-ordered scratch per process (the losses of a step run on one stream)
+__device__ float g_loss_partials[1024];
+
+// A scalar loss's forward: `kernel` on `nb` workgroups (at most 1024) writes one partial each, its last argument being where
+// to; then out[0] = inv_n * their sum in index order.
+template <typename... KArgs, typename... Args>
+static int loss_fwd_launch(void (*kernel)(KArgs...), unsigned nb, float inv_n, float* out, dei2i_stream s, Args... args) {
+  hipStream_t st = (hipStream_t)s;
+  float* part = nullptr;
+  if (hipGetSymbolAddress((void**)&part, HIP_SYMBOL(g_loss_partials)) != hipSuccess) return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, st, args..., part);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)nb, inv_n, out, 0);
+  return (int)hipGetLastError();
+}
+
+// the grid of the element-wise kinds, forward (one partial per workgroup) and backward
+static inline unsigned loss_blocks(size_t n) { return grid_for(n, 256, 1024); }
 
 extern "C" {
 
@@ -1194,62 +1204,41 @@ int dei2i_spade_bwd_apply(int dtype, int N, int H, int W, int C, int up, const v
   return (int)hipGetLastError();
 }
 
-// block partials of the scalar losses: one stream-ordered scratch per process (the losses of a step run on one stream)
-__device__ float g_loss_partials[1024];
-
 int dei2i_bce_logits_fwd(size_t n, const float* x, const float* target, float tconst, float* out, dei2i_stream s) {
   if (n == 0 || !x || !out) return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  float* part = nullptr;
-  if (hipGetSymbolAddress((void**)&part, HIP_SYMBOL(g_loss_partials)) != hipSuccess) return DEI2I_ERR_BAD_ARG;
-  const unsigned nb = grid_for(n, 256, 1024);
-  hipLaunchKernelGGL(bce_fwd_kernel, dim3(nb), dim3(256), 0, st, x, target, tconst, n, 1.f / (float)n, part);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)nb, 1.f / (float)n, out, 0);
-  return (int)hipGetLastError();
+  return loss_fwd_launch(loss_fwd_kernel<BceLoss>, loss_blocks(n), 1.f / (float)n, out, s, x, target, tconst, n);
 }
 
 int dei2i_bce_logits_bwd(size_t n, const float* x, const float* target, float tconst, const float* gout, float* dx,
                          dei2i_stream s) {
   if (n == 0 || !x || !gout || !dx) return DEI2I_ERR_BAD_ARG;
-  hipLaunchKernelGGL(bce_bwd_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, (hipStream_t)s, x, target, tconst, n,
-                     1.f / (float)n, gout, dx);
+  hipLaunchKernelGGL(loss_bwd_kernel<BceLoss>, dim3(loss_blocks(n)), dim3(256), 0, (hipStream_t)s, x, target, tconst, n,
+                     1.f / (float)n, gout, dx, (float*)nullptr);
   return (int)hipGetLastError();
 }
 
 int dei2i_l1_fwd(size_t n, const float* a, const float* b, float* out, dei2i_stream s) {
   if (n == 0 || !a || !out) return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  float* part = nullptr;
-  if (hipGetSymbolAddress((void**)&part, HIP_SYMBOL(g_loss_partials)) != hipSuccess) return DEI2I_ERR_BAD_ARG;
-  const unsigned nb = grid_for(n, 256, 1024);
-  hipLaunchKernelGGL(l1_fwd_kernel, dim3(nb), dim3(256), 0, st, a, b, n, 1.f / (float)n, part);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)nb, 1.f / (float)n, out, 0);
-  return (int)hipGetLastError();
+  return loss_fwd_launch(loss_fwd_kernel<L1Loss>, loss_blocks(n), 1.f / (float)n, out, s, a, b, 0.f, n);
 }
 
 int dei2i_l1_bwd(size_t n, const float* a, const float* b, const float* gout, float* da, float* db, dei2i_stream s) {
   if (n == 0 || !a || !gout) return DEI2I_ERR_BAD_ARG;
-  hipLaunchKernelGGL(l1_bwd_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, (hipStream_t)s, a, b, n, 1.f / (float)n, gout,
-                     da, db);
+  hipLaunchKernelGGL(loss_bwd_kernel<L1Loss>, dim3(loss_blocks(n)), dim3(256), 0, (hipStream_t)s, a, b, 0.f, n, 1.f / (float)n,
+                     gout, da, db);
   return (int)hipGetLastError();
 }
 
 int dei2i_mse_fwd(size_t n, const float* a, const float* b, float bconst, float* out, dei2i_stream s) {
   if (n == 0 || !a || !out) return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  float* part = nullptr;
-  if (hipGetSymbolAddress((void**)&part, HIP_SYMBOL(g_loss_partials)) != hipSuccess) return DEI2I_ERR_BAD_ARG;
-  const unsigned nb = grid_for(n, 256, 1024);
-  hipLaunchKernelGGL(mse_fwd_kernel, dim3(nb), dim3(256), 0, st, a, b, bconst, n, part);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)nb, 1.f / (float)n, out, 0);
-  return (int)hipGetLastError();
+  return loss_fwd_launch(loss_fwd_kernel<MseLoss>, loss_blocks(n), 1.f / (float)n, out, s, a, b, bconst, n);
 }
 
 int dei2i_mse_bwd(size_t n, const float* a, const float* b, float bconst, const float* gout, float* da, float* db,
                   dei2i_stream s) {
   if (n == 0 || !a || !gout) return DEI2I_ERR_BAD_ARG;
-  hipLaunchKernelGGL(mse_bwd_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, (hipStream_t)s, a, b, bconst, n, 1.f / (float)n,
-                     gout, da, db);
+  hipLaunchKernelGGL(loss_bwd_kernel<MseLoss>, dim3(loss_blocks(n)), dim3(256), 0, (hipStream_t)s, a, b, bconst, n,
+                     1.f / (float)n, gout, da, db);
   return (int)hipGetLastError();
 }
 
@@ -1258,13 +1247,7 @@ static inline unsigned cce_blocks(size_t rows) { return grid_for(rows, 4, 1024);
 
 int dei2i_cce_logits_fwd(size_t rows, int classes, const float* x, const float* target, float* out, dei2i_stream s) {
   if (rows == 0 || classes <= 0 || !x || !target || !out) return DEI2I_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)s;
-  float* part = nullptr;
-  if (hipGetSymbolAddress((void**)&part, HIP_SYMBOL(g_loss_partials)) != hipSuccess) return DEI2I_ERR_BAD_ARG;
-  const unsigned nb = cce_blocks(rows);
-  hipLaunchKernelGGL(cce_fwd_kernel, dim3(nb), dim3(256), 0, st, x, target, rows, classes, part);
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int)nb, 1.f / (float)rows, out, 0);
-  return (int)hipGetLastError();
+  return loss_fwd_launch(cce_fwd_kernel, cce_blocks(rows), 1.f / (float)rows, out, s, x, target, rows, classes);
 }
 
 int dei2i_cce_logits_bwd(size_t rows, int classes, const float* x, const float* target, const float* gout, float* dx,

@@ -15,7 +15,7 @@ import ctypes
 import weakref
 from ctypes import byref, c_int, c_void_p
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -257,8 +257,7 @@ class _SpectralWeight(torch.autograd.Function):
         L.check(lib.dei2i_spectral_fwd(cout, k, _p(w), _p(u), _p(v), 1 if iterate else 0, _p(scratch), _p(u_used), _p(v_used),
                                        _p(scal), _p(w_eff), _stream()), "spectral_fwd")
         if iterate:                      # the buffers were updated in place through raw pointers: bump their cache stamps
-            u._dei2i_epoch = getattr(u, "_dei2i_epoch", 0) + 1
-            v._dei2i_epoch = getattr(v, "_dei2i_epoch", 0) + 1
+            mark_written(u, v)
         ctx.save_for_backward(w_eff, u_used, v_used, scal)
         ctx.param = weight_orig
         return w_eff
@@ -398,6 +397,13 @@ def _desc(prec: Precision, g: ConvGeom, n: int, h: int, w: int, cins: int, couts
     return d
 
 
+def mark_written(*tensors) -> None:
+    """A kernel wrote these tensors through raw pointers, which moves no autograd version counter: packed copies made of them
+    are stale.  The one writer of the ``_dei2i_epoch`` stamp; ``PackedWeights._stamp`` is its one reader."""
+    for t in tensors:
+        t._dei2i_epoch = getattr(t, "_dei2i_epoch", 0) + 1
+
+
 class PackedWeights:
     """Kernel-layout copies of one conv weight: forward [Cout][k*k][CinS] and dgrad (per stride-parity class
     [Cin][taps][CoutS]).  Re-packed lazily when any source parameter changed (autograd version counter, or the
@@ -427,7 +433,7 @@ class PackedWeights:
 
     @staticmethod
     def _stamp(t: torch.Tensor):
-        return (t.data_ptr(), t._version, getattr(t, "_dei2i_epoch", 0))
+        return (t.data_ptr(), t._version, getattr(t, "_dei2i_epoch", 0))      # (the epoch: written by mark_written alone)
 
     def get(self, weight: torch.Tensor, sources, prec: Precision, geom: ConvGeom, cins: int, couts: int, need_dgrad: bool,
             need_fwd: bool = True, per_call: bool = False):
@@ -2197,74 +2203,69 @@ def nan_guard_(x):
 # --------------------------------------------------------------------------------------------------------------
 # losses (models/base_model.py:68-80)
 # --------------------------------------------------------------------------------------------------------------
-_slabs = {}
+class _LossKind(NamedTuple):
+    """One element-wise scalar loss (csrc/reduce.hip): the mean over i of term(a[i], b[i])."""
+    name: str
+    fwd: str             # entry points: fwd(n, a, b, [const,] out, stream), bwd(n, a, b, [const,] gout, da, [db,] stream)
+    bwd: str
+    takes_const: bool    # where there is no tensor ``b``, a python constant stands for it (else zeros)
+    grad_b: bool         # ``b`` gets a gradient when it requires one (else it is detached)
 
 
-def _zero_scalar(device) -> torch.Tensor:
-    """0-dim fp32 zero carved from a pre-zeroed slab (one memset per 256 scalars instead of one per loss).  Slabs are
-    never recycled, so a loss tensor stays valid for as long as anything references it."""
-    slab, used = _slabs.get(device, (None, 0))
-    if slab is None or used >= slab.numel():
-        slab, used = torch.zeros(256, dtype=torch.float32, device=device), 0
-    _slabs[device] = (slab, used + 1)
-    return slab[used]
+class _ScalarLoss(torch.autograd.Function):
+    """The one Function of the element-wise kinds.  A kind is a subclass that binds its record: ``_L1.apply(a, b)`` is this
+    forward with ``_L1.kind`` (a class per kind, so that a kind's ``apply`` can be wrapped on its own: the tests' kink tape
+    records the l1 sites that way)."""
+    kind: _LossKind = None
 
-
-class _BceLogits(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, target, tconst: float):
-        _require_gpu(x, "bce_logits")
-        x = x.contiguous().float()
-        t = None if target is None else target.detach().contiguous().float().view(-1)
-        if t is not None and t.numel() != x.numel():
-            raise ValueError("bce_logits: target size mismatch")
-        out = torch.empty((), dtype=torch.float32, device=x.device)      # written (not accumulated) by the finalize kernel
-        lib = _lib_for(x)
-        L.check(lib.dei2i_bce_logits_fwd(x.numel(), _p(x), _p(t), tconst, _p(out), _stream()), "bce_fwd")
-        ctx.tconst = tconst
-        ctx.save_for_backward(x, t)
-        return out
+    @classmethod
+    def apply(cls, a, b, const: float = 0.0):
+        return super().apply(cls.kind, a, b, const)
 
     @staticmethod
-    def backward(ctx, g):
-        x, t = ctx.saved_tensors
-        g = g.contiguous().float()
-        dx = torch.empty_like(x)
-        lib = _lib_for(x)
-        L.check(lib.dei2i_bce_logits_bwd(x.numel(), _p(x), _p(t), ctx.tconst, _p(g), _p(dx), _stream()), "bce_bwd")
-        return dx, None, None
-
-
-def bce_logits(x, target):
-    """binary_cross_entropy_with_logits(x, target), mean.  ``target`` is a tensor or a python float constant."""
-    if isinstance(target, (int, float)):
-        return _BceLogits.apply(x, None, float(target))
-    return _BceLogits.apply(x, target, 0.0)
-
-
-class _L1(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b):
-        _require_gpu(a, "l1")
+    def forward(ctx, kind: _LossKind, a, b, const: float):
+        _require_gpu(a, kind.name)
         a = a.contiguous().float()
-        bb = None if b is None else b.contiguous().float()
-        out = torch.empty((), dtype=torch.float32, device=a.device)
-        lib = _lib_for(a)
-        L.check(lib.dei2i_l1_fwd(a.numel(), _p(a), _p(bb), _p(out), _stream()), "l1_fwd")
+        bb = None if b is None else (b if kind.grad_b else b.detach()).contiguous().float()
+        if bb is not None and bb.numel() != a.numel():
+            raise ValueError(f"{kind.name}: target size mismatch")
+        out = torch.empty((), dtype=torch.float32, device=a.device)      # written (not accumulated) by the finalize kernel
+        ctx.kind, ctx.const = kind, (const,) if kind.takes_const else ()
+        L.check(getattr(_lib_for(a), kind.fwd)(a.numel(), _p(a), _p(bb), *ctx.const, _p(out), _stream()), kind.fwd)
         ctx.save_for_backward(a, bb)
         return out
 
     @staticmethod
     def backward(ctx, g):
         a, bb = ctx.saved_tensors
+        kind = ctx.kind
         g = g.contiguous().float()
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(bb) if (bb is not None and ctx.needs_input_grad[1]) else None
+        da = torch.empty_like(a) if ctx.needs_input_grad[1] else None
+        db = torch.empty_like(bb) if (kind.grad_b and bb is not None and ctx.needs_input_grad[2]) else None
         if da is None and db is None:
-            return None, None
-        lib = _lib_for(a)
-        L.check(lib.dei2i_l1_bwd(a.numel(), _p(a), _p(bb), _p(g), _p(da), _p(db), _stream()), "l1_bwd")
-        return da, db
+            return None, None, None, None
+        grads = (_p(da), _p(db)) if kind.grad_b else (_p(da),)
+        L.check(getattr(_lib_for(a), kind.bwd)(a.numel(), _p(a), _p(bb), *ctx.const, _p(g), *grads, _stream()), kind.bwd)
+        return None, da, db, None
+
+
+class _BceLogits(_ScalarLoss):
+    kind = _LossKind("bce_logits", "dei2i_bce_logits_fwd", "dei2i_bce_logits_bwd", takes_const=True, grad_b=False)
+
+
+class _L1(_ScalarLoss):
+    kind = _LossKind("l1", "dei2i_l1_fwd", "dei2i_l1_bwd", takes_const=False, grad_b=True)
+
+
+class _Mse(_ScalarLoss):
+    kind = _LossKind("mse", "dei2i_mse_fwd", "dei2i_mse_bwd", takes_const=True, grad_b=True)
+
+
+def bce_logits(x, target):
+    """binary_cross_entropy_with_logits(x, target), mean.  ``target`` is a tensor or a python float constant."""
+    if isinstance(target, (int, float)):
+        return _BceLogits.apply(x, None, float(target))
+    return _BceLogits.apply(x, target)
 
 
 def l1(a, b=None):
@@ -2272,39 +2273,11 @@ def l1(a, b=None):
     return _L1.apply(a, b)
 
 
-class _Mse(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b, bconst: float):
-        _require_gpu(a, "mse")
-        a = a.contiguous().float()
-        bb = None if b is None else b.contiguous().float()
-        if bb is not None and bb.numel() != a.numel():
-            raise ValueError("mse: target size mismatch")
-        out = torch.empty((), dtype=torch.float32, device=a.device)
-        lib = _lib_for(a)
-        L.check(lib.dei2i_mse_fwd(a.numel(), _p(a), _p(bb), bconst, _p(out), _stream()), "mse_fwd")
-        ctx.bconst = bconst
-        ctx.save_for_backward(a, bb)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        a, bb = ctx.saved_tensors
-        g = g.contiguous().float()
-        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(bb) if (bb is not None and ctx.needs_input_grad[1]) else None
-        if da is None and db is None:
-            return None, None, None
-        lib = _lib_for(a)
-        L.check(lib.dei2i_mse_bwd(a.numel(), _p(a), _p(bb), ctx.bconst, _p(g), _p(da), _p(db), _stream()), "mse_bwd")
-        return da, db, None
-
-
 def mse(a, b=0.0):
     """mse_loss(a, b), mean.  ``b`` is a tensor (it gets its gradient when it requires one) or a python number."""
     if b is None or isinstance(b, (int, float)):
         return _Mse.apply(a, None, float(b or 0.0))
-    return _Mse.apply(a, b, 0.0)
+    return _Mse.apply(a, b)
 
 
 class _CceLogits(torch.autograd.Function):

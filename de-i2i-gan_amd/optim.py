@@ -23,6 +23,47 @@ from . import _lib as L
 from . import ops
 
 
+class _PointerTable:
+    """The pointer table of one multi-tensor launch of csrc/adam.hip on the host: one row ``(p, g, aux0, aux1, numel)`` (a
+    ``dei2i_adam_rec``) per entry ``(p, g, aux0, aux1)`` of fp32 tensors, ``aux`` tensors or None.  ``p`` must be contiguous; a
+    ``g`` that is not is copied, and the copy lives as long as this object: keep it until the launch is queued."""
+
+    def __init__(self, who, entries):
+        self.rows, self.hold, self.max_n = [], [], 0
+        self.device = entries[0][0].device
+        for p, g, aux0, aux1 in entries:
+            ops._require_gpu(p, who)
+            if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous():
+                raise TypeError(f"{who} expects contiguous fp32 tensors to update, from fp32 gradients or sources")
+            g = g if g.is_contiguous() else g.contiguous()
+            self.hold.append(g)
+            self.rows.append((p.data_ptr(), g.data_ptr(), 0 if aux0 is None else aux0.data_ptr(),
+                              0 if aux1 is None else aux1.data_ptr(), p.numel()))
+            self.max_n = max(self.max_n, p.numel())
+
+    def upload(self, into=None):
+        """-> the rows on the device, through pinned memory and stream-ordered: in the first rows of ``into``, or a new tensor"""
+        host = torch.empty((len(self.rows), 5), dtype=torch.int64, pin_memory=True)
+        host.copy_(torch.tensor(self.rows, dtype=torch.int64))
+        if into is None:
+            return host.to(self.device, non_blocking=True)
+        into[:len(self.rows)].copy_(host, non_blocking=True)
+        return into
+
+    def cached(self, cache):
+        """-> the rows on the device, uploaded only when a pointer moved since the launch that left them in ``cache`` (in steady
+        state the caching allocator hands every gradient the address it had the step before)"""
+        key = (self.device, len(self.rows), self.rows[0][0])
+        hit = cache.get(key)
+        if hit is None or hit[0] != self.rows:
+            hit = cache[key] = (self.rows, self.upload())
+        return hit[1]
+
+    def args(self, table_dev):
+        """the (table_dev, count, max_n) every entry point of csrc/adam.hip begins with"""
+        return ctypes.c_void_p(table_dev.data_ptr()), len(self.rows), self.max_n
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, weight_decay=0.0, decoupled=True):
         """``decoupled=False``: torch.optim.Adam's weight decay (L2: the gradient becomes g + wd * p before the moments -- what
@@ -33,6 +74,21 @@ class FusedAdam(torch.optim.Optimizer):
         self.grad_scale = float(grad_scale)
         self.decoupled = bool(decoupled)
 
+    def _launch_groups(self, reach):
+        """One launch per param group and step count: yields (group index, group, t, the group's parameters with a gradient that
+        reach step ``t = reach(p, state)`` now, weight decay, whether it is the coupled kind)."""
+        for gi, group in enumerate(self.param_groups):
+            by_step = {}
+            for p in group["params"]:
+                if p.grad is not None:
+                    by_step.setdefault(reach(p, self.state[p]), []).append(p)
+            wd = float(group.get("weight_decay", 0.0))
+            for t, plist in by_step.items():
+                yield gi, group, t, plist, wd, wd > 0.0 and not self.decoupled
+
+    def _table(self, plist):
+        return _PointerTable("FusedAdam", [(p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in plist])
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -42,61 +98,29 @@ class FusedAdam(torch.optim.Optimizer):
         if torch.cuda.is_current_stream_capturing():
             self._step_captured()
             return loss
-        for group in self.param_groups:
-            by_step = {}
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                ops._require_gpu(p, "FusedAdam")
-                if p.dtype != torch.float32 or p.grad.dtype != torch.float32:
-                    raise TypeError("FusedAdam expects fp32 parameters and gradients")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["step"] += 1
-                by_step.setdefault(st["step"], []).append(p)
+
+        def reach(p, st):
+            if len(st) == 0:
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["step"] += 1
+            return st["step"]
+
+        for _, group, t, plist, wd, coupled in self._launch_groups(reach):
             b1, b2 = group["betas"]
-            wd = float(group.get("weight_decay", 0.0))
-            for t, plist in by_step.items():
-                # coupled L2 decay (g*grad_scale + wd*p) inside the kernel: p.grad is left as the caller's
-                self._launch(plist, t, float(group["lr"]), b1, b2, group["eps"], wd, coupled=wd > 0.0 and not self.decoupled)
+            # coupled L2 decay (g*grad_scale + wd*p) inside the kernel: p.grad is left as the caller's
+            self._launch(plist, t, float(group["lr"]), b1, b2, group["eps"], wd, coupled)
         return loss
 
     def _launch(self, plist, t, lr, b1, b2, eps, weight_decay=0.0, coupled=False):
-        dev = plist[0].device
         lib = ops._lib_for(plist[0])
-        n = len(plist)
-        rows = []
-        max_n = 0
-        for p in plist:
-            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-            if not p.is_contiguous():
-                raise RuntimeError("FusedAdam: non-contiguous parameter")
-            st = self.state[p]
-            rows.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()))
-            max_n = max(max_n, p.numel())
-            p._dei2i_keep = g          # keep a possibly-copied grad alive until the launch is enqueued
-        # the device pointer table is rebuilt and uploaded only when a pointer moved (in steady state the caching allocator hands
-        # every gradient the address it had the step before)
-        cache = self.__dict__.setdefault("_table_cache", {})
-        key = (dev, n, rows[0][0])
-        hit = cache.get(key)
-        if hit is not None and hit[0] == rows:
-            table_dev = hit[1]
-        else:
-            table = torch.empty((n, 5), dtype=torch.int64, pin_memory=True)
-            table.copy_(torch.tensor(rows, dtype=torch.int64))
-            table_dev = table.to(dev, non_blocking=True)
-            cache[key] = (rows, table_dev)
+        table = self._table(plist)
+        table_dev = table.cached(self.__dict__.setdefault("_table_cache", {}))
         step = lib.dei2i_adam_step_l2 if coupled else lib.dei2i_adam_step
-        L.check(step(ctypes.c_void_p(table_dev.data_ptr()), n, max_n, lr, b1, b2, eps, 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t),
-                     self.grad_scale, weight_decay, ops._stream()), "adam_step")
-        for p in plist:
-            p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1      # raw-pointer update: invalidate packed copies
-            p._dei2i_keep = None
-
+        L.check(step(*table.args(table_dev), lr, b1, b2, eps, 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), self.grad_scale,
+                     weight_decay, ops._stream()), "adam_step")
+        ops.mark_written(*plist)
 
     # ---- graph capture ------------------------------------------------------------------------------------------------
     def _step_captured(self):
@@ -104,47 +128,32 @@ class FusedAdam(torch.optim.Optimizer):
         ``_dev`` launch + one index advance per group.  Host state (``state["step"]``) is left to ``graph_finish``: the
         capture runs nothing.  The pointer tables are uploaded after the capture (``graph_prepare``): the gradients they
         point to are the graph's own, at fixed addresses from replay to replay."""
+        def reach(p, st):
+            if len(st) == 0:       # zeros_like inside the capture would reset the moments on every replay
+                raise RuntimeError("FusedAdam: a parameter received its first gradient while a graph was being captured "
+                                   "(capture after the set of parameters with a gradient has settled: raise graph_warmup)")
+            return st["step"] + 1
+
         plan = self.__dict__.setdefault("_graph_plan", [])
-        for gi, group in enumerate(self.param_groups):
-            by_step = {}
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                ops._require_gpu(p, "FusedAdam")
-                if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_contiguous():
-                    raise TypeError("FusedAdam expects contiguous fp32 parameters and fp32 gradients")
-                st = self.state[p]
-                if len(st) == 0:       # zeros_like inside the capture would reset the moments on every replay
-                    raise RuntimeError("FusedAdam: a parameter received its first gradient while a graph was being captured "
-                                       "(capture after the set of parameters with a gradient has settled: raise graph_warmup)")
-                by_step.setdefault(st["step"] + 1, []).append(p)
+        for gi, group, t, plist, wd, coupled in self._launch_groups(reach):
+            lib = ops._lib_for(plist[0])
+            table = self._table(plist)
+            # (reserved before the capture: a buffer allocated inside it comes from the graph's pool, whose blocks earlier
+            #  nodes of the same replay may use as scratch -- they would overwrite what graph_prepare uploaded)
+            slots = self.__dict__.get("_graph_reserve", {}).get(gi)
+            if not slots:
+                raise RuntimeError("FusedAdam: no table reserved for this group (call graph_reserve() before the capture)")
+            table_dev, hyper = slots.pop(0)
+            hyper.t0 = hyper.t = t
+            hyper.key = None
             b1, b2 = group["betas"]
-            wd = float(group.get("weight_decay", 0.0))
-            coupled = wd > 0.0 and not self.decoupled
-            for t, plist in by_step.items():
-                lib = ops._lib_for(plist[0])
-                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in plist]
-                rows = [(p.data_ptr(), g.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(),
-                         p.numel()) for p, g in zip(plist, grads)]
-                # (reserved before the capture: a buffer allocated inside it comes from the graph's pool, whose blocks earlier
-                #  nodes of the same replay may use as scratch -- they would overwrite what graph_prepare uploaded)
-                slots = self.__dict__.get("_graph_reserve", {}).get(gi)
-                if not slots:
-                    raise RuntimeError("FusedAdam: no table reserved for this group (call graph_reserve() before the capture)")
-                table_dev, hyper = slots.pop(0)
-                hyper.t0 = hyper.t = t
-                hyper.key = None
-                L.check(lib.dei2i_adam_step_l2_dev(ctypes.c_void_p(table_dev.data_ptr()), len(rows), max(r[4] for r in rows),
-                                                   ctypes.c_void_p(hyper.table.data_ptr()), ctypes.c_void_p(hyper.index.data_ptr()),
-                                                   hyper.rows, b1, b2, group["eps"], self.grad_scale, wd, ops._stream())
-                        if coupled else
-                        lib.dei2i_adam_step_dev(ctypes.c_void_p(table_dev.data_ptr()), len(rows), max(r[4] for r in rows),
-                                                ctypes.c_void_p(hyper.table.data_ptr()), ctypes.c_void_p(hyper.index.data_ptr()),
-                                                hyper.rows, b1, b2, group["eps"], self.grad_scale, ops._stream()), "adam_step_dev")
-                L.check(lib.dei2i_index_advance(ctypes.c_void_p(hyper.index.data_ptr()), ops._stream()), "index_advance")
-                plan.append(_CapturedGroup(gi, plist, grads, rows, table_dev, hyper, 0.0 if coupled else wd))
-                for p in plist:
-                    p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1      # later passes of the capture must repack
+            dev_args = (*table.args(table_dev), ctypes.c_void_p(hyper.table.data_ptr()), ctypes.c_void_p(hyper.index.data_ptr()),
+                        hyper.rows, b1, b2, group["eps"], self.grad_scale)
+            L.check(lib.dei2i_adam_step_l2_dev(*dev_args, wd, ops._stream()) if coupled else
+                    lib.dei2i_adam_step_dev(*dev_args, ops._stream()), "adam_step_dev")
+            L.check(lib.dei2i_index_advance(ctypes.c_void_p(hyper.index.data_ptr()), ops._stream()), "index_advance")
+            plan.append(_CapturedGroup(gi, plist, table, table_dev, hyper, 0.0 if coupled else wd))
+            ops.mark_written(*plist)      # later passes of the capture must repack
 
     def graph_reserve(self):
         """Before a capture: device tables for every launch group the captured step can make (one per distinct step count
@@ -168,9 +177,9 @@ class FusedAdam(torch.optim.Optimizer):
         """Before a replay of a graph holding ``plan``: the rows of every group cover this step with the current lr
         (a stream-ordered upload only when they do not)."""
         for g in plan:
-            if g.rows is not None:
-                g.upload()
-                g.rows = None
+            if not g.uploaded:
+                g.table.upload(into=g.table_dev)      # (a reserved slot: rows for the whole group)
+                g.uploaded = True
             group = self.param_groups[g.group]
             b1, b2 = group["betas"]
             # (the step from the state, not the mirror: an eager call between two replays has advanced it)
@@ -182,7 +191,7 @@ class FusedAdam(torch.optim.Optimizer):
             g.hyper.advance()
             for p in g.params:
                 self.state[p]["step"] += 1
-                p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1
+            ops.mark_written(*g.params)
 
 
 HYPER_ROWS = 4096
@@ -235,49 +244,34 @@ class _HyperTable:
 
 
 class _CapturedGroup:
-    """One recorded launch group.  ``rows``: its pointer table on the host until ``graph_prepare`` has uploaded it once
-    (then None).  The ``_dei2i_epoch`` stamps move at capture, so the rest of the capture repacks, and again after every
-    replay, so eager code repacks."""
-    __slots__ = ("group", "params", "grads", "rows", "table_dev", "hyper", "wd")
+    """One recorded launch group.  ``table``: its pointer table on the host (holding the graph's own gradients), which
+    ``graph_prepare`` uploads into ``table_dev`` once, after the capture and before the first replay.  The raw-write stamps
+    (``ops.mark_written``) move at capture, so the rest of the capture repacks, and again after every replay, so eager code
+    repacks."""
+    __slots__ = ("group", "params", "table", "table_dev", "hyper", "wd", "uploaded")
 
-    def __init__(self, group, params, grads, rows, table_dev, hyper, wd):
-        self.group, self.params, self.grads, self.rows, self.table_dev, self.hyper, self.wd = \
-            group, params, grads, rows, table_dev, hyper, wd
-
-    def upload(self):
-        """The pointer table, after the capture and before the first replay (stream-ordered)."""
-        host = torch.tensor(self.rows, dtype=torch.int64).pin_memory()
-        self.table_dev[:len(self.rows)].copy_(host, non_blocking=True)      # (a reserved slot: rows for the whole group)
+    def __init__(self, group, params, table, table_dev, hyper, wd):
+        self.group, self.params, self.table, self.table_dev, self.hyper, self.wd = group, params, table, table_dev, hyper, wd
+        self.uploaded = False
 
 
 def ema_lerp_(ema_params, params, weight):
     """``e.copy_(torch.lerp(p, e, weight))`` for every pair, in place, one launch (stargan-v2 moving_average, core/solver.py:549-551).
-    Every updated tensor's ``_dei2i_epoch`` is bumped: the packed-weight caches of the EMA network are keyed on it."""
+    Every updated tensor is stamped (``ops.mark_written``): the packed-weight caches of the EMA network are keyed on it."""
     ema_params, params = list(ema_params), list(params)
     if len(ema_params) != len(params):
         raise ValueError("ema_lerp_: parameter lists differ in length")
     if not params:
         return
-    rows, max_n = [], 0
     for e, p in zip(ema_params, params):
-        ops._require_gpu(e, "ema_lerp_")
-        if e.dtype != torch.float32 or p.dtype != torch.float32 or e.shape != p.shape or not e.is_contiguous() or not p.is_contiguous():
+        if e.shape != p.shape or not p.is_contiguous():
             raise TypeError("ema_lerp_ expects pairs of contiguous fp32 tensors of one shape")
         if e.device != p.device:
             raise ValueError("ema_lerp_: the EMA copy and the parameter are on different devices")
-        rows.append((e.data_ptr(), p.data_ptr(), 0, 0, p.numel()))
-        max_n = max(max_n, p.numel())
-    dev = ema_params[0].device
-    hit = _ema_tables.get((dev, rows[0][0], len(rows)))
-    if hit is not None and hit[0] == rows:
-        table_dev = hit[1]
-    else:
-        table_dev = torch.tensor(rows, dtype=torch.int64).to(dev)
-        _ema_tables[(dev, rows[0][0], len(rows))] = (rows, table_dev)
+    table = _PointerTable("ema_lerp_", [(e, p, None, None) for e, p in zip(ema_params, params)])
     lib = ops._lib_for(ema_params[0])
-    L.check(lib.dei2i_ema_lerp(ctypes.c_void_p(table_dev.data_ptr()), len(rows), max_n, float(weight), ops._stream()), "ema_lerp")
-    for e in ema_params:
-        e._dei2i_epoch = getattr(e, "_dei2i_epoch", 0) + 1      # raw-pointer update: invalidate packed copies
+    L.check(lib.dei2i_ema_lerp(*table.args(table.cached(_ema_tables)), float(weight), ops._stream()), "ema_lerp")
+    ops.mark_written(*ema_params)
 
 
 _ema_tables = {}
@@ -305,33 +299,24 @@ class _FusedPlain(torch.optim.Optimizer):
             plist = [p for p in group["params"] if p.grad is not None]
             if not plist:
                 continue
-            dev = plist[0].device
             lib = ops._lib_for(plist[0])
-            rows, max_n = [], 0
-            for p in plist:
-                ops._require_gpu(p, type(self).__name__)
-                if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_contiguous():
-                    raise TypeError(f"{type(self).__name__} expects contiguous fp32 parameters and fp32 gradients")
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                st = self.state[p]
-                if self.KIND == 1 and len(st) == 0:
-                    st["step"] = 0
-                    st["square_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                if self.KIND == 1:
-                    st["step"] += 1
-                aux = st["square_avg"].data_ptr() if self.KIND == 1 else 0
-                rows.append((p.data_ptr(), g.data_ptr(), aux, 0, p.numel()))
-                max_n = max(max_n, p.numel())
-                p._dei2i_keep = g
-            table = torch.tensor(rows, dtype=torch.int64).to(dev)
-            L.check(lib.dei2i_sgd_rmsprop_step(ctypes.c_void_p(table.data_ptr()), len(rows), max_n, self.KIND, float(group["lr"]),
-                                               float(group.get("alpha", 0.0)), float(group.get("eps", 0.0)), self.grad_scale,
-                                               ops._stream()), "sgd_rmsprop_step")
-            for p in plist:
-                p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1      # raw-pointer update: invalidate packed copies
-                p._dei2i_keep = None
-            self._table_keep = table           # (alive until the next step's launch is enqueued)
+            table = _PointerTable(type(self).__name__, [(p, p.grad, self._square_avg(p), None) for p in plist])
+            table_dev = table.cached(self.__dict__.setdefault("_table_cache", {}))
+            L.check(lib.dei2i_sgd_rmsprop_step(*table.args(table_dev), self.KIND, float(group["lr"]), float(group.get("alpha", 0.0)),
+                                               float(group.get("eps", 0.0)), self.grad_scale, ops._stream()), "sgd_rmsprop_step")
+            ops.mark_written(*plist)
         return loss
+
+    def _square_avg(self, p):
+        """RMSprop's state of ``p``, made on its first step and counted (None for SGD, which has none)"""
+        if self.KIND != 1:
+            return None
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = 0
+            st["square_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        st["step"] += 1
+        return st["square_avg"]
 
 
 class FusedSGD(_FusedPlain):

@@ -236,8 +236,8 @@ class GradReducer:
                     n = t.numel()
                     t.copy_(flat[off:off + n].view_as(t))
                     off += n
-            for p in list(net.parameters()) + list(net.buffers()):
-                p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1
+            from . import ops
+            ops.mark_written(*net.parameters(), *net.buffers())
 
     def sync_bn_exchange(self, msg: torch.Tensor) -> None:
         """SUM ``msg`` (one BatchNorm layer's fp64 statistics message, ops.bn_sync) over the ranks in place, ordered on the current

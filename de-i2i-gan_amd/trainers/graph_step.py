@@ -162,8 +162,7 @@ class GraphStep:
             o.graph_take_plan()
             o.graph_reserve()
         for net in self._trained_modules():
-            for p in net.parameters():
-                p._dei2i_epoch = getattr(p, "_dei2i_epoch", 0) + 1
+            ops.mark_written(*net.parameters())
         if hasattr(tr.model, "_label_sets"):
             tr.model._label_sets = None
         keep = list(ops._workspaces.values())        # the graph writes them by address: they must outlive it

@@ -231,6 +231,17 @@ def test_mse_target_forms_and_refusals(ops):
         ops.mse(torch.zeros(4), 0.0)
 
 
+def test_l1_refuses_a_shorter_target(ops):
+    """A ``b`` of fewer elements than ``a`` is refused (the kernel would read ``a.numel()`` elements of it); without ``b``, and with
+    one of ``a``'s size, the value is float64's: small integers and n = 8, so every sum and the 1 / n are exact in fp32."""
+    a = (torch.arange(8, dtype=torch.float32) - 3).view(2, 4)
+    b = torch.ones(8).view(2, 4)
+    with pytest.raises(ValueError, match="target size"):
+        ops.l1(a.to(dev()), torch.ones(4, device=dev()))
+    assert ops.l1(a.to(dev()), None).item() == a.double().abs().mean().item()
+    assert ops.l1(a.to(dev()), b.to(dev())).item() == (a.double() - b.double()).abs().mean().item()
+
+
 # ---- state and reproducibility ----------------------------------------------------------------------------------------------
 def test_smaller_call_after_larger_does_not_read_stale_partials(ops):
     """The block partials live in one process-wide buffer that is never cleared: (1025, 6) leaves 257 partials, (2, 6) must read one;
