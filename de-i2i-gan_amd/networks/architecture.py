@@ -320,6 +320,26 @@ class ResBlock(nn.Module):
         return second(h, res=x, out_stats=out_stats)           # identity add fused into the BatchNorm-apply kernel
 
 
+def _class_norm_conv(x, conv, up, skip, stats, table, table_grad, norm):
+    """conv(norm(x)) -- with skip: (that, x) -- for the norm layers that run on the SPADE kernels (SPADE, AdaIN, SEAN): the
+    InstanceNorm apply + modulate + ReLU (+ upsample) fused into ``conv`` (ops.spade_conv) when the layer modulates from a class
+    table, the conv is a plain one without bias and the kernels take the shape; the two-kernel form ``conv(norm(skip))`` otherwise.
+    ``table``: () -> the (N, 5, 5, 2C) class table, called only on the fused path (None: this call has no class table);
+    ``table_grad``: a backward pass will reach the table; ``norm``: (skip) -> the layer's own unfused call."""
+    if table is not None and isinstance(conv, Conv2d) and conv.bias is None:
+        geom = conv.geom(up)
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or table_grad or any(p.requires_grad for p in conv.parameters()))
+        mode = ops.spade_conv_supported(x, None, geom, need_grad)
+        if mode is not None:
+            gb = table()
+            wt, sources = conv.effective_weight()         # (a spectral conv iterates u, v here: once per forward, like conv(...))
+            return ops.spade_conv(x, gb, wt, conv._packed, geom, skip=skip, stats=stats, mode=mode, sources=sources)
+    if skip:
+        z, xs = norm(True)
+        return conv(z, stats=stats), xs
+    return conv(norm(False), stats=stats)
+
+
 class SPADE(nn.Module):
     """normalization.py:10-37.  ``forward`` returns relu(IN(x)*(1+gamma)+beta) -- every reference call site
     applies ReLU right after (architecture.py:244,346-347), so it is fused; a preceding nearest x2 upsample of x
@@ -356,24 +376,20 @@ class SPADE(nn.Module):
         """conv(self(x, segmap, up)) -- with skip: (that, x) -- the InstanceNorm apply + modulate + ReLU (+ upsample) on
         ``conv``'s operand path when the label map is constant and the kernels take the shape (ops.spade_conv); the
         two-kernel formulation otherwise."""
-        prec = ops.precision_of(x)
+        class_mode, h, w = self._class_mode(x, segmap, up)
+
+        def table():
+            self._ran_class_mode = True
+            return self._class_table(segmap, ops.precision_of(x), h, w)
+        return _class_norm_conv(x, conv, up, skip, stats, table if class_mode else None, self.mlp_gamma.weight.requires_grad,
+                                lambda skip: self(x, segmap, up=up, skip=skip))
+
+    @staticmethod
+    def _class_mode(x, segmap, up):
+        """-> (a constant label map and room for the 2-pixel border: gamma / beta as the 5x5 class table?, h, w of the (upsampled) x)"""
         n, hs, ws, c = x.shape
         h, w = (2 * hs, 2 * ws) if up else (hs, ws)
-        class_mode = segmap.shape[2] == 1 and segmap.shape[3] == 1 and h >= 4 and w >= 4
-        if class_mode and isinstance(conv, Conv2d) and conv.bias is None:
-            geom = conv.geom(up)
-            params_grad = any(p.requires_grad for p in conv.parameters()) or self.mlp_gamma.weight.requires_grad
-            need_grad = torch.is_grad_enabled() and (x.requires_grad or params_grad)
-            mode = ops.spade_conv_supported(x, None, geom, need_grad)
-            if mode is not None:
-                self._ran_class_mode = True
-                gb = self._class_table(segmap, prec, h, w)
-                wt, sources = conv.effective_weight()         # (a spectral conv iterates u, v here: once per forward, like conv(...))
-                return ops.spade_conv(x, gb, wt, conv._packed, geom, skip=skip, stats=stats, mode=mode, sources=sources)
-        if skip:
-            z, xs = self(x, segmap, up=up, skip=True)
-            return conv(z, stats=stats), xs
-        return conv(self(x, segmap, up=up), stats=stats)
+        return segmap.shape[2] == 1 and segmap.shape[3] == 1 and h >= 4 and w >= 4, h, w
 
     def _class_table(self, segmap, prec, h, w):
         # The class table depends only on (label map, this module's weights), not on x: the loss graphs call G several
@@ -393,9 +409,7 @@ class SPADE(nn.Module):
 
     def forward(self, x, segmap, up=False, skip=False):
         prec = ops.precision_of(x)
-        n, hs, ws, c = x.shape
-        h, w = (2 * hs, 2 * ws) if up else (hs, ws)
-        class_mode = segmap.shape[2] == 1 and segmap.shape[3] == 1 and h >= 4 and w >= 4
+        class_mode, h, w = self._class_mode(x, segmap, up)
         self._ran_class_mode = class_mode                 # prime() only serves modules that run (norm_s never does)
         if not class_mode:
             return ops.spade_relu(x, self._gamma_beta(segmap, prec, False, h, w), up, 0, skip=skip)
@@ -420,12 +434,8 @@ class SPADE(nn.Module):
         # (before the generator's first forward nobody knows which modules run -- norm_s of a block without a learned shortcut never
         #  does --: all are served then, so that the first step takes the same kernels as every later one; the generator marks the
         #  modules its first forward did not reach)
-        if not getattr(self, "_ran_class_mode", True):
+        if not self.wants_prime(segmaps, prec):          # (e.g. both tables are there already: same tensors, same parameter state)
             return
-        if len(segmaps) not in (1, 2) or any(s.dim() != 4 or s.shape[2] != 1 or s.shape[3] != 1 for s in segmaps):
-            return
-        if all(self._table_key(sgm, prec) in self._gb_cache for sgm in segmaps):
-            return                                       # both tables are there already (same tensors, same parameter state)
         if gb is None:        # (else: prime_spade computed this module's table in the batched launch, ops.label_gamma_beta)
             gb = self._gamma_beta(both if both is not None else torch.cat(list(segmaps), 0), prec, True, 0, 0, seg=seg, actv=actv)
         self._gb_cache.clear()
@@ -460,19 +470,8 @@ class AdaIN(nn.Module):
 
     def fused_conv(self, x, style_feat, conv, up=False, skip=False, stats=False):
         """conv(self(x, style_feat, up)) -- with skip: (that, x) -- see SPADE.fused_conv"""
-        prec = ops.precision_of(x)
-        gb = self._class_table(style_feat, prec, x.shape[-1])
-        if isinstance(conv, Conv2d) and conv.bias is None:
-            geom = conv.geom(up)
-            need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in conv.parameters()) or gb.requires_grad)
-            mode = ops.spade_conv_supported(x, None, geom, need_grad)
-            if mode is not None:
-                wt, sources = conv.effective_weight()
-                return ops.spade_conv(x, gb, wt, conv._packed, geom, skip=skip, stats=stats, mode=mode, sources=sources)
-        if skip:
-            z, xs = ops.spade_relu(x, gb, up, 1, skip=True)
-            return conv(z, stats=stats), xs
-        return conv(ops.spade_relu(x, gb, up, 1), stats=stats)
+        gb = self._class_table(style_feat, ops.precision_of(x), x.shape[-1])
+        return _class_norm_conv(x, conv, up, skip, stats, lambda: gb, gb.requires_grad, lambda skip: ops.spade_relu(x, gb, up, 1, skip=skip))
 
     def forward(self, x, style_feat, up=False, skip=False):
         return ops.spade_relu(x, self._class_table(style_feat, ops.precision_of(x), x.shape[-1]), up, 1, skip=skip)

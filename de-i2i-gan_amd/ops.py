@@ -22,6 +22,9 @@ import torch
 from . import _lib as L
 
 ACT = {"none": L.ACT_NONE, None: L.ACT_NONE, "relu": L.ACT_RELU, "leaky_relu": L.ACT_LRELU}
+# the ReLU family as a negative-side slope (what the per-image affine, the operand-path and the SPADE backward kernels take)
+ACT_SLOPE = {L.ACT_NONE: 1.0, L.ACT_RELU: 0.0, L.ACT_LRELU: 0.2}
+_SLOPE_ACT = {slope: act for act, slope in ACT_SLOPE.items()}
 
 
 @dataclass(frozen=True)
@@ -49,19 +52,26 @@ FP8_ACT_SCALE = 16.0
 _fp8_forward = False
 
 
-class fp8_forward:
-    def __init__(self, on: bool):
-        self.on = bool(on)
+class _GlobalScope:
+    """``with`` scope of a module-level switch: sets the module global named ``var`` to ``self.value`` for the block and puts the
+    previous value back on exit.  The switches stay plain module attributes (tests and the benchmark read them)."""
+    var = None
 
     def __enter__(self):
-        global _fp8_forward
-        self.prev, _fp8_forward = _fp8_forward, self.on
+        g = globals()
+        self.prev, g[self.var] = g[self.var], self.value
         return self
 
     def __exit__(self, *exc):
-        global _fp8_forward
-        _fp8_forward = self.prev
+        globals()[self.var] = self.prev
         return False
+
+
+class fp8_forward(_GlobalScope):
+    var = "_fp8_forward"
+
+    def __init__(self, on: bool):
+        self.value = bool(on)
 
 
 # fused conv + norm + act (halo-resident kernels).  Run-time switches for same-box A/B timing and for the parity tests of
@@ -129,6 +139,16 @@ def _require_gpu(t: torch.Tensor, what: str) -> None:
 
 def _p(t: Optional[torch.Tensor]):
     return None if t is None else c_void_p(t.data_ptr())
+
+
+def _f32c(t: torch.Tensor, strict: str = None) -> torch.Tensor:
+    """``t`` as a kernel reads an fp32 operand through its raw pointer: ``t`` itself when it is fp32 and contiguous, else a converted
+    copy -- or, with ``strict`` (the op's name), a TypeError: the ops that write derived weights do not convert."""
+    if t.dtype == torch.float32 and t.is_contiguous():
+        return t
+    if strict is not None:
+        raise TypeError(f"{strict} expects a contiguous fp32 weight")
+    return t.float().contiguous()
 
 
 # The current stream's handle straight from the C layer: ``torch.cuda.current_stream()`` builds a Stream object per call (~8 us of host
@@ -243,9 +263,7 @@ class _SpectralWeight(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight_orig, u, v, iterate: bool):
         _require_gpu(weight_orig, "spectral_weight")
-        w = weight_orig.detach()
-        if w.dtype != torch.float32 or not w.is_contiguous():
-            raise TypeError("spectral_weight expects a contiguous fp32 weight")
+        w = _f32c(weight_orig.detach(), strict="spectral_weight")
         cout, k = w.shape[0], w[0].numel()
         lib = _lib_for(w)
         dev = w.device
@@ -293,9 +311,7 @@ def fold_bn_weight(weight, bn_weight, bn_bias, running_mean, running_var, eps: f
     """-> (w_eff = a[co] * weight[co], b_eff = bn_bias - running_mean * a) with a = bn_weight * rsqrt(running_var + eps); no
     autograd (eval / no-grad passes only).  ``w_eff`` is marked as derived per call: its packed copy travels with the call."""
     _require_gpu(weight, "fold_bn_weight")
-    w = weight.detach()
-    if w.dtype != torch.float32 or not w.is_contiguous():
-        raise TypeError("fold_bn_weight expects a contiguous fp32 weight")
+    w = _f32c(weight.detach(), strict="fold_bn_weight")
     cout, k = w.shape[0], w[0].numel()
     w_eff, b_eff = torch.empty_like(w), torch.empty(cout, dtype=torch.float32, device=w.device)
     L.check(_lib_for(w).dei2i_fold_bn_weight(cout, k, _p(w), _p(bn_weight.detach()), _p(bn_bias.detach()), _p(running_mean), _p(running_var),
@@ -449,25 +465,20 @@ class PackedWeights:
         if key != self._key:
             self._key, self.fwd, self.dgrad, self.fp8 = key, None, None, None
         d = _desc(prec, geom, 1, max(geom.k, 4), max(geom.k, 4), cins, couts)
-        w = weight.detach()
-        if w.dtype != torch.float32 or not w.is_contiguous():
-            w = w.float().contiguous()
+        w = _f32c(weight.detach())
         self._await_pack()            # (copies packed by a launch on ANOTHER stream: the two chains of a forked pass share weights)
-        packed = False
-        if need_fwd and need_dgrad and self.fwd is None and self.dgrad is None:       # the training path: one launch
-            self.fwd = torch.empty(lib.dei2i_packed_fwd_elems(byref(d)), dtype=prec.dtype, device=weight.device)
-            self.dgrad = torch.empty(lib.dei2i_packed_dgrad_elems(byref(d)), dtype=prec.dtype, device=weight.device)
-            L.check(lib.dei2i_pack_weight_both(byref(d), _p(w), _p(self.fwd), _p(self.dgrad), _stream()), "pack_weight_both")
-            packed = True
-        if need_fwd and self.fwd is None:
-            self.fwd = torch.empty(lib.dei2i_packed_fwd_elems(byref(d)), dtype=prec.dtype, device=weight.device)
-            L.check(lib.dei2i_pack_weight_fwd(byref(d), _p(w), _p(self.fwd), _stream()), "pack_weight_fwd")
-            packed = True
-        if need_dgrad and self.dgrad is None:
-            self.dgrad = torch.empty(lib.dei2i_packed_dgrad_elems(byref(d)), dtype=prec.dtype, device=weight.device)
-            L.check(lib.dei2i_pack_weight_dgrad(byref(d), _p(w), _p(self.dgrad), _stream()), "pack_weight_dgrad")
-            packed = True
-        if packed:
+
+        def alloc(layout):
+            t = torch.empty(getattr(lib, f"dei2i_packed_{layout}_elems")(byref(d)), dtype=prec.dtype, device=weight.device)
+            setattr(self, layout, t)
+            return t
+        missing = [layout for layout, need in (("fwd", need_fwd), ("dgrad", need_dgrad)) if need and getattr(self, layout) is None]
+        if len(missing) == 2:                                                         # the training path: one launch
+            L.check(lib.dei2i_pack_weight_both(byref(d), _p(w), _p(alloc("fwd")), _p(alloc("dgrad")), _stream()), "pack_weight_both")
+        else:
+            for layout in missing:
+                L.check(getattr(lib, "dei2i_pack_weight_" + layout)(byref(d), _p(w), _p(alloc(layout)), _stream()), "pack_weight_" + layout)
+        if missing:
             self._mark_packed()
         return self.fwd, self.dgrad
 
@@ -480,9 +491,7 @@ class PackedWeights:
         if self.fp8 is None:
             lib = _lib_for(weight)
             d = _desc(prec, geom, 1, 8, 32, cins, couts)
-            w = weight.detach()
-            if w.dtype != torch.float32 or not w.is_contiguous():
-                w = w.float().contiguous()
+            w = _f32c(weight.detach())
             amax = torch.linalg.vector_norm(w, ord=float("inf")).reshape(1)
             wq = torch.empty(geom.cout * geom.k * geom.k * cins, dtype=torch.uint8, device=weight.device)
             dequant = torch.empty(1, dtype=torch.float32, device=weight.device)
@@ -501,6 +510,14 @@ def _stats_of(t, n, hw, c):
     if partial.shape != (n, chunks, 2, c) or partial.device != t.device:
         return None
     return partial, chunks
+
+
+def _leave_stats(n, chunks, c, device):
+    """-> fresh (N, chunks, 2, C) fp32 records for the kernel about to write a tensor AND its per-channel moments, left for the norm
+    layer that reads that tensor next (the public wrapper moves them onto the output: _attach; _stats_of reads them)."""
+    partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=device)
+    _handover["_dei2i_stats"] = (partial, chunks)
+    return partial
 
 
 def _moment_records(lib, prec, x, n, hw, c):
@@ -524,17 +541,33 @@ def _in_stats(lib, prec, x, n, hw, c, eps):
     return mean, rstd
 
 
-def _img_affine_act(lib, prec, x, a, b, slope):
-    """-> act(a[n, c] * x + b[n, c]) in one pass over the NHWC tensor ``x``; a, b (N, C) fp32; slope: 0.2 LeakyReLU, 0 ReLU, 1 none"""
-    n, h, w, c = x.shape
+def _affine_act(lib, prec, x, a, b, res, act, groups=1, stats=None, xq=None, xq_scale=1.0, what="affine_act"):
+    """-> act(a[g, c] * x + b[g, c] (+ res)) in one launch over the contiguous (..., C) tensor ``x``: ``groups`` equal row groups with
+    coefficient rows a, b (groups, C) fp32.  ``stats``: the (N, chunks, 2, C) records the launch fills with the output's per-image
+    moments (x is NHWC then; see _leave_stats), or ``xq``: uint8 storage for an e4m3 copy of the output times ``xq_scale`` (fp8_forward)."""
+    c = x.shape[-1]
+    if not isinstance(a, torch.Tensor):               # two python numbers: the same coefficients for every channel
+        a, b = _const_vec(x.device, c, a), _const_vec(x.device, c, b)
     out = torch.empty_like(x)
-    cv = c // (8 if prec is BF16 else 4)
-    if 256 % cv == 0 or cv % 256 == 0:                # (the per-image kernel keeps one channel vector per thread)
-        L.check(lib.dei2i_affine_act_img_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), slope, _p(out), _stream()), "affine_act_img")
-    else:                                             # odd channel counts: the per-channel kernel, one group per image
-        act = {1.0: L.ACT_NONE, 0.0: L.ACT_RELU, 0.2: L.ACT_LRELU}[slope]
-        L.check(lib.dei2i_affine_act_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), None, act, _p(out), None, 1.0, _stream()), "affine_act")
+    if stats is not None:
+        n = x.shape[0]
+        L.check(lib.dei2i_affine_act_stats_fwd(prec.code, groups, n, x.numel() // (n * c), c, _p(x), _p(a), _p(b), _p(res), act, _p(out),
+                                               _p(stats), _stream()), what)
+    else:
+        L.check(lib.dei2i_affine_act_fwd(prec.code, groups, x.numel() // (groups * c), c, _p(x), _p(a), _p(b), _p(res), act, _p(out),
+                                         _p(xq), xq_scale, _stream()), what)
     return out
+
+
+def _img_affine_act(lib, prec, x, a, b, slope):
+    """-> act(a[n, c] * x + b[n, c]) in one pass over the NHWC tensor ``x``; a, b (N, C) fp32; slope: see ACT_SLOPE"""
+    n, h, w, c = x.shape
+    cv = c // prec.vec
+    if 256 % cv == 0 or cv % 256 == 0:                # (the per-image kernel keeps one channel vector per thread)
+        out = torch.empty_like(x)
+        L.check(lib.dei2i_affine_act_img_fwd(prec.code, n, h * w, c, _p(x), _p(a), _p(b), slope, _p(out), _stream()), "affine_act_img")
+        return out
+    return _affine_act(lib, prec, x, a, b, None, _SLOPE_ACT[slope], groups=n)     # odd channel counts: the per-channel kernel, one group per image
 
 
 class _NormBwdHint:
@@ -572,6 +605,66 @@ class _NormBwdHint:
 
 
 bwd_fused_counts = {"epilogue": 0, "taken": 0}   # dgrad launches that took the reductions / norm backwards that used them (tests)
+
+
+def _sources(sources, weight):
+    """The parameters a conv's ``weight`` is made of (their stamps key its packed copies): the weight itself unless the caller says"""
+    return tuple(sources) if sources is not None else (weight,)
+
+
+def _packing(weight, cache, sources, input_grad=False):
+    """-> (cache, per_call, need_dgrad) of a conv forward.  per_call: a weight derived anew for THIS call (spectral norm in training
+    mode, an eval-folded BatchNorm) -- its packed copies travel with the call (a fresh cache, kept on ctx), not with the module,
+    whose single slot the next call would overwrite before this call's backward asks for the dgrad layout.  need_dgrad: trainable
+    sources (a backward pass of this optimizer step will want that layout, also when THIS call is the D step's no-grad generator
+    pass) or ``input_grad`` (a frozen weight behind an input that needs a gradient: D inside the G step) -> both in one pack launch."""
+    per_call = bool(getattr(weight, "_dei2i_per_call", False))
+    if per_call:
+        cache = PackedWeights()
+    return cache, per_call, input_grad or any(s_.requires_grad for s_ in sources)
+
+
+def _conv_out(lib, d, n, couts, prec, device):
+    """-> the uninitialised (N, Ho, Wo, CoutS) output of the conv ``d``"""
+    ho, wo = c_int(), c_int()
+    lib.dei2i_conv2d_out_shape(byref(d), byref(ho), byref(wo))
+    return torch.empty((n, ho.value, wo.value, couts), dtype=prec.dtype, device=device)
+
+
+def _bn_pro(a, b, act):
+    """-> (ProDesc, the tensors it points into): BatchNorm apply + activation on a conv's operand path (see _BnActConv)"""
+    return L.ProDesc(a.data_ptr(), b.data_ptr(), 0, ACT_SLOPE[act], None), (a, b)
+
+
+def _spade_pro(coefs, ring, c, ring_mode=False):
+    """-> (ProDesc, the tensors it points into) of _SpadeConv: the interior coefficients A | B = coefs[2] | coefs[3] and the frame's
+    ring tensor; ``ring_mode``: the conv's input is normalised already, only the ring is read"""
+    if ring_mode:
+        return L.ProDesc(None, None, 0, 0.0, ring.data_ptr()), (ring,)
+    return L.ProDesc(coefs[2].data_ptr(), coefs[3].data_ptr(), c, 0.0, ring.data_ptr()), (coefs, ring)
+
+
+def _skip_forward(op, x, gb, skip, up):
+    """-> (x, gb) contiguous.  ``skip``: the op also hands x through as a second output (the res block's identity branch: its gradient
+    is then added inside the backward-apply kernel, not by a separate autograd add launch) -- x must be the tensor the kernels read"""
+    xc = x.contiguous()
+    if skip and (up or xc is not x):
+        raise ValueError(f"{op}(skip=True) wants a contiguous activation and no upsample")
+    return xc, gb.contiguous()
+
+
+def _skip_backward(op, dskip, x):
+    """-> the identity branch's gradient as the backward-apply kernel adds it to dx (None: that branch was not used)"""
+    if dskip is not None:
+        dskip = dskip.contiguous()
+        if dskip.dtype != x.dtype or dskip.shape != x.shape:
+            raise RuntimeError(f"{op}: identity-branch gradient does not match the activation")
+    return dskip
+
+
+def _attach_skip(result, skip):
+    """_attach for an op called with ``skip``: its Function returned (out, x) then, and the handover belongs on out"""
+    return (_attach(result[0]), result[1]) if skip else _attach(result)
 
 
 def _conv_dgrad(lib, prec, geom, x_shape, couts, g, weight, cache, sources, per_call, dtype, device, hint=None):
@@ -798,24 +891,11 @@ class _Conv2d(torch.autograd.Function):
         couts = prec.pad(geom.cout)
         lib = _lib_for(x)
         d = _desc(prec, geom, n, h, w, cins, couts)
-        per_call = bool(getattr(weight, "_dei2i_per_call", False))
-        if per_call:
-            # a weight derived anew for THIS call (spectral norm in training mode): its packed copies travel with the
-            # call (ctx), not with the module -- the module's single slot would be overwritten by the next call before
-            # this call's backward asks for the dgrad layout
-            cache = PackedWeights()
+        cache, per_call, want_dgrad = _packing(weight, cache, sources, bool(ctx.needs_input_grad[0]))
         use_fp8 = bool(_fp8_forward and prec is BF16 and not per_call and lib.dei2i_conv2d_fp8_supported(byref(d)))
-        # trainable weights: a backward pass of this optimizer step will want the dgrad layout too (also when THIS call
-        # is the no-grad generator pass of the D step) -> both layouts in one pack launch
-        # (a frozen weight behind an input that needs a gradient -- D inside the G step -- wants the dgrad layout just as well)
-        want_dgrad = any(s_.requires_grad for s_ in sources) or bool(ctx.needs_input_grad[0])
         wf = None if use_fp8 else cache.get(weight, sources, prec, geom, cins, couts, need_dgrad=want_dgrad, per_call=per_call)[0]
-        ho, wo = c_int(), c_int()
-        lib.dei2i_conv2d_out_shape(byref(d), byref(ho), byref(wo))
-        y = torch.empty((n, ho.value, wo.value, couts), dtype=prec.dtype, device=x.device)
-        b32 = None
-        if bias is not None:
-            b32 = bias.detach().float().contiguous()
+        y = _conv_out(lib, d, n, couts, prec, x.device)
+        b32 = None if bias is None else _f32c(bias.detach())
         # the epilogue of the halo-resident kernel can leave the per-channel statistics of y for the norm that follows
         stats_fused = bool(want_stats and fuse_norm and not use_fp8 and prec is BF16 and lib.dei2i_conv2d_fused_supported(byref(d), 0))
         if use_fp8:
@@ -829,11 +909,9 @@ class _Conv2d(torch.autograd.Function):
             L.check(lib.dei2i_conv2d_fwd_fp8(byref(d), _p(xq), _p(wq), _p(b32), _p(dequant), act, _p(y), _stream()),
                     "conv2d_fwd_fp8")
         elif stats_fused:
-            chunks = lib.dei2i_conv2d_stats_chunks(byref(d))
-            partial = torch.empty((n, chunks, 2, couts), dtype=torch.float32, device=x.device)
+            partial = _leave_stats(n, lib.dei2i_conv2d_stats_chunks(byref(d)), couts, x.device)
             L.check(lib.dei2i_conv2d_fwd_fused(byref(d), _p(x), _p(wf), _p(b32), act, _p(y), None, _p(partial), _stream()),
                     "conv2d_fwd_fused")
-            _handover["_dei2i_stats"] = (partial, chunks)
         else:
             ws = _workspace(x.device, lib.dei2i_conv2d_workspace_bytes(byref(d)))
             L.check(lib.dei2i_conv2d_fwd(byref(d), _p(x), _p(wf), _p(b32), act, _p(y), _p(ws), ws.numel() * 4, _stream()),
@@ -885,63 +963,62 @@ def conv2d(x, weight, bias, cache: PackedWeights, geom: ConvGeom, act="none", so
     """y = act(conv(x) + bias) on an NHWC activation; ``weight`` is the reference's OIHW fp32 parameter.  ``stats``: a
     BatchNorm / InstanceNorm follows -- leave the statistics records of y with it when the kernel can (see _stats_of)."""
     _handover.clear()
-    return _attach(_Conv2d.apply(x, weight, bias, cache, tuple(sources) if sources is not None else (weight,), geom, ACT[act], bool(stats)))
+    return _attach(_Conv2d.apply(x, weight, bias, cache, _sources(sources, weight), geom, ACT[act], bool(stats)))
 
 
 # --------------------------------------------------------------------------------------------------------------
 # layout at the module boundary
 # --------------------------------------------------------------------------------------------------------------
+# The two conversions are each other's transpose: a Function's forward and its partner's first-order backward are the same launch
+# (the two plain functions); while a double-backward graph is recorded (_second_order) the backward is the partner Function itself.
+def _nchw_to_nhwc(x, prec: Precision, cs: int, size=None):
+    """NCHW -> (N, h, w, cs) NHWC of ``prec`` (channels zero-padded to cs); ``size``: nearest resize to (h, w) on the way"""
+    x = _f32c(x)
+    n, c, hs, ws = x.shape
+    h, w = (hs, ws) if size is None else size
+    out = torch.empty((n, h, w, cs), dtype=prec.dtype, device=x.device)
+    L.check(_lib_for(x).dei2i_nchw_to_nhwc_resize(prec.code, n, c, hs, ws, h, w, cs, _p(x), _p(out), _stream()), "nchw_to_nhwc")
+    return out
+
+
+def _nhwc_to_nchw(x, prec: Precision, c: int):
+    """NHWC of ``prec`` -> (N, c, H, W) fp32: the first c channels"""
+    x = x.contiguous()
+    n, h, w, cs = x.shape
+    out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    L.check(_lib_for(x).dei2i_nhwc_to_nchw(prec.code, n, c, h, w, cs, _p(x), _p(out), _stream()), "nhwc_to_nchw")
+    return out
+
+
 class _ToNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, prec: Precision, size):
         _require_gpu(x, "to_nhwc")
-        x = x.detach().float().contiguous() if x.dtype != torch.float32 or not x.is_contiguous() else x
-        n, c, hs, ws = x.shape
-        h, w = (hs, ws) if size is None else size
-        cs = prec.pad(c)
-        out = torch.empty((n, h, w, cs), dtype=prec.dtype, device=x.device)
-        lib = _lib_for(x)
-        L.check(lib.dei2i_nchw_to_nhwc_resize(prec.code, n, c, hs, ws, h, w, cs, _p(x), _p(out), _stream()), "nchw_to_nhwc")
-        ctx.shape, ctx.prec, ctx.resized = (n, c, hs, ws), prec, (h, w) != (hs, ws)
+        out = _nchw_to_nhwc(x, prec, prec.pad(x.shape[1]), size)
+        ctx.c, ctx.prec, ctx.resized = x.shape[1], prec, tuple(out.shape[1:3]) != tuple(x.shape[2:])
         return out
 
     @staticmethod
     def backward(ctx, g):
         if ctx.resized:
             raise RuntimeError("to_nhwc with nearest resize is only differentiable w.r.t. nothing (label maps)")
-        n, c, h, w = ctx.shape
         if _second_order(g):                              # R1-style penalties differentiate this backward: the conversion is linear
-            return _ToNCHW.apply(g, c), None, None
-        g = g.contiguous()
-        dx = torch.empty((n, c, h, w), dtype=torch.float32, device=g.device)
-        lib = _lib_for(g)
-        L.check(lib.dei2i_nhwc_to_nchw(ctx.prec.code, n, c, h, w, g.shape[-1], _p(g), _p(dx), _stream()), "nhwc_to_nchw")
-        return dx, None, None
+            return _ToNCHW.apply(g, ctx.c), None, None
+        return _nhwc_to_nchw(g, ctx.prec, ctx.c), None, None
 
 
 class _ToNCHW(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, c: int):
         _require_gpu(x, "to_nchw")
-        prec = precision_of(x)
-        x = x.contiguous()
-        n, h, w, cs = x.shape
-        out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
-        lib = _lib_for(x)
-        L.check(lib.dei2i_nhwc_to_nchw(prec.code, n, c, h, w, cs, _p(x), _p(out), _stream()), "nhwc_to_nchw")
-        ctx.prec, ctx.cs = prec, cs
-        return out
+        ctx.prec, ctx.cs = precision_of(x), x.shape[-1]
+        return _nhwc_to_nchw(x, ctx.prec, c)
 
     @staticmethod
     def backward(ctx, g):
         if _second_order(g):
             return _ToNHWC.apply(g, ctx.prec, None), None
-        g = g.contiguous().float()
-        n, c, h, w = g.shape
-        dx = torch.empty((n, h, w, ctx.cs), dtype=ctx.prec.dtype, device=g.device)
-        lib = _lib_for(g)
-        L.check(lib.dei2i_nchw_to_nhwc(ctx.prec.code, n, c, h, w, ctx.cs, _p(g), _p(dx), _stream()), "nchw_to_nhwc")
-        return dx, None
+        return _nchw_to_nhwc(g, ctx.prec, ctx.cs), None
 
 
 def to_nhwc(x_nchw, prec: Precision, size=None):
@@ -982,19 +1059,11 @@ paired_passes = True             # the G loss's four generator passes as two pas
 bn_groups = 1
 
 
-class bn_batch_groups:
+class bn_batch_groups(_GlobalScope):
+    var = "bn_groups"
+
     def __init__(self, groups: int):
-        self.groups = int(groups)
-
-    def __enter__(self):
-        global bn_groups
-        self.prev, bn_groups = bn_groups, self.groups
-        return self
-
-    def __exit__(self, *exc):
-        global bn_groups
-        bn_groups = self.prev
-        return False
+        self.value = int(groups)
 
 
 # ---- two independent chains of generator passes on two streams ---------------------------------------------------
@@ -1097,7 +1166,7 @@ def _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, m
     ``sync``: the bn_sync scope of a training-mode layer -- the statistics are those of the batch summed over the ranks."""
     n, h, w, c = y.shape
     dev, st = y.device, _stream()
-    w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+    w32, b32 = _f32c(weight.detach()), _f32c(bias.detach())
     nf = w32.numel()
     if n % groups or nf > c or running_mean.numel() != nf or running_var.numel() != nf:
         raise ValueError(f"batchnorm_act: {groups} groups over a batch of {n} / {nf} features for a {c}-channel activation")
@@ -1202,30 +1271,18 @@ class _BatchNormAct(torch.autograd.Function):
         y = y.contiguous()
         n, h, w, c = y.shape
         lib = _lib_for(y)
-        st = _stream()
         dev = y.device
         groups = bn_groups if training else 1
         ctx.sync = bn_sync.current if training else None
         a, b, mean, rstd, nf = _bn_coefs(lib, y, prec, weight, bias, running_mean, running_var, training, momentum, eps,
                                          num_batches_tracked, groups, sync=ctx.sync)
-        out = torch.empty_like(y)
         if res is not None:
             res = res.contiguous()
-        xq = torch.empty(out.numel(), dtype=torch.uint8, device=dev) if _fp8_copy_wanted(prec, c) else None
-        ng = n // groups
-        partial = None
-        if want_stats and fuse_norm and xq is None:
-            # the statistics records of the output in the same pass (an InstanceNorm / BatchNorm reads this tensor next)
-            chunks = lib.dei2i_moments_chunks(h * w)
-            partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=dev)
-            _handover["_dei2i_stats"] = (partial, chunks)
+        xq = torch.empty(y.numel(), dtype=torch.uint8, device=dev) if _fp8_copy_wanted(prec, c) else None
+        # the statistics records of the output in the same pass (an InstanceNorm / BatchNorm reads this tensor next)
+        partial = _leave_stats(n, lib.dei2i_moments_chunks(h * w), c, dev) if (want_stats and fuse_norm and xq is None) else None
         # every group in one launch (grid.y = group; coefficient rows (groups, c))
-        if partial is not None:
-            L.check(lib.dei2i_affine_act_stats_fwd(prec.code, groups, n, h * w, c, _p(y), _p(a), _p(b), _p(res), act, _p(out), _p(partial), st),
-                    "affine_act_stats")
-        else:
-            L.check(lib.dei2i_affine_act_fwd(prec.code, groups, ng * h * w, c, _p(y), _p(a), _p(b), _p(res), act, _p(out), _p(xq),
-                                             FP8_ACT_SCALE, st), "affine_act")
+        out = _affine_act(lib, prec, y, a, b, res, act, groups, stats=partial, xq=xq, xq_scale=FP8_ACT_SCALE)
         if xq is not None:
             _handover["_dei2i_fp8"] = xq
         ctx.prec, ctx.act, ctx.training, ctx.has_res = prec, act, training, res is not None
@@ -1233,7 +1290,7 @@ class _BatchNormAct(torch.autograd.Function):
         ctx.save_for_backward(y, a, b, mean, rstd)
         ctx.hint = None
         if fuse_bwd and prec is BF16 and ctx.needs_input_grad[0]:
-            ctx.hint = _NormBwdHint(2, y, mean, rstd, a=a, b=b, act=act, group_images=ng if groups > 1 else 0)
+            ctx.hint = _NormBwdHint(2, y, mean, rstd, a=a, b=b, act=act, group_images=n // groups if groups > 1 else 0)
             _handover["_dei2i_bwd_hint"] = ctx.hint
         return out
 
@@ -1272,20 +1329,15 @@ class _BnActConv(torch.autograd.Function):
                                          num_batches_tracked, sync=ctx.sync)
         couts = prec.pad(geom.cout)
         d = _desc(prec, geom, n, h, w, c, couts)
-        wf = cache.get(weight, sources, prec, geom, c, couts, need_dgrad=any(s_.requires_grad for s_ in sources))[0]
-        ho, wo = c_int(), c_int()
-        lib.dei2i_conv2d_out_shape(byref(d), byref(ho), byref(wo))
-        y = torch.empty((n, ho.value, wo.value, couts), dtype=prec.dtype, device=y1.device)
-        pro = L.ProDesc(a.data_ptr(), b.data_ptr(), 0, 0.2 if act == L.ACT_LRELU else (0.0 if act == L.ACT_RELU else 1.0), None)
-        partial = None
-        if want_stats:
-            chunks = lib.dei2i_conv2d_stats_chunks(byref(d))
-            partial = torch.empty((n, chunks, 2, couts), dtype=torch.float32, device=y1.device)
-            _handover["_dei2i_stats"] = (partial, chunks)
+        cache, per_call, need_dgrad = _packing(weight, cache, sources)
+        wf = cache.get(weight, sources, prec, geom, c, couts, need_dgrad=need_dgrad, per_call=per_call)[0]
+        y = _conv_out(lib, d, n, couts, prec, y1.device)
+        pro, _ = _bn_pro(a, b, act)
+        partial = _leave_stats(n, lib.dei2i_conv2d_stats_chunks(byref(d)), couts, y1.device) if want_stats else None
         L.check(lib.dei2i_conv2d_fwd_fused(byref(d), _p(y1), _p(wf), None, L.ACT_NONE, _p(y), byref(pro), _p(partial), _stream()),
                 "conv2d_fwd_fused(bn)")
         ctx.prec, ctx.act, ctx.training, ctx.nf, ctx.geom = prec, act, training, nf, geom
-        ctx.cache, ctx.sources, ctx.params, ctx.slope = cache, sources, (bn_w, bn_b), pro.slope
+        ctx.cache, ctx.sources, ctx.params, ctx.per_call = cache, sources, (bn_w, bn_b), per_call
         ctx.save_for_backward(y1, a, b, mean, rstd, weight)
         return y
 
@@ -1297,13 +1349,13 @@ class _BnActConv(torch.autograd.Function):
         dy = dy.contiguous()
         dw = None
         if _wants_grad(ctx, 3):
-            pro = L.ProDesc(a.data_ptr(), b.data_ptr(), 0, ctx.slope, None)
-            dw = _conv_wgrad(lib, prec, geom, y1, dy, weight, pro, keep=(a, b))
+            pro, keep = _bn_pro(a, b, ctx.act)
+            dw = _conv_wgrad(lib, prec, geom, y1, dy, weight, pro, keep=keep)
         dy1 = dbw = dbb = None
         if _wants_grad(ctx, 0) or _wants_grad(ctx, 1) or _wants_grad(ctx, 2):
             hint = _NormBwdHint(2, y1, mean, rstd, a=a, b=b, act=ctx.act)
-            dh = _conv_dgrad(lib, prec, geom, tuple(y1.shape), dy.shape[-1], dy, weight, ctx.cache, ctx.sources, False, y1.dtype, y1.device,
-                             hint=hint)
+            dh = _conv_dgrad(lib, prec, geom, tuple(y1.shape), dy.shape[-1], dy, weight, ctx.cache, ctx.sources, ctx.per_call, y1.dtype,
+                             y1.device, hint=hint)
             bn_w, bn_b = ctx.params
             dy1, dbw, dbb = _bn_backward(lib, prec, dh, y1, a, b, mean, rstd, ctx.act, ctx.training, bn_w, bn_b, ctx.nf, hint=hint,
                                          sync=ctx.sync)
@@ -1330,8 +1382,7 @@ def bn_act_conv(y1, bn_weight, bn_bias, running_mean, running_var, training, act
     """conv(act(BatchNorm2d(y1))), the norm + activation fused into the conv (ask bn_act_conv_supported first)."""
     _handover.clear()
     return _attach(_BnActConv.apply(y1, bn_weight, bn_bias, weight, running_mean, running_var, bool(training), float(momentum),
-                                    float(eps), ACT[act], num_batches_tracked, cache,
-                                    tuple(sources) if sources is not None else (weight,), geom, bool(stats)))
+                                    float(eps), ACT[act], num_batches_tracked, cache, _sources(sources, weight), geom, bool(stats)))
 
 
 def add(x, res, stats=False):
@@ -1348,20 +1399,11 @@ class _AffineAdd(torch.autograd.Function):
         _require_gpu(x, "add")
         prec = precision_of(x)
         x, res = x.contiguous(), res.contiguous()
-        out = torch.empty_like(x)
         lib = _lib_for(x)
-        c = x.shape[-1]
+        partial = None
         if want_stats and fuse_norm and x.dim() == 4:
-            n, hw = x.shape[0], x.shape[1] * x.shape[2]
-            chunks = lib.dei2i_moments_chunks(hw)
-            partial = torch.empty((n, chunks, 2, c), dtype=torch.float32, device=x.device)
-            L.check(lib.dei2i_affine_act_stats_fwd(prec.code, 1, n, hw, c, _p(x), _p(ones), _p(zeros), _p(res), L.ACT_NONE, _p(out),
-                                                   _p(partial), _stream()), "add_stats")
-            _handover["_dei2i_stats"] = (partial, chunks)
-        else:
-            L.check(lib.dei2i_affine_act_fwd(prec.code, 1, x.numel() // c, c, _p(x), _p(ones), _p(zeros), _p(res),
-                                             L.ACT_NONE, _p(out), None, 1.0, _stream()), "add")
-        return out
+            partial = _leave_stats(x.shape[0], lib.dei2i_moments_chunks(x.shape[1] * x.shape[2]), x.shape[-1], x.device)
+        return _affine_act(lib, prec, x, ones, zeros, res, L.ACT_NONE, stats=partial, what="add")
 
     @staticmethod
     def backward(ctx, g):
@@ -1404,14 +1446,9 @@ def _spade_backward(lib, prec, dout, dskip, x, gb, mean, rstd, up, gb_mode, out_
 class _SpadeRelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gb, up: bool, gb_mode: int, eps: float, skip: bool = False):
-        # skip: also hand x through as a second output (the res block's identity branch), so that the gradient arriving
-        # on that branch is added inside the backward-apply kernel instead of by a separate autograd add launch
         _require_gpu(x, "spade_relu")
         prec = precision_of(x)
-        x_in = x
-        x, gb = x.contiguous(), gb.contiguous()
-        if skip and (up or x is not x_in):
-            raise ValueError("spade_relu(skip=True) wants a contiguous activation and no upsample")
+        x, gb = _skip_forward("spade_relu", x, gb, skip, up)
         n, hs, ws, c = x.shape
         h, w = (hs * 2, ws * 2) if up else (hs, ws)
         lib = _lib_for(x)
@@ -1432,29 +1469,22 @@ class _SpadeRelu(torch.autograd.Function):
         if fuse_bwd and gb_mode == 1 and prec is BF16 and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             ctx.hint = _NormBwdHint(1, x, mean, rstd, gb=gb, up=up)
             _handover["_dei2i_bwd_hint"] = ctx.hint
-        return (out, x_in) if skip else out
+        return (out, x) if skip else out
 
     @staticmethod
     def backward(ctx, dout, dskip=None):
         x, gb, mean, rstd = ctx.saved_tensors
         if dout is None:                                 # only the identity branch was used
-            return dskip, None, None, None, None, None
-        if dskip is not None:
-            dskip = dskip.contiguous()
-            if dskip.dtype != x.dtype or dskip.shape != x.shape:
-                raise RuntimeError("spade_relu: identity-branch gradient does not match the activation")
-        dx, dgb = _spade_backward(_lib_for(x), ctx.prec, dout, dskip, x, gb, mean, rstd, ctx.up, ctx.gb_mode, ctx.out_shape,
-                                  hint=ctx.hint)
+            return (dskip,) + (None,) * 5
+        dx, dgb = _spade_backward(_lib_for(x), ctx.prec, dout, _skip_backward("spade_relu", dskip, x), x, gb, mean, rstd, ctx.up,
+                                  ctx.gb_mode, ctx.out_shape, hint=ctx.hint)
         return dx, dgb, None, None, None, None
 
 
 def spade_relu(x, gb, up: bool, gb_mode: int, eps: float = 1e-5, skip: bool = False):
     """relu(IN(x) * (1 + gamma) + beta); with ``skip`` -> (that, x): x handed through for the res block's identity add."""
     _handover.clear()
-    if skip:
-        out, xs = _SpadeRelu.apply(x, gb, bool(up), int(gb_mode), float(eps), True)
-        return _attach(out), xs
-    return _attach(_SpadeRelu.apply(x, gb, bool(up), int(gb_mode), float(eps)))
+    return _attach_skip(_SpadeRelu.apply(x, gb, bool(up), int(gb_mode), float(eps), bool(skip)), skip)
 
 
 class _SpadeConv(torch.autograd.Function):
@@ -1471,10 +1501,7 @@ class _SpadeConv(torch.autograd.Function):
         # interior-class coefficients (one elementwise pass over the small tensor) and let the conv read it through its fused
         # upsample, the logical frame's pixels from the ring tensor -- see fuse_ring
         prec = precision_of(x)
-        x_in = x
-        x, gb = x.contiguous(), gb.contiguous()
-        if skip and (up or x is not x_in):
-            raise ValueError("spade_conv(skip=True) wants a contiguous activation and no upsample")
+        x, gb = _skip_forward("spade_conv", x, gb, skip, up)
         n, hs, ws, c = x.shape
         h, w = (hs * 2, ws * 2) if up else (hs, ws)
         lib = _lib_for(x)
@@ -1487,16 +1514,10 @@ class _SpadeConv(torch.autograd.Function):
                                      _p(coefs[0]), _p(coefs[1]), _p(coefs[2]), _p(coefs[3]), _p(ring), st), "spade_prep")
         couts = prec.pad(geom.cout)
         d = _desc(prec, geom, n, hs, ws, c, couts)
-        per_call = bool(getattr(weight, "_dei2i_per_call", False))
-        if per_call:                                      # spectral norm in training mode: the packed copies travel with the call (see _Conv2d)
-            cache = PackedWeights()
-        wf = cache.get(weight, sources, prec, geom, c, couts, need_dgrad=any(s_.requires_grad for s_ in sources), per_call=per_call)[0]
+        cache, per_call, need_dgrad = _packing(weight, cache, sources)
+        wf = cache.get(weight, sources, prec, geom, c, couts, need_dgrad=need_dgrad, per_call=per_call)[0]
         y = torch.empty((n, h, w, couts), dtype=prec.dtype, device=dev)
-        out_partial = None
-        if want_stats:
-            ochunks = lib.dei2i_conv2d_stats_chunks(byref(d))
-            out_partial = torch.empty((n, ochunks, 2, couts), dtype=torch.float32, device=dev)
-            _handover["_dei2i_stats"] = (out_partial, ochunks)
+        out_partial = _leave_stats(n, lib.dei2i_conv2d_stats_chunks(byref(d)), couts, dev) if want_stats else None
         z_src = None
         if ring_mode:
             z_src = torch.empty_like(x)
@@ -1505,13 +1526,13 @@ class _SpadeConv(torch.autograd.Function):
             L.check(lib.dei2i_conv2d_fwd_ring(byref(d), _p(z_src), _p(ring), _p(wf), None, L.ACT_NONE, _p(y), _p(out_partial), st),
                     "conv2d_fwd_ring")
         else:
-            pro = L.ProDesc(coefs[2].data_ptr(), coefs[3].data_ptr(), c, 0.0, ring.data_ptr())
+            pro, _ = _spade_pro(coefs, ring, c)
             L.check(lib.dei2i_conv2d_fwd_fused(byref(d), _p(x), _p(wf), None, L.ACT_NONE, _p(y), byref(pro), _p(out_partial), st),
                     "conv2d_fwd_fused(spade)")
         ctx.prec, ctx.up, ctx.geom, ctx.cache, ctx.sources, ctx.ring_mode, ctx.per_call = prec, up, geom, cache, sources, ring_mode, per_call
         ctx.out_shape = (n, h, w, c)
         ctx.save_for_backward(x, gb, coefs, ring, weight, z_src)
-        return (y, x_in) if skip else y
+        return (y, x) if skip else y
 
     @staticmethod
     def backward(ctx, dy, dskip=None):
@@ -1522,17 +1543,12 @@ class _SpadeConv(torch.autograd.Function):
         lib = _lib_for(x)
         dy = dy.contiguous()
         n, h, w, c = ctx.out_shape
-        if dskip is not None:
-            dskip = dskip.contiguous()
-            if dskip.dtype != x.dtype or dskip.shape != x.shape:
-                raise RuntimeError("spade_conv: identity-branch gradient does not match the activation")
+        dskip = _skip_backward("spade_conv", dskip, x)
         dw = None
         if _wants_grad(ctx, 2):
-            if ctx.ring_mode:                            # the conv's input was z_src (+ ring): no transform in the wgrad
-                dw = _conv_wgrad(lib, prec, geom, z_src, dy, weight, L.ProDesc(None, None, 0, 0.0, ring.data_ptr()), keep=(ring,))
-            else:
-                pro = L.ProDesc(coefs[2].data_ptr(), coefs[3].data_ptr(), c, 0.0, ring.data_ptr())
-                dw = _conv_wgrad(lib, prec, geom, x, dy, weight, pro, keep=(coefs, ring))
+            # (ring mode: the conv's input was z_src (+ ring) -- no transform in the wgrad)
+            pro, keep = _spade_pro(coefs, ring, c, ctx.ring_mode)
+            dw = _conv_wgrad(lib, prec, geom, z_src if ctx.ring_mode else x, dy, weight, pro, keep=keep)
         dx = dgb = None
         if _wants_grad(ctx, 0) or _wants_grad(ctx, 1):
             # dL/dz at the LOGICAL (upsampled) resolution: the conv seen as a plain conv on z (the SPADE backward sums the
@@ -1567,12 +1583,8 @@ def spade_conv(x, gb, weight, cache, geom: ConvGeom, eps: float = 1e-5, skip: bo
     """conv(relu(IN(up(x)) * (1 + gamma) + beta)) with the class table ``gb`` (N,5,5,2C); ``geom.up`` = nearest x2 upsample in
     front of the norm.  With ``skip`` -> (y, x).  ``mode``: what spade_conv_supported answered."""
     _handover.clear()
-    src = tuple(sources) if sources is not None else (weight,)
-    ring_mode = mode == "ring"
-    if skip:
-        y, xs = _SpadeConv.apply(x, gb, weight, bool(geom.up), float(eps), True, cache, src, geom, bool(stats), ring_mode)
-        return _attach(y), xs
-    return _attach(_SpadeConv.apply(x, gb, weight, bool(geom.up), float(eps), False, cache, src, geom, bool(stats), ring_mode))
+    return _attach_skip(_SpadeConv.apply(x, gb, weight, bool(geom.up), float(eps), bool(skip), cache, _sources(sources, weight), geom,
+                                         bool(stats), mode == "ring"), skip)
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -1623,8 +1635,7 @@ class _InstanceNormAct(torch.autograd.Function):
 
 def instance_norm_act(x, act="none", res=None, eps=1e-5):
     """act(InstanceNorm2d(x)) (+ res) on an NHWC activation with H, W >= 4; act: "none" | "relu" | "leaky_relu" """
-    slope = {"none": 1.0, "relu": 0.0, "leaky_relu": 0.2}[act or "none"]
-    return _InstanceNormAct.apply(x, slope, res, float(eps))
+    return _InstanceNormAct.apply(x, ACT_SLOPE[ACT[act or "none"]], res, float(eps))
 
 
 # ---- SPADE's label path, second stage, batched over the modules of a generator (csrc/label_path.hip) ---------------------------
@@ -1760,13 +1771,8 @@ class _Scale(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, s: float):
         _require_gpu(x, "scale")
-        x = x.contiguous()
-        c = x.shape[-1]
-        out = torch.empty_like(x)
-        L.check(_lib_for(x).dei2i_affine_act_fwd(precision_of(x).code, 1, x.numel() // c, c, _p(x), _p(_const_vec(x.device, c, float(s))),
-                                                 _p(_const_vec(x.device, c, 0.0)), None, L.ACT_NONE, _p(out), None, 1.0, _stream()), "scale")
         ctx.s = s
-        return out
+        return _affine_act(_lib_for(x), precision_of(x), x.contiguous(), float(s), 0.0, None, L.ACT_NONE, what="scale")
 
     @staticmethod
     def backward(ctx, g):
@@ -1784,11 +1790,7 @@ class _Act(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, act: int):
         _require_gpu(x, "act")
-        x = x.contiguous()
-        c = x.shape[-1]
-        out = torch.empty_like(x)
-        L.check(_lib_for(x).dei2i_affine_act_fwd(precision_of(x).code, 1, x.numel() // c, c, _p(x), _p(_const_vec(x.device, c, 1.0)),
-                                                 _p(_const_vec(x.device, c, 0.0)), None, act, _p(out), None, 1.0, _stream()), "act")
+        out = _affine_act(_lib_for(x), precision_of(x), x.contiguous(), 1.0, 0.0, None, act, what="act")
         ctx.act = act
         ctx.save_for_backward(out)
         return out
@@ -1845,43 +1847,42 @@ class _InAffineAct(torch.autograd.Function):
 
 def in_affine_act(x, gamma, beta, act="leaky_relu", eps=1e-5):
     """act(InstanceNorm2d(x) * (1 + gamma) + beta) on an NHWC activation; gamma / beta: (N, C) fp32 (autograd flows into them)"""
-    slope = {"none": 1.0, "relu": 0.0, "leaky_relu": 0.2}[act or "none"]
-    return _InAffineAct.apply(x, gamma, beta, slope, float(eps))
+    return _InAffineAct.apply(x, gamma, beta, ACT_SLOPE[ACT[act or "none"]], float(eps))
 
 
 class _AvgPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _require_gpu(x, "avgpool2")
-        prec = precision_of(x)
         x = x.contiguous()
         n, h, w, c = x.shape
         out = torch.empty((n, h // 2, w // 2, c), dtype=x.dtype, device=x.device)
-        L.check(_lib_for(x).dei2i_avgpool2_fwd(prec.code, n, h, w, c, _p(x), _p(out), _stream()), "avgpool2_fwd")
-        ctx.prec, ctx.shape = prec, (n, h, w, c)
+        L.check(_lib_for(x).dei2i_avgpool2_fwd(precision_of(x).code, n, h, w, c, _p(x), _p(out), _stream()), "avgpool2_fwd")
+        ctx.shape = (n, h, w, c)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         if _second_order(dout):
             return _AvgPool2Bwd.apply(dout, ctx.shape)
-        n, h, w, c = ctx.shape
-        dout = dout.contiguous()
-        dx = torch.empty(ctx.shape, dtype=dout.dtype, device=dout.device)
-        L.check(_lib_for(dout).dei2i_avgpool2_bwd(ctx.prec.code, n, h, w, c, _p(dout), _p(dx), _stream()), "avgpool2_bwd")
-        return dx
+        return _avgpool2_bwd(dout, ctx.shape)
+
+
+def _avgpool2_bwd(dout, shape):
+    """-> the (N, H, W, C) = ``shape`` input gradient of the average pool: each value of ``dout`` / 4 to its 2x2 cell"""
+    n, h, w, c = shape
+    dout = dout.contiguous()
+    dx = torch.empty(shape, dtype=dout.dtype, device=dout.device)
+    L.check(_lib_for(dout).dei2i_avgpool2_bwd(precision_of(dout).code, n, h, w, c, _p(dout), _p(dx), _stream()), "avgpool2_bwd")
+    return dx
 
 
 class _AvgPool2Bwd(torch.autograd.Function):
-    """the average pool's input gradient as a function of the output gradient (each value / 4 to its 2x2 cell); transpose: the pool"""
+    """the average pool's input gradient as a function of the output gradient (_avgpool2_bwd); transpose: the pool"""
 
     @staticmethod
     def forward(ctx, dout, shape):
-        n, h, w, c = shape
-        dout = dout.contiguous()
-        dx = torch.empty(shape, dtype=dout.dtype, device=dout.device)
-        L.check(_lib_for(dout).dei2i_avgpool2_bwd(precision_of(dout).code, n, h, w, c, _p(dout), _p(dx), _stream()), "avgpool2_bwd")
-        return dx
+        return _avgpool2_bwd(dout, shape)
 
     @staticmethod
     def backward(ctx, gdx):
@@ -1951,19 +1952,11 @@ class _DiffAugAdjoint(torch.autograd.Function):
 diffaug_shard = None
 
 
-class diffaug_sharded:
+class diffaug_sharded(_GlobalScope):
+    var = "diffaug_shard"
+
     def __init__(self, rank: int, world: int):
-        self.shard = (int(rank), int(world))
-
-    def __enter__(self):
-        global diffaug_shard
-        self.prev, diffaug_shard = diffaug_shard, self.shard
-        return self
-
-    def __exit__(self, *exc):
-        global diffaug_shard
-        diffaug_shard = self.prev
-        return False
+        self.value = (int(rank), int(world))
 
 
 # Device-drawn parameters.  The host path above draws from the global CPU RNG and uploads per call, which a captured step would
@@ -2151,9 +2144,7 @@ class _Compose(torch.autograd.Function):
         _require_gpu(raw, "compose")
         prec = precision_of(raw)
         raw = raw.contiguous()
-        x32 = x_in.detach()
-        if x32.dtype != torch.float32 or not x32.is_contiguous():
-            x32 = x32.float().contiguous()
+        x32 = _f32c(x_in.detach())
         n, h, w, cs = raw.shape
         out = torch.empty((n, 3, h, w), dtype=torch.float32, device=raw.device)
         prob = torch.empty((n, 1, h, w), dtype=torch.float32, device=raw.device)
