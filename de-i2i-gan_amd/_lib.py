@@ -124,6 +124,7 @@ SIGNATURES = {
     "dei2i_adam_step_l2_dev": (c_int, [_P, c_int, c_int64, _P, _P, c_int, c_float, c_float, c_float, c_float, c_float, _P]),
     "dei2i_index_advance": (c_int, [_P, _P]),
     "dei2i_ema_lerp": (c_int, [_P, c_int, c_int64, c_float, _P]),
+    "dei2i_ema_lerp_dev": (c_int, [_P, c_int, c_int64, _P, _P, c_int, _P]),
     "dei2i_diffaug_partial_floats": (c_size_t, [c_int]),
     "dei2i_diffaug": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dei2i_diffaug_draw": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, c_int, c_int, _P, _P]),

@@ -93,15 +93,27 @@ __global__ __launch_bounds__(256) void sgd_rmsprop_kernel(const dei2i_adam_rec* 
 
 // stargan-v2's EMA (core/solver.py:549-551: param_test = torch.lerp(param, param_test, beta)) over every tensor of a network in
 // place: rec.p = param_test (lerp end), rec.g = param (lerp start).  torch.lerp's formula: start + w (end - start) for |w| < 0.5,
-// end - (end - start)(1 - w) otherwise.
-__global__ __launch_bounds__(256) void ema_lerp_kernel(const dei2i_adam_rec* __restrict__ table, float w) {
+// end - (end - start)(1 - w) otherwise.  One element, shared by both forms of the kernel so that they give the same bits.
+DEI2I_D float ema_update(const float start, const float end, const float w, const bool hi) {
+  const float diff = end - start;
+  return hi ? end - diff * (1.f - w) : start + w * diff;
+}
+
+// DEV: w is row `*index` of the device array `weights` (`rows` floats) instead of the kernel argument -- what a captured graph
+// replays with a weight that changes from one update to the next (the delayed start of the defectGAN / MAE trainers' EMA).
+template <bool DEV>
+__global__ __launch_bounds__(256) void ema_lerp_kernel(const dei2i_adam_rec* __restrict__ table, float w,
+                                                       const float* __restrict__ weights, const int* __restrict__ index, int rows) {
   const dei2i_adam_rec rec = table[blockIdx.y];
+  if (DEV) {
+    const int r = *index;
+    if (r < 0 || r >= rows) return;          // (the host refreshes the rows before the index can reach their end)
+    w = weights[r];
+  }
   const int64_t n = rec.n, stride = (int64_t)gridDim.x * blockDim.x;
   const bool hi = fabsf(w) >= 0.5f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float start = rec.g[i], end = rec.p[i], diff = end - start;
-    rec.p[i] = hi ? end - diff * (1.f - w) : start + w * diff;
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    rec.p[i] = ema_update(rec.g[i], rec.p[i], w, hi);
 }
 
 }  // namespace dei2i
@@ -176,6 +188,15 @@ extern "C" int dei2i_index_advance(int* index_dev, dei2i_stream s) {
 
 extern "C" int dei2i_ema_lerp(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float weight, dei2i_stream s) {
   if (!table_dev || count <= 0 || max_n <= 0) return DEI2I_ERR_BAD_ARG;
-  hipLaunchKernelGGL(ema_lerp_kernel, table_grid(max_n, 1, 1024, count), dim3(256), 0, (hipStream_t)s, table_dev, weight);
+  hipLaunchKernelGGL(ema_lerp_kernel<false>, table_grid(max_n, 1, 1024, count), dim3(256), 0, (hipStream_t)s, table_dev, weight,
+                     nullptr, nullptr, 0);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dei2i_ema_lerp_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* weights_dev,
+                                  const int* index_dev, int rows, dei2i_stream s) {
+  if (!table_dev || count <= 0 || max_n <= 0 || !weights_dev || !index_dev || rows <= 0) return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(ema_lerp_kernel<true>, table_grid(max_n, 1, 1024, count), dim3(256), 0, (hipStream_t)s, table_dev, 0.f,
+                     weights_dev, index_dev, rows);
   return (int)hipGetLastError();
 }

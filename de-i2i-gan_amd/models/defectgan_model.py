@@ -1,11 +1,12 @@
 """DefectGanModel (models/defectgan_model.py:18-171,173-314,361-383): the loss graphs of the D step and the G step of the
 defectGAN stage, and of the MAE-GAN pre-training stage (modes ``mae_*``)."""
+import contextlib
 import os
 import random
 
 import torch
 
-from .. import ops
+from .. import ops, optim
 from ..networks.architecture import MaskToken
 from ..networks.discriminator import DefectGanDiscriminator
 from ..networks.generator import DefectGanGenerator
@@ -86,7 +87,7 @@ class DefectGanModel(BaseModel):
             if mode == "mae_inference":
                 self.netD.eval()
                 self.netG.eval()
-                with torch.no_grad():
+                with torch.no_grad(), self._ema_scope():
                     if getattr(self.opt, "split_training", False):       # defectgan_model.py:69-72
                         rec_loss, gan_loss, _ = self._compute_mae_generator_loss(data, labels)
                         _, clf_loss = self._compute_mae_discriminator_loss(data, labels)
@@ -104,7 +105,8 @@ class DefectGanModel(BaseModel):
         if mode == "inference":
             self.netD.eval()
             self.netG.eval()
-            return self._generate_fake(data, labels)
+            with self._ema_scope():
+                return self._generate_fake(data, labels)
         if mode == "inference_classifier":
             self.netD.eval()
             self.netG.eval()
@@ -114,6 +116,33 @@ class DefectGanModel(BaseModel):
     @staticmethod
     def _mean(terms):
         return torch.stack(terms).mean()
+
+    # ---- EMA of the generator side (opt.ema_beta; base_model.py) -----------------------------------------------------------
+    def _ema_sources(self):
+        """What the G optimizer trains: netG, AdaIN's netE, the MAE stage's mask token where it has a parameter"""
+        out = {"G": self.netG}
+        if hasattr(self, "netE"):
+            out["E"] = self.netE
+        token = getattr(self, "mask_token", None)
+        if isinstance(token, torch.nn.Module) and next(token.parameters(), None) is not None:
+            out["mask_token"] = token
+        return out
+
+    @contextlib.contextmanager
+    def _ema_scope(self):
+        """The inference modes: ``_generator_side`` hands out the EMA copies inside (opt.ema_inference, while there is an EMA)"""
+        self._run_ema = bool(self.ema) and optim.ema_options(self.opt)[2]
+        try:
+            yield
+        finally:
+            self._run_ema = False
+
+    def _generator_side(self):
+        """-> (netG, netE or None, mask_token or None): the live modules, or inside ``_ema_scope`` their EMA copies"""
+        live = (self.netG, getattr(self, "netE", None), getattr(self, "mask_token", None))
+        if not self.__dict__.get("_run_ema"):
+            return live
+        return tuple(self.ema.get(label, mod) for label, mod in zip(("G", "E", "mask_token"), live))
 
     def _diff_augment(self, x, policy):
         """DiffAugment on one batch the discriminator sees: the torch-op policy functions with host draws, or (diff_aug_rng
@@ -148,6 +177,7 @@ class DefectGanModel(BaseModel):
         """Draw a shifted patch mask (host RNG, like the reference; mask_rng 'device': on the GPU, one draw launch and one fused
         fill launch), fill the masked pixels with the mask token and let the generator repair the image."""
         filled = None
+        netG, netE, mask_token = self._generator_side()
         sync = ops.bn_sync.current          # data-parallel with sync_bn: the GLOBAL batch's draw on every rank, this rank's rows of it
         if mask is not None:
             masks = self._upload_mask(mask)
@@ -157,7 +187,7 @@ class DefectGanModel(BaseModel):
             n, _, h, w = imgs.shape
             shift, keep = ops.mask_draw(self.mask_rng, n, h, w, self.opt.patch_size, self.opt.mask_ratio,
                                         row0=sync.rank * n if sync is not None else 0)
-            filled, masks = self.mask_token.fill(imgs if imgs.dtype == torch.float32 else imgs.float(), keep, shift, self.opt.patch_size)
+            filled, masks = mask_token.fill(imgs if imgs.dtype == torch.float32 else imgs.float(), keep, shift, self.opt.patch_size)
             self.last_mask = masks          # (for inspection; under graph_step a buffer of the graph that every replay rewrites)
         else:       # the reference's RNG draws on the host (utils/util.py:61-71); the expansion to pixels on the device
             n, world = imgs.size(0), sync.world if sync is not None else 1
@@ -166,19 +196,19 @@ class DefectGanModel(BaseModel):
                 keep = keep[sync.rank * n:(sync.rank + 1) * n]
             masks = expand_shifted_mask(self._upload_mask(keep), row0, col0, self.opt.patch_size, imgs.size(2), imgs.size(3))
         if filled is None:
-            filled = self.mask_token(imgs, masks)
+            filled = mask_token(imgs, masks)
         # (the tables are dropped and rebuilt on every call, whatever the parameter stamps say: a captured step -- graph_step.py --
         #  records the same launches an eager one makes)
-        self.netG.clear_spade_cache()
+        netG.clear_spade_cache()
         if self.opt.style_norm_block_type == "sean":             # defectgan_model.py:370-372
-            predicted, _ = self.netG(filled, labels, self._get_style_embeds(labels))
+            predicted, _ = netG(filled, labels, self._get_style_embeds(labels))
         elif self.opt.style_norm_block_type == "adain":          # :377-379
-            predicted, _ = self.netG(filled, labels, self.netE(imgs, labels))
+            predicted, _ = netG(filled, labels, netE(imgs, labels))
         else:
             seg = self._expand_seg(labels)
             if seg.shape[2:] == (1, 1):
-                self.netG.prime_spade((seg,))                # every SPADE module's class table in the batched launches (label_path.hip)
-            predicted, _ = self.netG(filled, seg)
+                netG.prime_spade((seg,))                     # every SPADE module's class table in the batched launches (label_path.hip)
+            predicted, _ = netG(filled, seg)
         return predicted, masks
 
     def _upload_mask(self, masks):
@@ -210,13 +240,14 @@ class DefectGanModel(BaseModel):
         """(rec, gan, clf): l1(G(masked), x), bce(D(G(masked)), 1), bce(cls(G(masked)), labels); with SEAN's --style_distill
         (defectgan_model.py:106-128) the two distillation terms are appended (logged only: their gradients were taken inside
         the SEAN layers' forward) -- but not in the --split_training return, like the reference"""
+        netG = self._generator_side()[0]
         if self._sean_distill():
-            self.netG.enable_sean_distill_loss(True)
+            netG.enable_sean_distill_loss(True)
         predicted, _ = self._repair_mask(imgs, labels)
         distill = None
         if self._sean_distill():
-            distill = self.netG.get_sean_distill_loss()
-            self.netG.enable_sean_distill_loss(False)
+            distill = netG.get_sean_distill_loss()
+            netG.enable_sean_distill_loss(False)
         rec_loss = self._cal_loss(predicted, imgs, "l1")
         if getattr(self.opt, "split_training", False):      # --split_training (defectgan_model.py:119-120): G sees only the L1 loss
             zero = torch.zeros([], device=rec_loss.device)
@@ -435,12 +466,13 @@ class DefectGanModel(BaseModel):
     @torch.no_grad()
     def _generate_fake(self, data, labels):
         """defectgan_model.py:302-314 (spade branch): labels (N,C) or a spatial (N,C,h,w) map"""
-        self.netG.clear_spade_cache()
+        netG, netE, _ = self._generator_side()
+        netG.clear_spade_cache()
         if self.opt.style_norm_block_type == "adain":            # defectgan_model.py:310-312
-            return self.netG(data, labels, self.netE(data, labels))
+            return netG(data, labels, netE(data, labels))
         if self.opt.style_norm_block_type == "sean":             # :304-306
-            return self.netG(data, labels, self._get_style_embeds(labels))
-        return self.netG(data, self._expand_seg(labels))
+            return netG(data, labels, self._get_style_embeds(labels))
+        return netG(data, self._expand_seg(labels))
 
     def _get_style_embeds(self, labels):
         """defectgan_model.py:394-411: per sample ``num_embeds`` embeddings drawn (python's ``random.choices``, like the

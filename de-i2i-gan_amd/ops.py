@@ -432,6 +432,9 @@ class PackedWeights:
         self.fp8 = None            # (packed e4m3 forward weights, dequant scalar) of the fp8 forward mode
         self._packed_on = None     # (stream id, event) of the last pack launch: another stream waits for it before reading
 
+    def __deepcopy__(self, memo):
+        return PackedWeights()     # (a copied module -- the models' EMA networks -- packs its own weights)
+
     def _mark_packed(self):
         # (the event object is made once per cache: constructing one per pack launch -- every conv weight after every optimizer step --
         #  was ~20 us of host time each; re-recording moves it to the newest pack launch, which is the one a reader has to wait for)

@@ -4,7 +4,8 @@ A ``torch.optim.Optimizer`` subclass, so ``lr_scheduler``s, ``param_groups`` / `
 ``torch.amp.GradScaler`` keep working the way the reference's trainers use them (trainers/base_trainer.py:68-126,
 mae_trainer.py:28,139-158).  Semantics = torch.optim.Adam (no amsgrad), or torch.optim.AdamW with ``weight_decay > 0``
 (decoupled: p *= 1 - lr*wd before the update): parameters whose ``grad`` is None are skipped and get no state.
-``ema_lerp_`` is stargan-v2's parameter EMA on the same pointer table (csrc/adam.hip).
+``ema_lerp_`` is stargan-v2's parameter EMA on the same pointer table (csrc/adam.hip); ``EmaGroup`` is the defectGAN / MAE
+trainers' (``opt.ema_beta``): the same launch per G update, buffers included, and a device-read form for captured graphs.
 
 Under graph capture (``torch.cuda.is_current_stream_capturing()``) ``FusedAdam.step`` records the ``_dev`` kernels instead:
 they read (lr, 1 - b1^t, sqrt(1 - b2^t), 1 - lr*wd) from a device table of the next ``HYPER_ROWS`` steps
@@ -211,36 +212,51 @@ def adam_hyper_rows(lr, b1, b2, decoupled_decay, t0, count):
     return out
 
 
-class _HyperTable:
-    """Device rows of ``adam_hyper_rows`` + the int32 row index the ``_dev`` kernels read, in one buffer (one upload).
-    ``t0``: the step of row 0; ``t``: the step the next replay runs (host mirror of t0 + index)."""
+class _RowTable:
+    """``rows`` rows of ``width`` floats + the int32 row index the ``_dev`` kernels read, in one device buffer (one upload).
+    ``t0``: the step of row 0; ``t``: the step the next replay runs (host mirror of t0 + index); ``key``: what the rows were
+    computed from.  A subclass's ``_rows(t, key)`` gives the (rows, width) float32 rows from step ``t`` on."""
+    WIDTH = 1
 
-    def __init__(self, device, t, rows=HYPER_ROWS):
+    def __init__(self, device, t, rows):
         self.rows = rows
-        self.buf = torch.empty(rows * 4 + 1, dtype=torch.float32, device=device)      # (written by the first refresh)
-        self.table = self.buf[:rows * 4]
-        self.index = self.buf[rows * 4:].view(torch.int32)
+        self.buf = torch.empty(rows * self.WIDTH + 1, dtype=torch.float32, device=device)      # (written by the first refresh)
+        self.table = self.buf[:rows * self.WIDTH]
+        self.index = self.buf[rows * self.WIDTH:].view(torch.int32)
         self.t0, self.t = t, t
         self.key = None            # no rows yet: the first ensure() uploads
         self._host = None
 
-    def refresh(self, t, lr, b1, b2, wd):
+    def refresh(self, t, *key):
         """Rows from step ``t`` on and index 0, one stream-ordered upload on the current stream (outside any capture)."""
-        host = torch.empty(self.rows * 4 + 1, dtype=torch.float32, pin_memory=True)
-        host[:self.rows * 4].copy_(torch.from_numpy(adam_hyper_rows(lr, b1, b2, wd, t, self.rows).reshape(-1)))
-        host[self.rows * 4:].view(torch.int32).fill_(0)
+        cells = self.rows * self.WIDTH
+        host = torch.empty(cells + 1, dtype=torch.float32, pin_memory=True)
+        host[:cells].copy_(torch.from_numpy(np.ascontiguousarray(self._rows(t, key), dtype=np.float32).reshape(-1)))
+        host[cells:].view(torch.int32).fill_(0)
         self.buf.copy_(host, non_blocking=True)
         self._host = host          # (the caching host allocator keeps the block until the copy has run; this is belt and braces)
         self.t0 = self.t = t
-        self.key = (lr, b1, b2, wd)
+        self.key = key
 
-    def ensure(self, t, lr, b1, b2, wd):
-        """The device index is at step ``t``'s row, computed with these hyper-parameters (else: rewrite from ``t`` on)."""
-        if self.key != (lr, b1, b2, wd) or t != self.t or t - self.t0 >= self.rows - 1:
-            self.refresh(t, lr, b1, b2, wd)
+    def ensure(self, t, *key):
+        """The device index is at step ``t``'s row, computed from ``key`` (else: rewrite from ``t`` on)."""
+        if self.key != key or t != self.t or t - self.t0 >= self.rows - 1:
+            self.refresh(t, *key)
 
     def advance(self):
         self.t += 1
+
+
+class _HyperTable(_RowTable):
+    """Device rows of ``adam_hyper_rows``; the key is (lr, b1, b2, decoupled decay)."""
+    WIDTH = 4
+
+    def __init__(self, device, t, rows=HYPER_ROWS):
+        super().__init__(device, t, rows)
+
+    def _rows(self, t, key):
+        lr, b1, b2, wd = key
+        return adam_hyper_rows(lr, b1, b2, wd, t, self.rows)
 
 
 class _CapturedGroup:
@@ -275,6 +291,143 @@ def ema_lerp_(ema_params, params, weight):
 
 
 _ema_tables = {}
+
+EMA_ROWS = 4096
+
+
+def ema_options(opt):
+    """-> (ema_beta, ema_start_iter, ema_inference) of an option object, absent options at their defaults (0.0: no EMA, 0, True)"""
+    beta = float(getattr(opt, "ema_beta", 0.0) or 0.0)
+    if not 0.0 <= beta < 1.0:
+        raise ValueError(f"|ema_beta {beta}| is invalid (0 <= ema_beta < 1; 0 turns the EMA off)")
+    return beta, int(getattr(opt, "ema_start_iter", 0) or 0), bool(getattr(opt, "ema_inference", True))
+
+
+def ema_weight(iters, start_iter, beta):
+    """The lerp weight of the G update that ends with ``trainer.iters == iters``: 0 (the copy follows the live weights) up to
+    ``start_iter``, ``beta`` after it."""
+    return 0.0 if iters <= start_iter else beta
+
+
+def ema_weight_rows(iters, num_critics, start_iter, beta, count):
+    """(count,) float32: row j is ``ema_weight`` of the j-th G update after iteration ``iters`` (G updates end at the multiples of
+    ``num_critics``), the float the eager launch hands the kernel."""
+    ends = (iters // num_critics + 1 + np.arange(count, dtype=np.int64)) * num_critics
+    return np.where(ends <= start_iter, np.float32(0.0), np.float32(beta)).astype(np.float32)
+
+
+class _WeightRows(_RowTable):
+    """Device rows of ``ema_weight_rows``: a "step" is the iteration a G update ends at; the key is (num_critics, start_iter, beta),
+    whose first entry is also the distance between two steps."""
+
+    def __init__(self, device, rows=EMA_ROWS):
+        super().__init__(device, 0, rows)
+
+    def _rows(self, t, key):
+        num_critics, start_iter, beta = key
+        return ema_weight_rows(t - num_critics, num_critics, start_iter, beta, self.rows)
+
+    def ensure(self, t, *key):
+        if self.key != key or t != self.t or (t - self.t0) // key[0] >= self.rows - 1:
+            self.refresh(t, *key)
+
+    def advance(self):
+        self.t += self.key[0]
+
+
+class _CapturedEma:
+    """The recorded launches of one EmaGroup in one graph: the host pointer tables, which ``graph_prepare`` uploads into the
+    reserved device tables once, after the capture and before the first replay, and the device weight rows."""
+    __slots__ = ("tables", "tables_dev", "weights", "uploaded")
+
+    def __init__(self, tables, tables_dev, weights):
+        self.tables, self.tables_dev, self.weights, self.uploaded = tables, tables_dev, weights, False
+
+
+class EmaGroup:
+    """The EMA copies of a set of trained tensors and the buffers that go with them, updated once per G update by the defectGAN and
+    MAE trainers.  ``lerp``: pairs (e, p) of fp32 tensors, ``e = lerp(p, e, weight)`` in one launch of csrc/adam.hip's EMA kernel;
+    ``copy``: pairs (e, b) of buffers, ``e = b``: the contiguous fp32 ones in one more launch of that kernel with weight 0, which is
+    an exact copy, the others (``num_batches_tracked``) through ``copy_``.
+
+    Eager, ``update(weight)`` passes the weight by value.  Under graph capture it records the ``_dev`` kernel, which reads its
+    weight from device rows (``ema_weight_rows``) at a device index that one ``dei2i_index_advance`` moves after the launch, so that
+    a replay uses its own update's weight: the switch from copying to averaging (``ema_start_iter``) happens between two replays of
+    one graph.  The owner of the graph calls ``graph_reserve`` before the capture (tables outside the graph's memory pool, like
+    ``FusedAdam.graph_reserve``), ``graph_take_plan`` after it, and ``graph_prepare`` / ``graph_finish`` around every replay."""
+
+    def __init__(self, lerp, copy=()):
+        self.lerp = [(e, p) for e, p in lerp]
+        fused = [e.dtype == torch.float32 and b.dtype == torch.float32 and e.is_contiguous() and b.is_contiguous() for e, b in copy]
+        self.copy = [pair for pair, f in zip(copy, fused) if f]
+        self.plain = [pair for pair, f in zip(copy, fused) if not f]
+        for e, p in self.lerp + self.copy + self.plain:
+            if e.shape != p.shape or e.device != p.device or e.dtype != p.dtype:
+                raise ValueError("EmaGroup: a copy differs from its source in shape, dtype or device")
+        if not self.lerp:
+            raise ValueError("EmaGroup: nothing to average")
+        self.device = self.lerp[0][0].device
+
+    def _launches(self):
+        """(pairs, whether their weight is the update's: else 0) of the kernel launches of one update"""
+        return [(pairs, lerps) for pairs, lerps in ((self.lerp, True), (self.copy, False)) if pairs]
+
+    @torch.no_grad()
+    def update(self, weight):
+        """One update with ``weight`` (``ema_weight``).  While a graph is being captured the launches are recorded in their device-read
+        form and ``weight`` is not used: every replay reads its own from the rows ``graph_prepare`` keeps."""
+        if torch.cuda.is_current_stream_capturing():
+            self._update_captured()
+            return
+        for pairs, lerps in self._launches():
+            ema_lerp_([e for e, _ in pairs], [p for _, p in pairs], weight if lerps else 0.0)
+        for e, b in self.plain:
+            e.copy_(b)
+
+    # ---- graph capture ------------------------------------------------------------------------------------------------
+    def graph_reserve(self):
+        """Before a capture: a device pointer table per launch and the weight rows, outside the graph's memory pool."""
+        self._graph_reserve = ([torch.empty((len(pairs), 5), dtype=torch.int64, device=self.device) for pairs, _ in self._launches()],
+                               _WeightRows(self.device))
+
+    def _update_captured(self):
+        reserve = self.__dict__.pop("_graph_reserve", None)
+        if reserve is None:
+            raise RuntimeError("EmaGroup: no table reserved (call graph_reserve() before the capture; one update per capture)")
+        tables_dev, weights = reserve
+        lib = ops._lib_for(self.lerp[0][0])
+        tables = []
+        for (pairs, lerps), table_dev in zip(self._launches(), tables_dev):
+            table = _PointerTable("EmaGroup", [(e, p, None, None) for e, p in pairs])
+            tables.append(table)
+            if lerps:
+                L.check(lib.dei2i_ema_lerp_dev(*table.args(table_dev), ctypes.c_void_p(weights.table.data_ptr()),
+                                               ctypes.c_void_p(weights.index.data_ptr()), weights.rows, ops._stream()), "ema_lerp_dev")
+                L.check(lib.dei2i_index_advance(ctypes.c_void_p(weights.index.data_ptr()), ops._stream()), "index_advance")
+            else:
+                L.check(lib.dei2i_ema_lerp(*table.args(table_dev), 0.0, ops._stream()), "ema_lerp")
+        for e, b in self.plain:
+            e.copy_(b)
+        self._graph_plan = _CapturedEma(tables, tables_dev, weights)
+
+    def graph_take_plan(self):
+        """-> the update recorded since the last call (None: none); an unused reservation is dropped"""
+        self.__dict__.pop("_graph_reserve", None)
+        return self.__dict__.pop("_graph_plan", None)
+
+    def graph_prepare(self, plan, iters, num_critics, start_iter, beta):
+        """Before a replay, after ``iters`` iterations, of a graph holding ``plan``: the pointer tables are on the device (uploaded
+        once) and the device index is at the row of the G update this replay makes, the one that ends iteration ``iters + 1``."""
+        if not plan.uploaded:
+            for table, table_dev in zip(plan.tables, plan.tables_dev):
+                table.upload(into=table_dev)
+            plan.uploaded = True
+        plan.weights.ensure(iters + 1, int(num_critics), int(start_iter), float(beta))
+
+    def graph_finish(self, plan):
+        """After a replay: the host mirror of the index, and the stamps the eager update would have moved."""
+        plan.weights.advance()
+        ops.mark_written(*[e for e, _ in self.lerp + self.copy])
 
 
 class _FusedPlain(torch.optim.Optimizer):

@@ -8,7 +8,7 @@ import torch
 from torch import optim
 
 from ..models import create_model
-from ..optim import FusedAdam, FusedRMSprop, FusedSGD
+from ..optim import FusedAdam, FusedRMSprop, FusedSGD, ema_options
 
 
 # opt.optimizer -> keyword arguments of the fused optimizer (the reference builds torch.optim.Adam(betas=(0.5, 0.999)) /
@@ -28,8 +28,10 @@ class BaseTrainer:
 
     def __init__(self, opt):
         self.opt = opt
+        ema_options(opt)                  # (an invalid opt.ema_beta is refused before anything is built)
         self.model = create_model(opt)
-        self._restore_or_init_weights(opt)
+        # opt.ema_beta > 0: the EMA copies of what the G optimizer trains start from the weights just initialised or restored
+        self.model.create_ema(self._restore_or_init_weights(opt))
         self.losses, self.dis_outputs = defaultdict(list), defaultdict(list)
         if opt.phase == "val":
             self.metrics = {}
@@ -48,12 +50,15 @@ class BaseTrainer:
         self._graph_records = None        # (keys, stacked losses) of the step being captured
 
     def _restore_or_init_weights(self, opt):
+        """-> the checkpoint epoch the weights were restored from (None: initialised)"""
         if opt.continue_training:
             self.model.load("latest")
-        elif opt.load_model_name is not None:
+            return "latest"
+        if opt.load_model_name is not None:
             self.model.load(opt.which_epoch)
-        else:
-            self.model.init_weights()
+            return opt.which_epoch
+        self.model.init_weights()
+        return None
 
     def _resume_progress(self, opt):
         """Epoch / iteration counters and the derived run length (num_epochs == -1 means 'from num_iters')."""

@@ -58,6 +58,8 @@ class DefectGanTrainer(BaseTrainer):
             self.optimizers["E"].step()
         if self.reducer is not None:
             self.reducer.broadcast_buffers(self.model.netG)      # BatchNorm running stats follow rank 0 (sync_bn: equal already)
+        # opt.ema_beta: no collective -- every rank applies one function to equal parameters and to buffers already synchronised
+        self.model.update_ema(self.iters)
         self._record([("gan", "G"), ("clf", "G"), ("aux", "rec"), ("aux", "cyc"), ("aux", "con")],
                      [gan_loss, clf_loss, rec_loss, sd_cyc_loss, sd_con_loss])
         if self.distill:                                  # (:142-146) logged; the gradients were taken inside the SEAN layers

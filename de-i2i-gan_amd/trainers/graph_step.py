@@ -6,7 +6,9 @@ the trainer's ``step`` runs eagerly for ``opt.graph_warmup`` calls (on the strea
 exists before the capture), then captures the graph the iteration needs -- D only, or D + G (``num_critics > 1`` replays both)
 -- and from then on copies the inputs into static device buffers, replays, and does the host bookkeeping the replay cannot:
 ``iters``, each optimizer's ``state["step"]`` and the rows of its device hyper-parameter table (optim.FusedAdam), the
-``_dei2i_epoch`` stamps (eager code repacks afterwards), ``p.grad`` and one queued device copy of the step's losses.
+``_dei2i_epoch`` stamps (eager code repacks afterwards), ``p.grad`` and one queued device copy of the step's losses.  With
+``opt.ema_beta`` the G step ends with the EMA update (optim.EmaGroup), captured in its device-read form: its tables are reserved,
+prepared and finished next to the optimizers', and go with the graphs.
 
 A call whose inputs differ in shape, dtype or device from the captured ones runs eagerly on the current stream and keeps the
 graphs.  ``release_graphs()`` drops them; a checkpoint load, a change of ``opt.compute_dtype`` and ``attach_ddp`` do so too.
@@ -65,9 +67,9 @@ def unsupported(trainer):
 class _Captured:
     """One graph and what its replays need on the host."""
 
-    def __init__(self, graph, with_g, plans, grads, keys, losses, keep):
-        self.graph, self.with_g, self.plans, self.grads, self.keys, self.losses, self.keep = \
-            graph, with_g, plans, grads, keys, losses, keep
+    def __init__(self, graph, with_g, plans, grads, keys, losses, keep, ema=None):
+        self.graph, self.with_g, self.plans, self.grads, self.keys, self.losses, self.keep, self.ema = \
+            graph, with_g, plans, grads, keys, losses, keep, ema
 
 
 class GraphStep:
@@ -125,11 +127,15 @@ class GraphStep:
         with torch.cuda.stream(st):
             for name, plan in cap.plans.items():
                 tr.optimizers[name].graph_prepare(plan)
+            if cap.ema is not None:
+                tr.model.ema_graph_prepare(cap.ema, tr.iters)
             cap.graph.replay()
         cur.wait_stream(st)
         tr.iters += 1
         for name, plan in cap.plans.items():
             tr.optimizers[name].graph_finish(plan)
+        if cap.ema is not None:
+            tr.model.ema_group.graph_finish(cap.ema)
         for p, g in cap.grads:
             p.grad = g
         if tr.defer_loss_sync:
@@ -161,6 +167,10 @@ class GraphStep:
         for o in tr.optimizers.values():
             o.graph_take_plan()
             o.graph_reserve()
+        ema = getattr(tr.model, "ema_group", None) if with_g else None      # (opt.ema_beta: the G update ends with the EMA's)
+        if ema is not None:
+            ema.graph_take_plan()
+            ema.graph_reserve()
         for net in self._trained_modules():
             ops.mark_written(*net.parameters())
         if hasattr(tr.model, "_label_sets"):
@@ -184,4 +194,4 @@ class GraphStep:
         plans = {name: o.graph_take_plan() for name, o in tr.optimizers.items()}
         plans = {name: plan for name, plan in plans.items() if plan}
         grads = [(p, p.grad) for net in self._trained_modules() for p in net.parameters()]
-        return _Captured(graph, with_g, plans, grads, keys, losses, keep)
+        return _Captured(graph, with_g, plans, grads, keys, losses, keep, ema.graph_take_plan() if ema is not None else None)

@@ -68,6 +68,8 @@ class MAETrainer(BaseTrainer):
         self._scaled_update(g_loss, "G")
         if self.reducer is not None:
             self.reducer.broadcast_buffers(self.model.netG)
+        # opt.ema_beta (with grad_scaler, after a skipped optimizer step too: the copies then move towards unchanged weights)
+        self.model.update_ema(self.iters)
         self._record([("rec", "train"), ("gan", "G"), ("clf", "G")], [rec_loss, gan_loss, clf_loss])
         if self.distill and len(losses) == 5:             # (:125-131) logged only
             self._record([("distill", "latent"), ("distill", "embed")], list(losses[3:5]))

@@ -287,6 +287,11 @@ int dei2i_index_advance(int* index_dev, dei2i_stream s);
 /* EMA of a network's parameters in place, one launch (stargan-v2 moving_average, core/solver.py:549-551): rec.p = the EMA copy,
  * rec.g = the trained parameter, rec.m / rec.v unused; p = torch.lerp(g, p, weight) with torch.lerp's two-sided formula */
 int dei2i_ema_lerp(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float weight, dei2i_stream s);
+/* The same update with weight = weights_dev[*index_dev] (`rows` floats) -- the form a captured graph replays, the host rewriting the
+ * rows between replays and dei2i_index_advance moving the index.  Bit-identical to the argument form given the same float; an
+ * index outside [0, rows) leaves every tensor untouched. */
+int dei2i_ema_lerp_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* weights_dev, const int* index_dev,
+                       int rows, dei2i_stream s);
 
 /* ---- DiffAugment (utils/diffaug.py) on fp32 NCHW images: one canonical-order policy run (color -> translation -> cutout) as
  * y = Cut . Trans . (L x + beta) per sample, L(x)[c] = a x[c] + b mean_c(x) + k mean_chw(x) (csrc/diffaug.hip).

@@ -12,10 +12,13 @@ host time of a ``step()`` call, ``wall_ms_per_step`` the whole timed region divi
 
     python tools/bench_graph_step.py --stage mae --mask-rng device [--mode eager --mode graph]
 
+    python tools/bench_graph_step.py --ema-beta 0.999 [--ema-start-iter N]
+
 ``--diff-aug-rng host`` draws DiffAugment's parameters on the host like the reference (graph mode refuses it), ``device`` on the
 GPU (``ops.DiffAugRng``).  ``--stage mae`` runs ``MAETrainer`` (bench.py's MAE option set) on the background batch and its labels;
 ``--mask-rng host`` draws its patch masks on the host like the reference (graph mode refuses it), ``device`` on the GPU
-(``ops.mask_draw``)."""
+(``ops.mask_draw``).  ``--ema-beta B`` keeps the EMA copies of the generator side (``opt.ema_beta``: one more multi-tensor launch and the
+buffer copies per G update), averaging from the first update unless ``--ema-start-iter`` delays it."""
 import argparse
 import json
 import os
@@ -43,6 +46,8 @@ def run(opts, mode, device):
     if opts.mask_rng is not None:
         opt.mask_rng = opts.mask_rng
         opt.mask_seed = opts.mask_seed
+    if opts.ema_beta:
+        opt.ema_beta, opt.ema_start_iter = opts.ema_beta, opts.ema_start_iter
     if mode == "graph":
         opt.graph_step, opt.graph_warmup = True, 3
     torch.manual_seed(123)
@@ -90,6 +95,8 @@ def main():
     ap.add_argument("--diff-aug", dest="diff_aug", default="", metavar="POLICY", help="e.g. color,translation,cutout ('' = none)")
     ap.add_argument("--diff-aug-rng", dest="diff_aug_rng", default=None, choices=["host", "device"])
     ap.add_argument("--diff-aug-seed", dest="diff_aug_seed", type=int, default=1234)
+    ap.add_argument("--ema-beta", dest="ema_beta", type=float, default=0.0, help="opt.ema_beta (0 = no EMA, the default)")
+    ap.add_argument("--ema-start-iter", dest="ema_start_iter", type=int, default=0, help="opt.ema_start_iter")
     ap.add_argument("--mode", action="append", default=None, choices=["eager", "graph"], help="repeatable; default: eager, then graph")
     opts = ap.parse_args()
     if opts.steps < 20:
@@ -106,7 +113,8 @@ def main():
         print("[bench_graph_step]", json.dumps(res), file=sys.stderr, flush=True)
     print(json.dumps({"workload": "MAE-GAN MAETrainer.step" if opts.stage == "mae" else "defectGAN DefectGanTrainer.step", "device": torch.cuda.get_device_name(0), "image_size": opts.image_size,
                       "batch": opts.batch, "dtype": opts.dtype, "use_spectral": opts.use_spectral, "add_noise": opts.add_noise,
-                      "diff_aug": opts.diff_aug, "diff_aug_rng": opts.diff_aug_rng or "host", "mask_rng": opts.mask_rng or "host", "steps": opts.steps,
+                      "diff_aug": opts.diff_aug, "diff_aug_rng": opts.diff_aug_rng or "host", "mask_rng": opts.mask_rng or "host", "ema_beta": opts.ema_beta,
+                      "ema_start_iter": opts.ema_start_iter, "steps": opts.steps,
                       "warmup": opts.warmup, "runs": runs}))
 
 
