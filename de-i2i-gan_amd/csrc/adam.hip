@@ -4,6 +4,8 @@
 //   p *= 1 - lr*wd  (AdamW only: keep = 1 - lr*wd, 1 for Adam)
 //   g = g*grad_scale + wd*p  (COUPLED: torch.optim.Adam's weight_decay, stargan-v2 core/solver.py:52-56; p.grad is not written)
 //   m += (1-b1)(g-m); v = b2 v + (1-b2) g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+// Global-norm clipping (torch.nn.utils.clip_grad_norm_, L2) rides on grad_scale: grad_sumsq_kernel + grad_clip_finalize_kernel leave
+// grad_scale * min(1, max_norm / (|g * grad_scale| + 1e-6)) in device memory, where the CLIP form of adam_kernel reads it.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dei2i_hip.h"
@@ -28,12 +30,14 @@ DEI2I_D void adam_update(float& p, const float g, float& m, float& v, const floa
 
 // DEV: (lr, bias_c1, bias_c2_sqrt, keep) are row `*index` of the device array `hyper` (`rows` rows of 4 floats) instead of the
 // kernel arguments of the same names -- what a captured graph replays with per-step values; the rest of the math is shared.
-template <bool COUPLED, bool DEV>
+// CLIP: grad_scale is `*scale` (what grad_clip_finalize_kernel left) instead of the kernel argument.
+template <bool COUPLED, bool DEV, bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(const dei2i_adam_rec* __restrict__ table, float lr, float beta1,
                                                    float beta2, float eps, float bias_c1, float bias_c2_sqrt,
                                                    float grad_scale, float keep, float wd, const float* __restrict__ hyper,
-                                                   const int* __restrict__ index, int rows) {
+                                                   const int* __restrict__ index, int rows, const float* __restrict__ scale) {
   const dei2i_adam_rec rec = table[blockIdx.y];
+  if (CLIP) grad_scale = *scale;
   if (DEV) {
     const int r = *index;
     if (r < 0 || r >= rows) return;          // (the host refreshes the rows before the index can reach their end)
@@ -68,6 +72,57 @@ __global__ __launch_bounds__(256) void adam_kernel(const dei2i_adam_rec* __restr
     rec.m[i] = m;
     rec.v[i] = v;
     rec.p[i] = p;
+  }
+}
+
+// Sum of g^2 over every tensor of the table, the first half of the global gradient norm: workgroup (x, y) sums its grid-stride
+// share of row y in fp32 -- one fmaf per element in either loop, so an element contributes the same bits whichever loop reaches
+// it -- then the 64 lanes by shuffle and the four waves through LDS, in a fixed order.  Every workgroup stores its partial (0
+// when it had no element): nothing is cleared beforehand, nothing is atomic, the same inputs give the same bits.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const dei2i_adam_rec* __restrict__ table, float* __restrict__ partial) {
+  const dei2i_adam_rec rec = table[blockIdx.y];
+  const int64_t n = rec.n;
+  const int64_t n4 = (reinterpret_cast<uintptr_t>(rec.g) & 15) == 0 ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4 g = reinterpret_cast<const float4*>(rec.g)[i];
+    acc = fmaf(g.x, g.x, acc);
+    acc = fmaf(g.y, g.y, acc);
+    acc = fmaf(g.z, g.z, acc);
+    acc = fmaf(g.w, g.w, acc);
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float g = rec.g[i];
+    acc = fmaf(g, g, acc);
+  }
+  acc = wave_sum(acc);
+  __shared__ float waves[4];
+  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((waves[0] + waves[1]) + waves[2]) + waves[3];
+}
+
+// The second half, one workgroup: S = the sum of the partials in double (thread t adds t, t + 256, ..., then a fixed LDS tree);
+// out[0] = sqrt(S) * grad_scale, the norm of the gradients the optimizer applies; out[1] = grad_scale * min(1, max_norm /
+// (out[0] + 1e-6)) in float, clip_grad_norm_'s arithmetic (a NaN stays NaN, as torch.clamp(max=1) leaves it).
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const float* __restrict__ partial, int n, float grad_scale,
+                                                                 float max_norm, float* __restrict__ out) {
+  __shared__ double tree[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)partial[i];
+  tree[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) tree[threadIdx.x] += tree[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)(sqrt(tree[0]) * (double)grad_scale);
+    float coef = max_norm / (norm + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;
+    out[0] = norm;
+    out[1] = grad_scale * coef;
   }
 }
 
@@ -129,12 +184,12 @@ static dim3 table_grid(int64_t max_n, int per_thread, int64_t cap, int count) {
   return dim3((unsigned)bx, (unsigned)count);
 }
 
-template <bool COUPLED, bool DEV>
+template <bool COUPLED, bool DEV, bool CLIP = false>
 static int adam_launch(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2, float eps,
                        float bias_c1, float bias_c2_sqrt, float grad_scale, float keep, float wd, const float* hyper_dev,
-                       const int* index_dev, int rows, dei2i_stream s) {
-  hipLaunchKernelGGL((adam_kernel<COUPLED, DEV>), table_grid(max_n, 4, 512, count), dim3(256), 0, (hipStream_t)s, table_dev, lr,
-                     beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, keep, wd, hyper_dev, index_dev, rows);
+                       const int* index_dev, int rows, dei2i_stream s, const float* scale_dev = nullptr) {
+  hipLaunchKernelGGL((adam_kernel<COUPLED, DEV, CLIP>), table_grid(max_n, 4, 512, count), dim3(256), 0, (hipStream_t)s, table_dev,
+                     lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, keep, wd, hyper_dev, index_dev, rows, scale_dev);
   return (int)hipGetLastError();
 }
 
@@ -176,6 +231,45 @@ extern "C" int dei2i_adam_step_l2_dev(const dei2i_adam_rec* table_dev, int count
   if (!table_dev || count <= 0 || max_n <= 0 || !hyper_dev || !index_dev || rows <= 0) return DEI2I_ERR_BAD_ARG;
   return adam_launch<true, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, weight_decay,
                                  hyper_dev, index_dev, rows, s);
+}
+
+// (the _clip forms: grad_scale comes from *scale_dev, where dei2i_grad_clip_finalize left it; `coupled` selects the _l2 update)
+extern "C" int dei2i_adam_step_clip(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2,
+                                    float eps, float bias_c1, float bias_c2_sqrt, const float* scale_dev, int coupled,
+                                    float weight_decay, dei2i_stream s) {
+  if (!table_dev || count <= 0 || max_n <= 0 || !scale_dev) return DEI2I_ERR_BAD_ARG;
+  if (coupled)
+    return adam_launch<true, false, true>(table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, 1.f, 1.f,
+                                          weight_decay, nullptr, nullptr, 0, s, scale_dev);
+  return adam_launch<false, false, true>(table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, 1.f,
+                                         1.f - lr * weight_decay, 0.f, nullptr, nullptr, 0, s, scale_dev);
+}
+
+extern "C" int dei2i_adam_step_clip_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev,
+                                        const int* index_dev, int rows, float beta1, float beta2, float eps,
+                                        const float* scale_dev, int coupled, float weight_decay, dei2i_stream s) {
+  if (!table_dev || count <= 0 || max_n <= 0 || !hyper_dev || !index_dev || rows <= 0 || !scale_dev) return DEI2I_ERR_BAD_ARG;
+  if (coupled)
+    return adam_launch<true, true, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, 1.f, 1.f, weight_decay,
+                                         hyper_dev, index_dev, rows, s, scale_dev);
+  return adam_launch<false, true, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, 1.f, 1.f, 0.f, hyper_dev,
+                                        index_dev, rows, s, scale_dev);
+}
+
+extern "C" int dei2i_grad_sumsq_blocks(int64_t max_n) { return (int)table_grid(max_n, 4, 512, 1).x; }
+
+extern "C" int dei2i_grad_sumsq(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float* partial_dev, dei2i_stream s) {
+  if (!table_dev || count <= 0 || max_n <= 0 || !partial_dev) return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(grad_sumsq_kernel, table_grid(max_n, 4, 512, count), dim3(256), 0, (hipStream_t)s, table_dev, partial_dev);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dei2i_grad_clip_finalize(const float* partial_dev, int n_partials, float grad_scale, float max_norm, float* out_dev,
+                                        dei2i_stream s) {
+  if (!partial_dev || n_partials <= 0 || !(max_norm > 0.f) || !out_dev) return DEI2I_ERR_BAD_ARG;
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, partial_dev, n_partials, grad_scale, max_norm,
+                     out_dev);
+  return (int)hipGetLastError();
 }
 
 __global__ void index_advance_kernel(int* index) { *index += 1; }

@@ -13,7 +13,12 @@ they read (lr, 1 - b1^t, sqrt(1 - b2^t), 1 - lr*wd) from a device table of the n
 advances after each update, so a replayed step sees its own step's values without a host wait.  ``graph_take_plan`` hands
 the recorded groups to the owner of the graph, which calls ``graph_prepare`` before and ``graph_finish`` after every replay:
 the host work the graph cannot do (uploading the pointer tables once, rewriting the rows when the lr changed or they run
-out, ``state["step"]`` and the ``_dei2i_epoch`` stamps)."""
+out, ``state["step"]`` and the ``_dei2i_epoch`` stamps).
+
+``max_grad_norm`` (``torch.nn.utils.clip_grad_norm_`` over every parameter of the optimizer, L2): the step first sums g^2 over
+each launch group's pointer table (``dei2i_grad_sumsq``, fixed-order partials, no atomics), one more launch turns the partials into
+``grad_scale * min(1, max_grad_norm / (norm + 1e-6))`` in device memory, and the Adam launches read their gradient scale from
+there (the ``_clip`` entry points): no host wait, no gradient written, the same launches eagerly and in a captured graph."""
 import ctypes
 import math
 
@@ -66,14 +71,35 @@ class _PointerTable:
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, weight_decay=0.0, decoupled=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, weight_decay=0.0, decoupled=True,
+                 max_grad_norm=None):
         """``decoupled=False``: torch.optim.Adam's weight decay (L2: the gradient becomes g + wd * p before the moments -- what
-        stargan-v2's optimizers use, core/solver.py:52-56) instead of AdamW's"""
+        stargan-v2's optimizers use, core/solver.py:52-56) instead of AdamW's.  ``max_grad_norm`` (None or 0: off; a plain attribute,
+        read at every step): the gradients ``g * grad_scale`` of all the optimizer's parameters are clipped to this joint L2 norm
+        inside the update; ``grad_norm`` is their norm before clipping, on the device."""
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0):
             raise ValueError("invalid Adam hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.grad_scale = float(grad_scale)
         self.decoupled = bool(decoupled)
+        self.max_grad_norm = max_grad_norm
+        self._clip_norm()
+
+    def _clip_norm(self):
+        """-> ``max_grad_norm`` as a float > 0, or None: no clipping"""
+        c = self.max_grad_norm
+        if c is None or c == 0:
+            return None
+        if not float(c) > 0.0:
+            raise ValueError(f"|max_grad_norm {c}| is invalid (> 0; None or 0 turns clipping off)")
+        return float(c)
+
+    @property
+    def grad_norm(self):
+        """One-element device view: the L2 norm of ``g * grad_scale`` over every parameter the last clipped step updated, before
+        clipping (None until such a step has run).  Reading it does not wait for the device."""
+        out = self.__dict__.get("_clip_out")
+        return None if out is None else out[:1]
 
     def _launch_groups(self, reach):
         """One launch per param group and step count: yields (group index, group, t, the group's parameters with a gradient that
@@ -108,6 +134,10 @@ class FusedAdam(torch.optim.Optimizer):
             st["step"] += 1
             return st["step"]
 
+        max_norm = self._clip_norm()
+        if max_norm is not None:
+            self._step_clipped(list(self._launch_groups(reach)), max_norm)
+            return loss
         for _, group, t, plist, wd, coupled in self._launch_groups(reach):
             b1, b2 = group["betas"]
             # coupled L2 decay (g*grad_scale + wd*p) inside the kernel: p.grad is left as the caller's
@@ -123,12 +153,67 @@ class FusedAdam(torch.optim.Optimizer):
                      weight_decay, ops._stream()), "adam_step")
         ops.mark_written(*plist)
 
+    # ---- global-norm clipping -----------------------------------------------------------------------------------------
+    def _step_clipped(self, groups, max_norm):
+        """The eager step with clipping: the norm over every launch group, then each group's update on the shared scale.  One
+        pointer table per group serves both, so a gradient that had to be copied is copied once."""
+        if not groups:
+            return
+        lib = ops._lib_for(groups[0][3][0])
+        cache = self.__dict__.setdefault("_table_cache", {})
+        tables = [self._table(plist) for _, _, _, plist, _, _ in groups]
+        tables = [(table, table.cached(cache)) for table in tables]
+        scale = self._clip_scale(lib, tables, max_norm, reserve=True)
+        for (_, group, t, plist, wd, coupled), (table, table_dev) in zip(groups, tables):
+            b1, b2 = group["betas"]
+            L.check(lib.dei2i_adam_step_clip(*table.args(table_dev), float(group["lr"]), b1, b2, group["eps"], 1.0 - b1 ** t,
+                                             math.sqrt(1.0 - b2 ** t), scale, int(coupled), wd, ops._stream()), "adam_step_clip")
+            ops.mark_written(*plist)
+
+    def _clip_buffers(self, reserve):
+        """-> (partials, out): room for the partial sums of any split of the parameters into launch groups (a group's grid is no
+        wider than its longest parameter's, its rows no more than its parameters), and (norm, scale).  Both persist; ``reserve``
+        False (inside a capture, whose pool must not hold them): raise instead of allocating."""
+        key = tuple(len(group["params"]) for group in self.param_groups)
+        bufs = self.__dict__.get("_clip_bufs")
+        if bufs is None or bufs[0] != key:
+            if not reserve:
+                raise RuntimeError("FusedAdam: no clipping buffers reserved (call graph_reserve() before the capture)")
+            lib = L.load()
+            groups = [group["params"] for group in self.param_groups if group["params"]]
+            need = sum(lib.dei2i_grad_sumsq_blocks(max(p.numel() for p in params)) * len(params) for params in groups)
+            device = groups[0][0].device
+            if self.__dict__.get("_clip_out") is None or self._clip_out.device != device:
+                self._clip_out = torch.zeros(2, dtype=torch.float32, device=device)
+            bufs = self._clip_bufs = (key, torch.empty(max(need, 1), dtype=torch.float32, device=device), self._clip_out)
+        return bufs[1], bufs[2]
+
+    def _clip_scale(self, lib, tables, max_norm, reserve):
+        """One dei2i_grad_sumsq per (host table, device table), their partials appended, and one dei2i_grad_clip_finalize over all of
+        them: -> the device address of ``grad_scale * min(1, max_norm / (norm + 1e-6))``, which the ``_clip`` updates read"""
+        partial, out = self._clip_buffers(reserve)
+        used = 0
+        for table, table_dev in tables:
+            if table.device != partial.device:
+                raise ValueError("FusedAdam: max_grad_norm needs every parameter of the optimizer on one device")
+            cells = lib.dei2i_grad_sumsq_blocks(table.max_n) * len(table.rows)
+            if used + cells > partial.numel():
+                raise RuntimeError("FusedAdam: the clipping buffers are too small for this step's launch groups")
+            L.check(lib.dei2i_grad_sumsq(*table.args(table_dev), ctypes.c_void_p(partial.data_ptr() + 4 * used), ops._stream()),
+                    "grad_sumsq")
+            used += cells
+        L.check(lib.dei2i_grad_clip_finalize(ctypes.c_void_p(partial.data_ptr()), used, self.grad_scale, max_norm,
+                                             ctypes.c_void_p(out.data_ptr()), ops._stream()), "grad_clip_finalize")
+        return ctypes.c_void_p(out.data_ptr() + 4)
+
     # ---- graph capture ------------------------------------------------------------------------------------------------
     def _step_captured(self):
         """The step as recorded into a graph: the eager step's grouping (by the step count each parameter reaches), one
-        ``_dev`` launch + one index advance per group.  Host state (``state["step"]``) is left to ``graph_finish``: the
-        capture runs nothing.  The pointer tables are uploaded after the capture (``graph_prepare``): the gradients they
-        point to are the graph's own, at fixed addresses from replay to replay."""
+        ``_dev`` launch + one index advance per group (with ``max_grad_norm``: the norm launches first, then the ``_clip_dev``
+        form; ``max_grad_norm`` and ``grad_scale`` are arguments frozen into the graph, which ``graph_prepare`` checks).  Host
+        state (``state["step"]``) is left to ``graph_finish``: the capture runs nothing.  The pointer tables are uploaded after
+        the capture (``graph_prepare``): the gradients they point to are the graph's own, at fixed addresses from replay to
+        replay."""
         def reach(p, st):
             if len(st) == 0:       # zeros_like inside the capture would reset the moments on every replay
                 raise RuntimeError("FusedAdam: a parameter received its first gradient while a graph was being captured "
@@ -136,8 +221,9 @@ class FusedAdam(torch.optim.Optimizer):
             return st["step"] + 1
 
         plan = self.__dict__.setdefault("_graph_plan", [])
+        max_norm = self._clip_norm()
+        recorded = []
         for gi, group, t, plist, wd, coupled in self._launch_groups(reach):
-            lib = ops._lib_for(plist[0])
             table = self._table(plist)
             # (reserved before the capture: a buffer allocated inside it comes from the graph's pool, whose blocks earlier
             #  nodes of the same replay may use as scratch -- they would overwrite what graph_prepare uploaded)
@@ -147,18 +233,32 @@ class FusedAdam(torch.optim.Optimizer):
             table_dev, hyper = slots.pop(0)
             hyper.t0 = hyper.t = t
             hyper.key = None
+            recorded.append((gi, group, plist, wd, coupled, table, table_dev, hyper))
+        if not recorded:
+            return
+        lib = ops._lib_for(recorded[0][2][0])
+        scale = None
+        if max_norm is not None:       # (buffers reserved before the capture, like the tables: never allocated inside it)
+            scale = self._clip_scale(lib, [(table, table_dev) for *_, table, table_dev, _ in recorded], max_norm, reserve=False)
+        for gi, group, plist, wd, coupled, table, table_dev, hyper in recorded:
             b1, b2 = group["betas"]
             dev_args = (*table.args(table_dev), ctypes.c_void_p(hyper.table.data_ptr()), ctypes.c_void_p(hyper.index.data_ptr()),
-                        hyper.rows, b1, b2, group["eps"], self.grad_scale)
-            L.check(lib.dei2i_adam_step_l2_dev(*dev_args, wd, ops._stream()) if coupled else
-                    lib.dei2i_adam_step_dev(*dev_args, ops._stream()), "adam_step_dev")
+                        hyper.rows, b1, b2, group["eps"])
+            if scale is not None:
+                L.check(lib.dei2i_adam_step_clip_dev(*dev_args, scale, int(coupled), wd, ops._stream()), "adam_step_clip_dev")
+            else:
+                L.check(lib.dei2i_adam_step_l2_dev(*dev_args, self.grad_scale, wd, ops._stream()) if coupled else
+                        lib.dei2i_adam_step_dev(*dev_args, self.grad_scale, ops._stream()), "adam_step_dev")
             L.check(lib.dei2i_index_advance(ctypes.c_void_p(hyper.index.data_ptr()), ops._stream()), "index_advance")
-            plan.append(_CapturedGroup(gi, plist, table, table_dev, hyper, 0.0 if coupled else wd))
+            plan.append(_CapturedGroup(gi, plist, table, table_dev, hyper, 0.0 if coupled else wd, (max_norm, self.grad_scale),
+                                       self.__dict__.get("_clip_bufs") if scale is not None else None))
             ops.mark_written(*plist)      # later passes of the capture must repack
 
     def graph_reserve(self):
         """Before a capture: device tables for every launch group the captured step can make (one per distinct step count
-        among the parameters, plus one), outside the graph's memory pool."""
+        among the parameters, plus one), and with ``max_grad_norm`` the clipping buffers, outside the graph's memory pool."""
+        if self._clip_norm() is not None and any(group["params"] for group in self.param_groups):
+            self._clip_buffers(reserve=True)
         reserve = {}
         for gi, group in enumerate(self.param_groups):
             params = group["params"]
@@ -178,6 +278,10 @@ class FusedAdam(torch.optim.Optimizer):
         """Before a replay of a graph holding ``plan``: the rows of every group cover this step with the current lr
         (a stream-ordered upload only when they do not)."""
         for g in plan:
+            if g.frozen != (self._clip_norm(), self.grad_scale):
+                raise RuntimeError(f"FusedAdam: (max_grad_norm, grad_scale) = {(self._clip_norm(), self.grad_scale)} now, but the graph "
+                                   f"was captured with {g.frozen}, which are arguments frozen into it (call the trainer's "
+                                   "release_graphs(), or capture again)")
             if not g.uploaded:
                 g.table.upload(into=g.table_dev)      # (a reserved slot: rows for the whole group)
                 g.uploaded = True
@@ -263,11 +367,13 @@ class _CapturedGroup:
     """One recorded launch group.  ``table``: its pointer table on the host (holding the graph's own gradients), which
     ``graph_prepare`` uploads into ``table_dev`` once, after the capture and before the first replay.  The raw-write stamps
     (``ops.mark_written``) move at capture, so the rest of the capture repacks, and again after every replay, so eager code
-    repacks."""
-    __slots__ = ("group", "params", "table", "table_dev", "hyper", "wd", "uploaded")
+    repacks.  ``frozen``: the (max_grad_norm or None, grad_scale) recorded as launch arguments; ``clip``: the clipping buffers the
+    graph reads and writes by address, kept alive with it."""
+    __slots__ = ("group", "params", "table", "table_dev", "hyper", "wd", "uploaded", "frozen", "clip")
 
-    def __init__(self, group, params, table, table_dev, hyper, wd):
+    def __init__(self, group, params, table, table_dev, hyper, wd, frozen, clip=None):
         self.group, self.params, self.table, self.table_dev, self.hyper, self.wd = group, params, table, table_dev, hyper, wd
+        self.frozen, self.clip = frozen, clip
         self.uploaded = False
 
 
@@ -301,6 +407,18 @@ def ema_options(opt):
     if not 0.0 <= beta < 1.0:
         raise ValueError(f"|ema_beta {beta}| is invalid (0 <= ema_beta < 1; 0 turns the EMA off)")
     return beta, int(getattr(opt, "ema_start_iter", 0) or 0), bool(getattr(opt, "ema_inference", True))
+
+
+def clip_options(opt):
+    """-> ``opt.max_grad_norm`` as a float > 0, or None (absent, None or 0: no clipping).  Only the Adam family clips."""
+    c = getattr(opt, "max_grad_norm", None)
+    if c is None or c == 0:
+        return None
+    if not float(c) > 0.0:
+        raise ValueError(f"|max_grad_norm {c}| is invalid (> 0; None or 0 turns clipping off)")
+    if getattr(opt, "optimizer", None) in ("sgd", "rmsprop"):
+        raise NotImplementedError(f"max_grad_norm with optimizer={opt.optimizer!r} (only FusedAdam clips by global norm)")
+    return float(c)
 
 
 def ema_weight(iters, start_iter, beta):

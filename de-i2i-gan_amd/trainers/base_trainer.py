@@ -8,7 +8,7 @@ import torch
 from torch import optim
 
 from ..models import create_model
-from ..optim import FusedAdam, FusedRMSprop, FusedSGD, ema_options
+from ..optim import FusedAdam, FusedRMSprop, FusedSGD, clip_options, ema_options
 
 
 # opt.optimizer -> keyword arguments of the fused optimizer (the reference builds torch.optim.Adam(betas=(0.5, 0.999)) /
@@ -29,6 +29,8 @@ class BaseTrainer:
     def __init__(self, opt):
         self.opt = opt
         ema_options(opt)                  # (an invalid opt.ema_beta is refused before anything is built)
+        # opt.max_grad_norm > 0: every FusedAdam clips its gradients to this global L2 norm inside the update (optim.FusedAdam)
+        self.max_grad_norm = clip_options(opt)
         self.model = create_model(opt)
         # opt.ema_beta > 0: the EMA copies of what the G optimizer trains start from the weights just initialised or restored
         self.model.create_ema(self._restore_or_init_weights(opt))
@@ -92,7 +94,8 @@ class BaseTrainer:
             return
         if opt.optimizer not in _OPTIMIZER_ARGS:
             raise NameError(f"optimizer named {opt.optimizer} not defined")
-        self.optimizers = {name: FusedAdam(net.parameters(), lr=self._lr_of(name), **_OPTIMIZER_ARGS[opt.optimizer])
+        self.optimizers = {name: FusedAdam(net.parameters(), lr=self._lr_of(name), max_grad_norm=self.max_grad_norm,
+                                           **_OPTIMIZER_ARGS[opt.optimizer])
                            for name, net in self.model.networks.items()}
 
     def _scheduler_for(self, opt, name, optimizer):
@@ -122,6 +125,16 @@ class BaseTrainer:
         else:
             for (kind, name), v in zip(keys, stacked.tolist()):        # ONE device->host read for the group
                 self.losses[kind][name].append(v)
+
+    def _grad_norm_records(self, *names):
+        """-> (keys, tensors) to add to a ``_record`` call after the updates of the optimizers ``names``: with ``opt.max_grad_norm``
+        the norm each of them measured before clipping, ``("grad_norm", name)``, read from device memory like a loss (NaN when the
+        optimizer has not stepped yet: a GradScaler skipped its first update); else nothing."""
+        if self.max_grad_norm is None:
+            return [], []
+        norms = [self.optimizers[name].grad_norm for name in names]
+        return ([("grad_norm", name) for name in names],
+                [torch.full((), float("nan"), device=self.opt.device) if n is None else n[0] for n in norms])
 
     def flush_losses(self):
         if self._pending:

@@ -24,6 +24,8 @@ class DefectGanTrainer(BaseTrainer):
         self.distill = opt.style_norm_block_type == "sean" and getattr(opt, "style_distill", False)      # defectgan_trainer.py:29-30
         if self.distill:
             self.loss_types.append("distill")
+        if self.max_grad_norm is not None:                # opt.max_grad_norm: the norm before clipping, per update
+            self.loss_types.append("grad_norm")
         self._init_losses()
         if opt.phase == "val":
             raise NotImplementedError("phase='val' builds FID/LPIPS metric networks (downloaded weights): out of scope")
@@ -60,8 +62,9 @@ class DefectGanTrainer(BaseTrainer):
             self.reducer.broadcast_buffers(self.model.netG)      # BatchNorm running stats follow rank 0 (sync_bn: equal already)
         # opt.ema_beta: no collective -- every rank applies one function to equal parameters and to buffers already synchronised
         self.model.update_ema(self.iters)
-        self._record([("gan", "G"), ("clf", "G"), ("aux", "rec"), ("aux", "cyc"), ("aux", "con")],
-                     [gan_loss, clf_loss, rec_loss, sd_cyc_loss, sd_con_loss])
+        norm_keys, norms = self._grad_norm_records(*(("G", "E") if with_e else ("G",)))
+        self._record([("gan", "G"), ("clf", "G"), ("aux", "rec"), ("aux", "cyc"), ("aux", "con")] + norm_keys,
+                     [gan_loss, clf_loss, rec_loss, sd_cyc_loss, sd_con_loss] + norms)
         if self.distill:                                  # (:142-146) logged; the gradients were taken inside the SEAN layers
             self._record([("distill", "latent"), ("distill", "embed")], list(losses[5:7]))
 
@@ -75,7 +78,8 @@ class DefectGanTrainer(BaseTrainer):
         if self.reducer is not None:
             self.reducer.reduce(self.model.netD)
         self.optimizers["D"].step()
-        self._record([("gan", "D"), ("clf", "D")], [gan_loss, clf_loss])
+        norm_keys, norms = self._grad_norm_records("D")
+        self._record([("gan", "D"), ("clf", "D")] + norm_keys, [gan_loss, clf_loss] + norms)
 
     def step(self, bg_data, df_labels, df_data):
         """One iteration of the reference's hot loop (defectgan_trainer.py:96-109).  ``opt.graph_step``: replayed from a

@@ -11,6 +11,9 @@ and un-scaling before the update is the identity unless a gradient overflows fp3
 come from -- torch disables the scaler altogether.  ``opt.grad_scaler = True`` routes the updates through
 ``torch.amp.GradScaler`` exactly like the reference's GPU path (one host sync per update for its overflow check); the
 default applies the update directly, which is the reference's CPU semantics and keeps the step free of host syncs.
+``opt.max_grad_norm`` (global-norm clipping inside the fused Adam, G's norm taken jointly with the mask token's) needs nothing
+more under the scaler: ``GradScaler.step`` has un-scaled the gradients before it calls ``FusedAdam.step``, so the norm that is
+clipped and logged as ``losses["grad_norm"]`` is that of the un-scaled gradients (an update the scaler skips logs the last norm).
 TensorBoard logging, image grids and FID validation are host-side tooling outside the step and are not part of this
 package."""
 from collections import defaultdict
@@ -31,6 +34,8 @@ class MAETrainer(BaseTrainer):
         self.distill = opt.style_norm_block_type == "sean" and getattr(opt, "style_distill", False)      # mae_trainer.py:20-21
         if self.distill:
             self.loss_types.append("distill")
+        if self.max_grad_norm is not None:                # opt.max_grad_norm: the norm before clipping, per update
+            self.loss_types.append("grad_norm")
         self._init_losses()
         self.data_types = data_types
         if opt.phase == "val":
@@ -70,7 +75,8 @@ class MAETrainer(BaseTrainer):
             self.reducer.broadcast_buffers(self.model.netG)
         # opt.ema_beta (with grad_scaler, after a skipped optimizer step too: the copies then move towards unchanged weights)
         self.model.update_ema(self.iters)
-        self._record([("rec", "train"), ("gan", "G"), ("clf", "G")], [rec_loss, gan_loss, clf_loss])
+        norm_keys, norms = self._grad_norm_records("G")
+        self._record([("rec", "train"), ("gan", "G"), ("clf", "G")] + norm_keys, [rec_loss, gan_loss, clf_loss] + norms)
         if self.distill and len(losses) == 5:             # (:125-131) logged only
             self._record([("distill", "latent"), ("distill", "embed")], list(losses[3:5]))
 
@@ -81,7 +87,8 @@ class MAETrainer(BaseTrainer):
             gan_loss, clf_loss = self.model("mae_discriminator", data, labels)
         d_loss = gan_loss + clf_loss * self.loss_weights["clf_D"]
         self._scaled_update(d_loss, "D")
-        self._record([("gan", "D"), ("clf", "D")], [gan_loss, clf_loss])
+        norm_keys, norms = self._grad_norm_records("D")
+        self._record([("gan", "D"), ("clf", "D")] + norm_keys, [gan_loss, clf_loss] + norms)
 
     def step(self, data, labels):
         """One iteration of the reference's loop (mae_trainer.py:92-99).  ``opt.graph_step``: replayed from a captured graph after

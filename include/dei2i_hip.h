@@ -282,6 +282,26 @@ int dei2i_adam_step_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_
                         int rows, float beta1, float beta2, float eps, float grad_scale, dei2i_stream s);
 int dei2i_adam_step_l2_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev, const int* index_dev,
                            int rows, float beta1, float beta2, float eps, float grad_scale, float weight_decay, dei2i_stream s);
+/* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, L2, error_if_nonfinite=False) on g * grad_scale, without
+ * writing a gradient: the clip coefficient is folded into the scale the Adam update multiplies every gradient by anyway.
+ * dei2i_grad_sumsq: one launch over a table (only rec.g and rec.n are read), grid = dei2i_grad_sumsq_blocks(max_n) x count;
+ * every workgroup stores the fp32 sum of g^2 over its share to partial_dev[row * blocks + block] (0 where it had none), in a fixed
+ * order: no clearing, no atomics, bit-reproducible.  Several tables append their partials in one buffer. */
+int dei2i_grad_sumsq_blocks(int64_t max_n);
+int dei2i_grad_sumsq(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float* partial_dev, dei2i_stream s);
+/* One workgroup: S = the sum of the n_partials partials in double; out_dev[0] = (float)(sqrt(S) * grad_scale), the norm of the
+ * gradients the optimizer applies; out_dev[1] = grad_scale * min(1, max_norm / (out_dev[0] + 1e-6f)) in float (a NaN stays NaN).
+ * max_norm must be > 0. */
+int dei2i_grad_clip_finalize(const float* partial_dev, int n_partials, float grad_scale, float max_norm, float* out_dev,
+                             dei2i_stream s);
+/* dei2i_adam_step / dei2i_adam_step_l2 (coupled != 0; weight_decay is then the L2 one, else the decoupled one) and their _dev
+ * forms with grad_scale = *scale_dev (out_dev + 1 of dei2i_grad_clip_finalize): bit-identical to them when *scale_dev holds the
+ * grad_scale they were given. */
+int dei2i_adam_step_clip(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2, float eps,
+                         float bias_c1, float bias_c2_sqrt, const float* scale_dev, int coupled, float weight_decay, dei2i_stream s);
+int dei2i_adam_step_clip_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev, const int* index_dev,
+                             int rows, float beta1, float beta2, float eps, const float* scale_dev, int coupled, float weight_decay,
+                             dei2i_stream s);
 /* *index_dev += 1 (one thread): captured after a _dev update, it moves the next replay to the next row */
 int dei2i_index_advance(int* index_dev, dei2i_stream s);
 /* EMA of a network's parameters in place, one launch (stargan-v2 moving_average, core/solver.py:549-551): rec.p = the EMA copy,

@@ -14,11 +14,17 @@ host time of a ``step()`` call, ``wall_ms_per_step`` the whole timed region divi
 
     python tools/bench_graph_step.py --ema-beta 0.999 [--ema-start-iter N]
 
+    python tools/bench_graph_step.py --max-grad-norm 1.0 --clip off --clip torch --clip fused [--repeat 2]
+
 ``--diff-aug-rng host`` draws DiffAugment's parameters on the host like the reference (graph mode refuses it), ``device`` on the
 GPU (``ops.DiffAugRng``).  ``--stage mae`` runs ``MAETrainer`` (bench.py's MAE option set) on the background batch and its labels;
 ``--mask-rng host`` draws its patch masks on the host like the reference (graph mode refuses it), ``device`` on the GPU
 (``ops.mask_draw``).  ``--ema-beta B`` keeps the EMA copies of the generator side (``opt.ema_beta``: one more multi-tensor launch and the
-buffer copies per G update), averaging from the first update unless ``--ema-start-iter`` delays it."""
+buffer copies per G update), averaging from the first update unless ``--ema-start-iter`` delays it.  ``--clip`` (repeatable) is how
+``--max-grad-norm X`` is applied: ``fused`` is ``opt.max_grad_norm`` (the norm and the clip inside the fused Adam, eager or captured),
+``torch`` is what a user would write without it -- ``torch.nn.utils.clip_grad_norm_(params, X, foreach=True)`` right before every
+``optimizer.step()``, eager only --, ``off`` no clipping.  Every (clip, mode) pair is one column; ``--repeat N`` runs the columns N
+times in turn, so that a run shows its own spread."""
 import argparse
 import json
 import os
@@ -34,7 +40,18 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 
 
-def run(opts, mode, device):
+def clip_before_step(optimizer, max_norm):
+    """the yardstick: clip_grad_norm_ over the optimizer's parameters right before each of its steps"""
+    params = [p for group in optimizer.param_groups for p in group["params"]]
+    step = optimizer.step
+
+    def clipped_step(*args, **kwargs):
+        torch.nn.utils.clip_grad_norm_([p for p in params if p.grad is not None], max_norm, foreach=True)
+        return step(*args, **kwargs)
+    optimizer.step = clipped_step
+
+
+def run(opts, mode, device, clip="off"):
     from de_i2i_gan_amd.trainers.defectgan_trainer import DefectGanTrainer
     from de_i2i_gan_amd.trainers.mae_trainer import MAETrainer
     mae = opts.stage == "mae"
@@ -48,10 +65,15 @@ def run(opts, mode, device):
         opt.mask_seed = opts.mask_seed
     if opts.ema_beta:
         opt.ema_beta, opt.ema_start_iter = opts.ema_beta, opts.ema_start_iter
+    if clip == "fused":
+        opt.max_grad_norm = opts.max_grad_norm
     if mode == "graph":
         opt.graph_step, opt.graph_warmup = True, 3
     torch.manual_seed(123)
     tr = (MAETrainer if mae else DefectGanTrainer)(opt)
+    if clip == "torch":          # (after the MAE trainer has added the mask token's group)
+        for optimizer in tr.optimizers.values():
+            clip_before_step(optimizer, opts.max_grad_norm)
     bg, lab, df = (t.to(device) for t in bench.synthetic_batch(opts.batch, opts.image_size, seed=7))
     inputs = (bg, lab) if mae else (bg, lab, df)
     for _ in range(opts.warmup):
@@ -70,10 +92,12 @@ def run(opts, mode, device):
     wall = 1e3 * (time.perf_counter() - t_start) / opts.steps
     gaps = [events[i].elapsed_time(events[i + 1]) for i in range(opts.steps)]
     tr.flush_losses()
-    res = {"mode": mode, "ms_per_step": round(statistics.median(gaps), 3), "ms_min": round(min(gaps), 3), "ms_max": round(max(gaps), 3),
+    res = {"mode": mode, "clip": clip, "ms_per_step": round(statistics.median(gaps), 3), "ms_min": round(min(gaps), 3), "ms_max": round(max(gaps), 3),
            "wall_ms_per_step": round(wall, 3), "host_enqueue_ms": round(statistics.median(host), 3),
            "graphs": len(tr._graphs.graphs) if tr._graphs is not None else 0,
            "d_gan_last": round(tr.losses["gan"]["D"][-1], 6)}
+    if clip == "fused":
+        res["grad_norm_last"] = {name: round(v[-1], 6) for name, v in tr.losses["grad_norm"].items()}
     tr.release_graphs()
     del tr
     torch.cuda.empty_cache()
@@ -97,6 +121,11 @@ def main():
     ap.add_argument("--diff-aug-seed", dest="diff_aug_seed", type=int, default=1234)
     ap.add_argument("--ema-beta", dest="ema_beta", type=float, default=0.0, help="opt.ema_beta (0 = no EMA, the default)")
     ap.add_argument("--ema-start-iter", dest="ema_start_iter", type=int, default=0, help="opt.ema_start_iter")
+    ap.add_argument("--max-grad-norm", dest="max_grad_norm", type=float, default=None, help="the global gradient norm --clip torch / fused clip to")
+    ap.add_argument("--clip", action="append", default=None, choices=["off", "torch", "fused"],
+                    help="repeatable; how --max-grad-norm is applied (torch: clip_grad_norm_ before every optimizer.step, eager only; "
+                         "fused: opt.max_grad_norm); default: off")
+    ap.add_argument("--repeat", type=int, default=1, help="run every (clip, mode) column this many times, in turn")
     ap.add_argument("--mode", action="append", default=None, choices=["eager", "graph"], help="repeatable; default: eager, then graph")
     opts = ap.parse_args()
     if opts.steps < 20:
@@ -105,16 +134,24 @@ def main():
         ap.error("--warmup must be >= 5 (graph mode warms up and captures inside it)")
     if not torch.cuda.is_available():
         raise SystemExit("bench_graph_step.py needs a GPU (the HIP path has no CPU fallback)")
+    clips = opts.clip or ["off"]
+    if any(c != "off" for c in clips) and not (opts.max_grad_norm and opts.max_grad_norm > 0):
+        ap.error("--clip torch / fused need --max-grad-norm X with X > 0")
+    # (clip_grad_norm_ between backward and step is host code a capture would freeze: the yardstick is eager only)
+    columns = [(c, m) for c in clips for m in (opts.mode or ["eager", "graph"]) if not (c == "torch" and m == "graph")]
+    if not columns or opts.repeat < 1:
+        ap.error("nothing to run (--clip torch is eager only)")
     torch.cuda.set_device(0)
     runs = []
-    for mode in (opts.mode or ["eager", "graph"]):
-        res = run(opts, mode, "cuda:0")
-        runs.append(res)
-        print("[bench_graph_step]", json.dumps(res), file=sys.stderr, flush=True)
+    for _ in range(opts.repeat):
+        for clip, mode in columns:
+            res = run(opts, mode, "cuda:0", clip)
+            runs.append(res)
+            print("[bench_graph_step]", json.dumps(res), file=sys.stderr, flush=True)
     print(json.dumps({"workload": "MAE-GAN MAETrainer.step" if opts.stage == "mae" else "defectGAN DefectGanTrainer.step", "device": torch.cuda.get_device_name(0), "image_size": opts.image_size,
                       "batch": opts.batch, "dtype": opts.dtype, "use_spectral": opts.use_spectral, "add_noise": opts.add_noise,
                       "diff_aug": opts.diff_aug, "diff_aug_rng": opts.diff_aug_rng or "host", "mask_rng": opts.mask_rng or "host", "ema_beta": opts.ema_beta,
-                      "ema_start_iter": opts.ema_start_iter, "steps": opts.steps,
+                      "ema_start_iter": opts.ema_start_iter, "max_grad_norm": opts.max_grad_norm, "steps": opts.steps,
                       "warmup": opts.warmup, "runs": runs}))
 
 
