@@ -178,63 +178,104 @@ def lrelu(x: Tensor) -> Tensor:
     return F.leaky_relu(x, 0.2)
 
 
-def instance_norm_affine(S: State, p: str, x: Tensor) -> Tensor:
+# --------------------------------------------------------------------------- #
+# the store hook: ``store(t)`` stands wherever de_i2i_gan_amd/stargan/model.py materialises a tensor in the compute dtype.  The
+# default is the identity, which leaves every function below bit for bit what it was.  With a straight-through round-to-bf16 (the
+# backward rounds the arriving gradient the same way) the float64 oracle becomes "exact arithmetic, the product's roundings": the
+# reference the bf16 tests measure their bounds on (tests/stargan_emulation.py).  What the product keeps in fp32 is not stored: norm
+# / AdaIN / linear parameters, style codes, biases, statistics, the fp32 accumulators, the NCHW tensors to_nchw writes.
+# A conv reads its weight from a packed compute-dtype copy (ops.PackedWeights) but writes the weight GRADIENT in fp32, so the hook
+# may carry a second callable ``store.weight`` (forward rounding only); without one the weights take ``store`` itself.
+# The kernels take LeakyReLU'(0) = 1 (csrc/common.h act_grad_from_out: the mask is ``z >= 0`` on the stored output; pinned by
+# tests/test_elementwise_edges_gpu.py) where torch takes the slope.  In fp32 an exact 0 does not occur; between bf16 stores it does
+# (four bf16 values under an average pool cancel), so the hook may also carry ``store.lrelu`` with that convention.
+# --------------------------------------------------------------------------- #
+def _same(t: Tensor) -> Tensor:
+    return t
+
+
+def _wt(store, w: Tensor) -> Tensor:
+    """a conv weight as the kernel reads it: PackedWeights' compute-dtype copy"""
+    return getattr(store, "weight", store)(w)
+
+
+def _act(store, x: Tensor) -> Tensor:
+    """LeakyReLU(0.2) as the product differentiates it under this hook (the forward value is lrelu's either way)"""
+    return getattr(store, "lrelu", lrelu)(x)
+
+
+def instance_norm_affine(S: State, p: str, x: Tensor, store=_same) -> Tensor:
     """nn.InstanceNorm2d(C, affine=True): eps 1e-5, biased variance per (n, c), no running stats"""
-    return F.instance_norm(x, weight=S[p + "weight"], bias=S[p + "bias"], eps=1e-5)
+    w, b = S[p + "weight"], S[p + "bias"]
+    # ops._InAffineAct rounds its (gamma | beta) table = (weight - 1 | bias) to the compute dtype before it builds the fp32
+    # coefficients -- a store of a derived table, not of the parameters.  Written as a correction to the parameter so that an identity
+    # hook adds an exact 0 and leaves the result bit for bit
+    w = w + (store(w - 1.0) - (w - 1.0))
+    b = b + (store(b) - b)
+    return F.instance_norm(x, weight=w, bias=b, eps=1e-5)
 
 
-def resblk(S: State, p: str, x: Tensor, normalize: bool, downsample: bool) -> Tensor:
+def resblk(S: State, p: str, x: Tensor, normalize: bool, downsample: bool, store=_same) -> Tensor:
     """ResBlk -- M:26-67: (shortcut + residual) / sqrt(2); shortcut = [conv1x1] -> [avg_pool2d 2]; residual = [IN] -> LReLU ->
     conv1 -> [avg_pool2d 2] -> [IN] -> LReLU -> conv2 (3x3, zero padding 1, bias)"""
     sc = x
     if p + "conv1x1.weight" in S:
-        sc = F.conv2d(sc, S[p + "conv1x1.weight"])
+        sc = store(F.conv2d(sc, _wt(store, S[p + "conv1x1.weight"])))                        # conv1x1: ops.conv2d
     if downsample:
-        sc = F.avg_pool2d(sc, 2)
+        sc = store(F.avg_pool2d(sc, 2))                                                      # ops.avgpool2
     h = x
     if normalize:
-        h = instance_norm_affine(S, p + "norm1.", h)
-    h = F.conv2d(lrelu(h), S[p + "conv1.weight"], S[p + "conv1.bias"], padding=1)
-    if downsample:
-        h = F.avg_pool2d(h, 2)
-    if normalize:
-        h = instance_norm_affine(S, p + "norm2.", h)
-    h = F.conv2d(lrelu(h), S[p + "conv2.weight"], S[p + "conv2.bias"], padding=1)
-    return (sc + h) / math.sqrt(2)
+        h = instance_norm_affine(S, p + "norm1.", h, store)
+    h = store(_act(store, h))                                                                      # norm1: ops.in_affine_act | ops.leaky_relu
+    h = F.conv2d(h, _wt(store, S[p + "conv1.weight"]), S[p + "conv1.bias"], padding=1)
+    if downsample or normalize:
+        h = store(h)                                                                         # conv1: ops.conv2d
+        if downsample:
+            h = store(F.avg_pool2d(h, 2))                                                    # ops.avgpool2
+        if normalize:
+            h = instance_norm_affine(S, p + "norm2.", h, store)
+    h = store(_act(store, h))                               # norm2: ops.in_affine_act | ops.leaky_relu | conv1's LeakyReLU epilogue
+    h = store(F.conv2d(h, _wt(store, S[p + "conv2.weight"]), S[p + "conv2.bias"], padding=1))    # conv2: ops.conv2d
+    return store(store(sc + h) / math.sqrt(2))                                               # ops.add, ops.scale
 
 
-def adain(S: State, p: str, x: Tensor, s: Tensor) -> Tensor:
+def adain(S: State, p: str, x: Tensor, s: Tensor, store=_same) -> Tensor:
     """AdaIN -- M:69-80: (1 + gamma) * IN(x) + beta, (gamma | beta) = fc(s)"""
     h = F.linear(s, S[p + "fc.weight"], S[p + "fc.bias"])
+    h = store(h)                                      # ops._InAffineAct: the (gamma | beta) table in the compute dtype (fc itself is fp32)
     gamma, beta = torch.chunk(h.view(h.size(0), h.size(1), 1, 1), 2, dim=1)
     return (1 + gamma) * F.instance_norm(x, eps=1e-5) + beta
 
 
-def adain_resblk(S: State, p: str, x: Tensor, s: Tensor, upsample: bool) -> Tensor:
+def adain_resblk(S: State, p: str, x: Tensor, s: Tensor, upsample: bool, store=_same) -> Tensor:
     """AdainResBlk -- M:83-123 with w_hpf = 0: (residual + shortcut) / sqrt(2)"""
     sc = x
     if upsample:
         sc = F.interpolate(sc, scale_factor=2, mode="nearest")
     if p + "conv1x1.weight" in S:
-        sc = F.conv2d(sc, S[p + "conv1x1.weight"])
-    h = lrelu(adain(S, p + "norm1.", x, s))
+        sc = store(F.conv2d(sc, _wt(store, S[p + "conv1x1.weight"])))                        # conv1x1 (x2 upsample fused): ops.conv2d
+    elif upsample:
+        sc = store(sc)                                                                       # ops.upsample2
+    h = store(_act(store, adain(S, p + "norm1.", x, s, store)))                                    # norm1: ops.in_affine_act
     if upsample:
-        h = F.interpolate(h, scale_factor=2, mode="nearest")
-    h = F.conv2d(h, S[p + "conv1.weight"], S[p + "conv1.bias"], padding=1)
-    h = F.conv2d(lrelu(adain(S, p + "norm2.", h, s)), S[p + "conv2.weight"], S[p + "conv2.bias"], padding=1)
-    return (h + sc) / math.sqrt(2)
+        h = F.interpolate(h, scale_factor=2, mode="nearest")                                 # (inside conv1: nothing is written)
+    h = store(F.conv2d(h, _wt(store, S[p + "conv1.weight"]), S[p + "conv1.bias"], padding=1))    # conv1: ops.conv2d
+    h = store(_act(store, adain(S, p + "norm2.", h, s, store)))                                    # norm2: ops.in_affine_act
+    h = store(F.conv2d(h, _wt(store, S[p + "conv2.weight"]), S[p + "conv2.bias"], padding=1))    # conv2: ops.conv2d
+    return store(store(h + sc) / math.sqrt(2))                                               # ops.add, ops.scale
 
 
-def generator(S: State, x: Tensor, s: Tensor, cfg: Cfg) -> Tensor:
+def generator(S: State, x: Tensor, s: Tensor, cfg: Cfg, store=_same) -> Tensor:
     """Generator.forward -- M:365-382 (masks None): from_rgb -> encode -> decode(s) -> to_rgb (IN affine, LReLU, conv 1x1)"""
     _, enc, dec = generator_plan(cfg)
-    h = F.conv2d(x, S["from_rgb.weight"], S["from_rgb.bias"], padding=1)
+    h = store(x)                                                                             # ops.to_nhwc
+    h = store(F.conv2d(h, _wt(store, S["from_rgb.weight"]), S["from_rgb.bias"], padding=1))  # from_rgb: ops.conv2d
     for i, (_, _, down) in enumerate(enc):
-        h = resblk(S, f"encode.{i}.", h, True, down)
+        h = resblk(S, f"encode.{i}.", h, True, down, store)
     for i, (_, _, up) in enumerate(dec):
-        h = adain_resblk(S, f"decode.{i}.", h, s, up)
-    h = lrelu(instance_norm_affine(S, "to_rgb.0.", h))
-    return F.conv2d(h, S["to_rgb.2.weight"], S["to_rgb.2.bias"])
+        h = adain_resblk(S, f"decode.{i}.", h, s, up, store)
+    h = store(_act(store, instance_norm_affine(S, "to_rgb.0.", h, store)))                         # to_rgb[0]: ops.in_affine_act
+    return store(F.conv2d(h, _wt(store, S["to_rgb.2.weight"]), S["to_rgb.2.bias"]))          # to_rgb[2]: ops.conv2d (to_nchw: fp32)
 
 
 def mapping_network(S: State, z: Tensor, y: Tensor, cfg: Cfg) -> Tensor:
@@ -252,32 +293,34 @@ def mapping_network(S: State, z: Tensor, y: Tensor, cfg: Cfg) -> Tensor:
     return out[torch.arange(y.size(0)), y]
 
 
-def _trunk(S: State, p: str, x: Tensor, cfg: Cfg) -> Tensor:
+def _trunk(S: State, p: str, x: Tensor, cfg: Cfg, store=_same) -> Tensor:
     """the shared trunk of StyleEncoder / Discriminator -- M:474-492, 508-524: conv3x3 -> ResBlk(downsample) x (log2(size) - 2) ->
     LReLU -> conv4x4 valid -> LReLU"""
     _, blocks = _trunk_plan(cfg)
-    h = F.conv2d(x, S[p + "0.weight"], S[p + "0.bias"], padding=1)
+    h = store(x)                                                                             # ops.to_nhwc
+    h = store(F.conv2d(h, _wt(store, S[p + "0.weight"]), S[p + "0.bias"], padding=1))        # blocks[0]: ops.conv2d
     for i in range(len(blocks)):
-        h = resblk(S, f"{p}{i + 1}.", h, False, True)
+        h = resblk(S, f"{p}{i + 1}.", h, False, True, store)
     n = len(blocks)
-    h = F.conv2d(lrelu(h), S[f"{p}{n + 2}.weight"], S[f"{p}{n + 2}.bias"])
-    return lrelu(h)
+    h = store(_act(store, h))                                                                      # ops.leaky_relu
+    h = F.conv2d(h, _wt(store, S[f"{p}{n + 2}.weight"]), S[f"{p}{n + 2}.bias"])
+    return store(_act(store, h))                                                                   # conv4x4 with its LeakyReLU epilogue
 
 
-def style_encoder(S: State, x: Tensor, y: Tensor, cfg: Cfg) -> Tensor:
+def style_encoder(S: State, x: Tensor, y: Tensor, cfg: Cfg, store=_same) -> Tensor:
     """StyleEncoder.forward -- M:494-505"""
-    h = _trunk(S, "shared.", x, cfg)
-    h = h.view(h.size(0), -1)
+    h = _trunk(S, "shared.", x, cfg, store)
+    h = h.view(h.size(0), -1)                                                                # (to_nchw and the linear heads: fp32)
     out = torch.stack([F.linear(h, S[f"unshared.{d}.weight"], S[f"unshared.{d}.bias"]) for d in range(cfg.num_domains)], dim=1)
     return out[torch.arange(y.size(0)), y]
 
 
-def discriminator(S: State, x: Tensor, y: Tensor, cfg: Cfg) -> Tensor:
+def discriminator(S: State, x: Tensor, y: Tensor, cfg: Cfg, store=_same) -> Tensor:
     """Discriminator.forward -- M:526-532"""
     _, blocks = _trunk_plan(cfg)
     n = len(blocks)
-    h = _trunk(S, "main.", x, cfg)
-    h = F.conv2d(h, S[f"main.{n + 4}.weight"], S[f"main.{n + 4}.bias"])
+    h = _trunk(S, "main.", x, cfg, store)
+    h = store(F.conv2d(h, _wt(store, S[f"main.{n + 4}.weight"]), S[f"main.{n + 4}.bias"]))   # the 1x1 head: ops.conv2d (to_nchw: fp32)
     h = h.view(h.size(0), -1)
     return h[torch.arange(y.size(0)), y]
 
@@ -295,41 +338,44 @@ def r1_reg(d_out: Tensor, x_in: Tensor) -> Tensor:
     return 0.5 * g.pow(2).view(x_in.size(0), -1).sum(1).mean(0)
 
 
-def style_code(N: Dict[str, State], y: Tensor, cfg: Cfg, x_ref: Optional[Tensor] = None, z: Optional[Tensor] = None) -> Tensor:
+def style_code(N: Dict[str, State], y: Tensor, cfg: Cfg, x_ref: Optional[Tensor] = None, z: Optional[Tensor] = None,
+               store=_same) -> Tensor:
     """core/utils.py:485-490 (adain): the mapping network on a latent code, else the style encoder on a reference image"""
-    return mapping_network(N["mapping_network"], z, y, cfg) if z is not None else style_encoder(N["style_encoder"], x_ref, y, cfg)
+    if z is not None:
+        return mapping_network(N["mapping_network"], z, y, cfg)                              # fp32 linears: nothing is stored
+    return style_encoder(N["style_encoder"], x_ref, y, cfg, store)
 
 
-def compute_d_loss(N, x_real, y_org, y_trg, cfg: Cfg, z_trg=None, x_ref=None):
+def compute_d_loss(N, x_real, y_org, y_trg, cfg: Cfg, z_trg=None, x_ref=None, store=_same):
     """S:467-491 -> (loss, {real, fake, reg})"""
     assert (z_trg is None) != (x_ref is None)
     x_real = x_real.detach().requires_grad_(True)
-    out = discriminator(N["discriminator"], x_real, y_org, cfg)
+    out = discriminator(N["discriminator"], x_real, y_org, cfg, store)
     loss_real = adv_loss(out, 1)
     loss_reg = r1_reg(out, x_real)
     with torch.no_grad():
-        s_trg = style_code(N, y_trg, cfg, x_ref, z_trg)
-        x_fake = generator(N["generator"], x_real, s_trg, cfg)
-    loss_fake = adv_loss(discriminator(N["discriminator"], x_fake, y_trg, cfg), 0)
+        s_trg = style_code(N, y_trg, cfg, x_ref, z_trg, store)
+        x_fake = generator(N["generator"], x_real, s_trg, cfg, store)
+    loss_fake = adv_loss(discriminator(N["discriminator"], x_fake, y_trg, cfg, store), 0)
     loss = loss_real + loss_fake + cfg.lambda_reg * loss_reg
     return loss, {"real": float(loss_real), "fake": float(loss_fake), "reg": float(loss_reg)}
 
 
-def compute_g_loss(N, x_real, y_org, y_trg, cfg: Cfg, z_trgs=None, x_refs=None):
+def compute_g_loss(N, x_real, y_org, y_trg, cfg: Cfg, z_trgs=None, x_refs=None, store=_same):
     """S:494-546 (w_hpf = 0) -> (loss, {adv, sty, ds, cyc})"""
     assert (z_trgs is None) != (x_refs is None)
     z_trg, z_trg2 = z_trgs if z_trgs is not None else (None, None)
     x_ref, x_ref2 = x_refs if x_refs is not None else (None, None)
-    s_trg = style_code(N, y_trg, cfg, x_ref, z_trg)
-    x_fake = generator(N["generator"], x_real, s_trg, cfg)
-    loss_adv = adv_loss(discriminator(N["discriminator"], x_fake, y_trg, cfg), 1)
-    s_pred = style_encoder(N["style_encoder"], x_fake, y_trg, cfg)
+    s_trg = style_code(N, y_trg, cfg, x_ref, z_trg, store)
+    x_fake = generator(N["generator"], x_real, s_trg, cfg, store)
+    loss_adv = adv_loss(discriminator(N["discriminator"], x_fake, y_trg, cfg, store), 1)
+    s_pred = style_encoder(N["style_encoder"], x_fake, y_trg, cfg, store)
     loss_sty = torch.mean(torch.abs(s_pred - s_trg))
-    s_trg2 = style_code(N, y_trg, cfg, x_ref2, z_trg2)
-    x_fake2 = generator(N["generator"], x_real, s_trg2, cfg).detach()
+    s_trg2 = style_code(N, y_trg, cfg, x_ref2, z_trg2, store)
+    x_fake2 = generator(N["generator"], x_real, s_trg2, cfg, store).detach()
     loss_ds = torch.mean(torch.abs(x_fake - x_fake2))
-    s_org = style_encoder(N["style_encoder"], x_real, y_org, cfg)
-    x_rec = generator(N["generator"], x_fake, s_org, cfg)
+    s_org = style_encoder(N["style_encoder"], x_real, y_org, cfg, store)
+    x_rec = generator(N["generator"], x_fake, s_org, cfg, store)
     loss_cyc = torch.mean(torch.abs(x_rec - x_real))
     loss = loss_adv + cfg.lambda_sty * loss_sty - cfg.lambda_ds * loss_ds + cfg.lambda_cyc * loss_cyc
     return loss, {"adv": float(loss_adv), "sty": float(loss_sty), "ds": float(loss_ds), "cyc": float(loss_cyc)}

@@ -7,6 +7,8 @@ widths), which the tiny goldens and the f32-mode full-size tests never reach (VE
     rounding of the stored output (2^-9 relative per element);
   * which kernel ran: the library's host-side launch counters (dei2i_launch_counts) must show the tuned kernel family
     for every phase -- a silent hipErrorNotSupported fall-through to the generic GEMM fails the test;
+  * the same op-level comparison and family pin for the conv geometries of one stargan-v2 train iteration at the AFHQ setting
+    (table AFHQ below: 256x256, max_conv_dim 512, stride 1, zero padding, N = 2), the families read from the gates;
   * step level: one D + G loss/backward at 256x256, batch 16, default widths, bf16 mode against this build's exact-f32
     mode with the same seed (the f32 mode is what the reference-generated goldens pin, tests/test_model_gpu.py).
 
@@ -197,6 +199,115 @@ def test_small_m_shapes_on_the_split_k_gemm_vs_oracle(ops, case):
     assert c_fwd.get("gather_v1") == 1 and (c_fwd.get("splitk_finalize", 0) == 1) == want_split, c_fwd
     assert set(c_bwd) <= {"gather_v1", "splitk_finalize", "wgrad_v1"}, c_bwd
     _seen[name] = {"fwd": c_fwd, "bwd": c_bwd}
+
+
+# The distinct conv geometries ONE stargan-v2 train_iteration launches at the README's AFHQ setting (img 256, max_conv_dim 512, 3
+# domains), derived from de_i2i_gan_amd/stargan/model.py, at N = 2: all stride 1, ZERO padding, bias except on the 1x1 shortcuts.
+#   Generator: from_rgb; ResBlk(normalize, downsample) 64 -> 128 -> 256 -> 512 -> 512 from 256^2 to 16^2 (conv1 din -> din at the input
+#   size, the learned 1x1 shortcut din -> dout there too -- it runs BEFORE the pool -- conv2 din -> dout behind the pool), two 512
+#   bottlenecks at 16^2; AdainResBlk mirror: two bottlenecks, then 512 -> 512 -> 256 -> 128 -> 64 with the x2 upsample fused into conv1
+#   and into the 1x1 shortcut, conv2 dout -> dout at the doubled size (those geometries are the encoder's); to_rgb 1x1.
+#   Trunk (style encoder, discriminator): the 3 -> 64 conv and the first four blocks repeat the generator's geometries; then 512 -> 512
+#   at 8^2 and 4^2, the 4x4 valid conv on the 4 x 4 map (LeakyReLU in its epilogue) and the discriminator's 1x1 head 512 -> 3.
+# (name, cin, cout, k, pad, up, H = W of the physical input, bias, act, forward kernel, dgrad kernel, wgrad kernel)
+# The kernel columns are READ from the gates with 256 CUs (conv_gemm.hip gather_gemm_multi: thin_cin -> thin_cout -> halo16 -> halo
+# -> gather_v2 -> gather_v1, each *_shape_ok; conv_api.hip dei2i_conv2d_wgrad_oihw: wgrad_thin -> wgrad_halo -> wgrad_v2 -> wgrad_v1),
+# split-K finalize launches apart.  Why a shape sits on the generic GEMM at N = 2 -- every one by a gate that says so on purpose:
+#   * forward / dgrad of the 3x3 convs from 64^2 down (and the up-convs into 32^2 / 64^2): 16 x 32 tiles x channel tiles < 7/8 of a
+#     round (halo16_shape_ok), 8 x 32 tiles < half a round (halo_conv_shape_ok: "small grids: split-K v1 fills the chip better"),
+#     256-row tiles < half a round (gather_gemm_v2: "small-M layers").  The dgrad of dec3's up-conv reaches half a round (32 tiles x
+#     4 channel tiles of its 512 input channels) and takes halo_conv, its forward (2 channel tiles) does not;
+#   * wgrad with 64 input channels and more than 32 output channels: wgrad_halo has no tile for it (64-row tiles want 128-channel
+#     slices or <= 32 rows), wgrad_v2 wants 128-channel slices; with 512 channels at 32^2 and below: wgrad_halo's combos x splits
+#     < 3/4 of the chip ("too little parallelism"), wgrad_v2 needs M >= 4096 rows;
+#   * to_rgb's dgrad (8 padded source channels, ONE tap): thin_cin builds 3x3 / 4x4 / 7x7 tap blocks only -- K = 8, HBM-bound;
+#   * 1 x 1 and 4 x 4 maps: no 8 x 32 tile.
+# A change of dispatch must move this table on purpose.
+AFHQ_N = 2
+H16, HAL, G2, G1 = "halo16_conv", "halo_conv", "gather_v2", "gather_v1"
+AFHQ = [
+    ("from_rgb 3->64 3x3 @256^2", 3, 64, 3, 1, False, 256, True, "none", "thin_cin", "thin_cout", "wgrad_v1"),
+    ("conv1 64->64 3x3 @256^2", 64, 64, 3, 1, False, 256, True, "none", H16, H16, "wgrad_v1"),
+    ("conv2 64->128 3x3 @128^2", 64, 128, 3, 1, False, 128, True, "none", HAL, HAL, "wgrad_v1"),
+    ("shortcut 64->128 1x1 @256^2", 64, 128, 1, 0, False, 256, False, "none", G2, G2, "wgrad_v1"),
+    ("conv1 128->128 3x3 @128^2", 128, 128, 3, 1, False, 128, True, "none", HAL, HAL, "wgrad_v2"),
+    ("conv2 128->256 3x3 @64^2", 128, 256, 3, 1, False, 64, True, "none", G1, G1, "wgrad_v2"),
+    ("shortcut 128->256 1x1 @128^2", 128, 256, 1, 0, False, 128, False, "none", G2, G2, "wgrad_v2"),
+    ("conv1 256->256 3x3 @64^2", 256, 256, 3, 1, False, 64, True, "none", G1, G1, "wgrad_v2"),
+    ("conv2 256->512 3x3 @32^2", 256, 512, 3, 1, False, 32, True, "none", G1, G1, "wgrad_v1"),
+    ("shortcut 256->512 1x1 @64^2", 256, 512, 1, 0, False, 64, False, "none", G2, G1, "wgrad_v2"),
+    ("conv 512->512 3x3 @32^2", 512, 512, 3, 1, False, 32, True, "none", G1, G1, "wgrad_v1"),
+    ("conv 512->512 3x3 @16^2", 512, 512, 3, 1, False, 16, True, "none", G1, G1, "wgrad_v1"),
+    ("up-conv1 512->512 3x3 16^2->32^2", 512, 512, 3, 1, True, 16, True, "none", G1, G1, "wgrad_v1"),
+    ("up-conv1 512->256 3x3 32^2->64^2", 512, 256, 3, 1, True, 32, True, "none", G1, HAL, "wgrad_halo"),
+    ("up-shortcut 512->256 1x1 32^2->64^2", 512, 256, 1, 0, True, 32, False, "none", G1, G2, "wgrad_v2"),
+    ("up-conv1 256->128 3x3 64^2->128^2", 256, 128, 3, 1, True, 64, True, "none", HAL, HAL, "wgrad_halo"),
+    ("up-shortcut 256->128 1x1 64^2->128^2", 256, 128, 1, 0, True, 64, False, "none", G2, G2, "wgrad_v2"),
+    ("up-conv1 128->64 3x3 128^2->256^2", 128, 64, 3, 1, True, 128, True, "none", H16, H16, "wgrad_halo"),
+    ("up-shortcut 128->64 1x1 128^2->256^2", 128, 64, 1, 0, True, 128, False, "none", G2, G2, "wgrad_v1"),
+    ("to_rgb 64->3 1x1 @256^2", 64, 3, 1, 0, False, 256, True, "none", "thin_cout", G1, "wgrad_v1"),
+    ("trunk conv 512->512 3x3 @8^2", 512, 512, 3, 1, False, 8, True, "none", G1, G1, "wgrad_v1"),
+    ("trunk conv 512->512 3x3 @4^2", 512, 512, 3, 1, False, 4, True, "none", G1, G1, "wgrad_v1"),
+    ("trunk 512->512 4x4 valid @4^2", 512, 512, 4, 0, False, 4, True, "none", G1, G1, "wgrad_v1"),
+    ("trunk 512->512 4x4 valid @4^2 +LReLU", 512, 512, 4, 0, False, 4, True, "leaky_relu", G1, G1, "wgrad_v1"),
+    ("D head 512->3 1x1 @1^2", 512, 3, 1, 0, False, 1, True, "none", G1, G1, "wgrad_v1"),
+]
+
+
+@pytest.mark.parametrize("case", AFHQ, ids=[c[0] for c in AFHQ])
+def test_afhq_stargan_conv_fwd_dgrad_wgrad_vs_oracle(ops, case):
+    """One conv call per phase, the method and the bounds of test_hot_shape_conv_fwd_dgrad_wgrad_vs_oracle: the oracle's conv in fp32 on
+    the bf16-rounded operands (forward 3e-3, input gradient 4e-3, weight gradient 1e-3 relative L2; behind a fused LeakyReLU -- the
+    model's 4x4 conv, listed both ways -- the gradients 1e-2: the mask comes from the rounded output), and the serving family."""
+    name, cin, cout, k, pad, up, H, has_bias, act, fam_fwd, fam_dgrad, fam_wgrad = case
+    prec, N = ops.BF16, AFHQ_N
+    gen = torch.Generator().manual_seed(501 + [c[0] for c in AFHQ].index(name))
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    x = torch.randn(N, cin, H, H, generator=gen).bfloat16().float()
+    w = (torch.randn(cout, cin, k, k, generator=gen) * math.sqrt(2.0 / (cin * k * k))).bfloat16().float()
+    b = torch.randn(cout, generator=gen) * 0.1 if has_bias else None
+    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    y_ref = O.conv2d(O.upsample2x(xr) if up else xr, wr, stride=1, pad=pad, mode="zeros", bias=b)
+    if act == "leaky_relu":
+        y_ref = O.leaky_relu(y_ref)
+    gy = torch.randn(y_ref.shape, generator=gen).bfloat16().float()
+    gx_ref, gw_ref = torch.autograd.grad(y_ref, [xr, wr], gy)
+    y_ref = y_ref.detach()
+    xg = ops.to_nhwc(x.to(DEV), prec).requires_grad_(True)
+    wg = w.to(DEV).requires_grad_(True)
+    geom = ops.ConvGeom(cin, cout, k, 1, pad, False, up)
+    _counts()
+    y = ops.conv2d(xg, wg, b.to(DEV) if has_bias else None, ops.PackedWeights(), geom, act)
+    torch.cuda.synchronize()
+    c_fwd = _counts()
+    got_y = ops.to_nchw(y, cout)
+    assert got_y.shape == y_ref.shape
+    gyh = torch.zeros(N, y.shape[1], y.shape[2], prec.pad(cout), dtype=torch.bfloat16, device=DEV)
+    gyh[..., :cout] = gy.to(DEV).permute(0, 2, 3, 1).to(torch.bfloat16)
+    _counts()
+    (dx,) = torch.autograd.grad(y, [xg], gyh, retain_graph=True)
+    torch.cuda.synchronize()
+    c_dgrad = _counts()
+    (dw,) = torch.autograd.grad(y, [wg], gyh)
+    torch.cuda.synchronize()
+    c_wgrad = _counts()
+    got_dx = dx[..., :cin].permute(0, 3, 1, 2)
+    e_fwd, e_dx, e_dw = rel_l2(got_y, y_ref), rel_l2(got_dx, gx_ref), rel_l2(dw, gw_ref)
+    print(f"{name}: fwd {e_fwd:.2e} {c_fwd}  dgrad {e_dx:.2e} {c_dgrad}  wgrad {e_dw:.2e} {c_wgrad}")
+    assert e_fwd < 3e-3 and maxrel(got_y, y_ref) < 1.5e-2, ("fwd", e_fwd, maxrel(got_y, y_ref))
+    if act == "none":
+        assert e_dx < 4e-3 and maxrel(got_dx, gx_ref) < 1.5e-2, ("dgrad", e_dx, maxrel(got_dx, gx_ref))
+        assert e_dw < 1e-3 and maxrel(dw, gw_ref) < 2e-3, ("wgrad", e_dw, maxrel(dw, gw_ref))
+    else:
+        assert e_dx < 1e-2, ("dgrad", e_dx)
+        assert e_dw < 1e-2, ("wgrad", e_dw)
+    if prec.pad(cin) > cin:
+        assert float(dx[..., cin:].abs().max()) == 0.0                  # padded input channels get no gradient
+    if prec.pad(cout) > cout:
+        assert float(y.detach()[..., cout:].abs().max()) == 0.0         # padded output channels stay zero
+    assert c_fwd == {fam_fwd: 1}, ("forward was served by", c_fwd)
+    assert c_dgrad == {fam_dgrad: 1}, ("dgrad was served by", c_dgrad)
+    assert c_wgrad == {fam_wgrad: 1}, ("wgrad was served by", c_wgrad)
 
 
 COS_MIN, L2_MAX = {"D": 0.99, "G": 0.95}, {"D": 0.12, "G": 0.30}
