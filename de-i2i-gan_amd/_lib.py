@@ -133,6 +133,9 @@ SIGNATURES = {
     "dei2i_diffaug_partial_floats": (c_size_t, [c_int]),
     "dei2i_diffaug": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dei2i_diffaug_draw": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, c_int, c_int, _P, _P]),
+    "dei2i_diffaug_draw_p": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "dei2i_ada_measure": (c_int, [_P, c_int64, _P, c_int, _P]),
+    "dei2i_ada_apply": (c_int, [_P, c_int64, _P, _P, c_int, c_float, c_float, c_float, _P]),
     "dei2i_mask_draw": (c_int, [c_uint64, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),
     "dei2i_mask_fill": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, POINTER(c_int64), _P, _P, _P]),
     "dei2i_mask_fill_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),

@@ -12,7 +12,8 @@
 //
 // dei2i_diffaug_draw fills the record table on the device: Philox4x32-10 keyed by a seed, counted by (call, run, global row), the
 // call count one word of device memory that the launch itself advances -- an eager step and a replay of a captured step draw the
-// same parameters, and every replay draws new ones.
+// same parameters, and every replay draws new ones.  dei2i_diffaug_draw_p is the same draw with a gate per row and policy: each
+// policy applies with a probability read from device memory (adaptive discriminator augmentation; its controller: ada.hip).
 #include <hip/hip_runtime.h>
 
 #include "../../include/dei2i_hip.h"
@@ -160,17 +161,25 @@ struct DrawGeom {
   int max_y, max_x;          // translation: ty in [-max_y, max_y], tx in [-max_x, max_x]
   int range_cy, range_cx;    // cutout centre: cy in [0, range_cy), cx in [0, range_cx)
   int half_ch, half_cw;      // top = cy - half_ch, left = cx - half_cw
+  int H, W;                  // (GATED) the cut window of a row whose cutout gate is off starts at (H, W): off the image
 };
 
 // One workgroup strides over the runs x N records.  flags: 3 bits per run (DEI2I_DIFFAUG_COLOR / _TRANSLATION / _CUTOUT).  Every
 // thread reads the call count, then thread 0 stores count + 1 behind the barrier: one launch, no atomics.  Contraction is off:
 // the arithmetic has no multiply-add, so a numpy reference reproduces the table bit for bit.
+// GATED (dei2i_diffaug_draw_p): a third Philox block, run | 2 << 16, gives one gate per policy (x0 color, x1 translation, x2
+// cutout); a policy of the run applies to the row iff unit_float(x) < *p_dev, else its fields go back to the identity.  The
+// parameter blocks are drawn as without gates, so a row's parameters do not depend on its gates and p = 1 is the ungated table.
+template <bool GATED>
 __global__ __launch_bounds__(kThreads) void diffaug_draw_kernel(unsigned long long seed, unsigned long long* __restrict__ counter,
                                                                 int runs, unsigned long long flags, int N, unsigned row0,
-                                                                DrawGeom g, dei2i_diffaug_rec* __restrict__ tab) {
+                                                                DrawGeom g, const float* __restrict__ p_dev,
+                                                                dei2i_diffaug_rec* __restrict__ tab) {
 #pragma clang fp contract(off)
   const unsigned long long call = *counter;
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), c0 = (uint32_t)call, c1 = (uint32_t)(call >> 32);
+  float p = 1.f;
+  if (GATED) p = *p_dev;
   for (int i = threadIdx.x; i < runs * N; i += kThreads) {
     const int run = i / N, n = i - run * N;
     const unsigned f = (unsigned)(flags >> (3 * run)) & 7u;
@@ -194,6 +203,18 @@ __global__ __launch_bounds__(kThreads) void diffaug_draw_kernel(unsigned long lo
       if (f & DEI2I_DIFFAUG_CUTOUT) {
         r.top = (int)__umulhi(x.x2, (uint32_t)g.range_cy) - g.half_ch;
         r.left = (int)__umulhi(x.x3, (uint32_t)g.range_cx) - g.half_cw;
+      }
+    }
+    if (GATED) {
+      const Philox4 x = philox4x32_10(c0, c1, (uint32_t)run | (2u << 16), row, k0, k1);
+      if ((f & DEI2I_DIFFAUG_COLOR) && !(unit_float(x.x0) < p)) {
+        r.a = 1.f;
+        r.b = r.k = r.beta = 0.f;
+      }
+      if ((f & DEI2I_DIFFAUG_TRANSLATION) && !(unit_float(x.x1) < p)) r.ty = r.tx = 0;
+      if ((f & DEI2I_DIFFAUG_CUTOUT) && !(unit_float(x.x2) < p)) {
+        r.top = g.H;          // rows [H, H + ch) x cols [W, W + cw): no pixel of the image (in_hole is false in every mode)
+        r.left = g.W;
       }
     }
     tab[i] = r;
@@ -236,8 +257,9 @@ extern "C" int dei2i_diffaug(int mode, int N, int C, int H, int W, int ch, int c
   return (int)hipGetLastError();
 }
 
-extern "C" int dei2i_diffaug_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
-                                  dei2i_diffaug_rec* tab, dei2i_stream s) {
+// both draws: p_dev null = dei2i_diffaug_draw (no gate block), else dei2i_diffaug_draw_p
+static int draw_launch(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
+                       const float* p_dev, dei2i_diffaug_rec* tab, dei2i_stream s) {
   if (!counter_dev || !tab || runs <= 0 || runs > DEI2I_DIFFAUG_MAX_RUNS || N <= 0 || row0 < 0 || H <= 0 || W <= 0) return DEI2I_ERR_BAD_ARG;
   if ((long long)row0 + N > (1ll << 31) || (long long)runs * N >= (1ll << 24) || H > (1 << 24) || W > (1 << 24)) return DEI2I_ERR_BAD_ARG;
   if ((run_flags >> (3 * runs)) != 0) return DEI2I_ERR_BAD_ARG;
@@ -251,7 +273,25 @@ extern "C" int dei2i_diffaug_draw(uint64_t seed, uint64_t* counter_dev, int runs
   g.range_cx = W + (1 - cw % 2);
   g.half_ch = ch / 2;
   g.half_cw = cw / 2;
-  hipLaunchKernelGGL(diffaug_draw_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)s, (unsigned long long)seed,
-                     reinterpret_cast<unsigned long long*>(counter_dev), runs, (unsigned long long)run_flags, N, (unsigned)row0, g, tab);
+  g.H = H;
+  g.W = W;
+  unsigned long long* counter = reinterpret_cast<unsigned long long*>(counter_dev);
+  if (p_dev)
+    hipLaunchKernelGGL(diffaug_draw_kernel<true>, dim3(1), dim3(kThreads), 0, (hipStream_t)s, (unsigned long long)seed, counter, runs,
+                       (unsigned long long)run_flags, N, (unsigned)row0, g, p_dev, tab);
+  else
+    hipLaunchKernelGGL(diffaug_draw_kernel<false>, dim3(1), dim3(kThreads), 0, (hipStream_t)s, (unsigned long long)seed, counter, runs,
+                       (unsigned long long)run_flags, N, (unsigned)row0, g, p_dev, tab);
   return (int)hipGetLastError();
+}
+
+extern "C" int dei2i_diffaug_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
+                                  dei2i_diffaug_rec* tab, dei2i_stream s) {
+  return draw_launch(seed, counter_dev, runs, run_flags, N, row0, H, W, nullptr, tab, s);
+}
+
+extern "C" int dei2i_diffaug_draw_p(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
+                                    const float* p_dev, dei2i_diffaug_rec* tab, dei2i_stream s) {
+  if (!p_dev) return DEI2I_ERR_BAD_ARG;
+  return draw_launch(seed, counter_dev, runs, run_flags, N, row0, H, W, p_dev, tab, s);
 }

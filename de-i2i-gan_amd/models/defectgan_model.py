@@ -57,6 +57,21 @@ class DefectGanModel(BaseModel):
             self.diffaug_rng = ops.DiffAugRng(seed, opt.device)
         elif where != "host":
             raise ValueError(f"|diff_aug_rng {where}| is invalid (host | device)")
+        # opt.diff_aug_p / opt.ada_target (optim.ada_options): every policy of opt.diff_aug applies to a row with probability p, one
+        # fp32 word of device memory the draw launch reads -- fixed, or (ada_target) moved by the controller after every D update so
+        # that r_t = E[sign(D(real))] stays at the target (ops.AdaState).  Off: none of these exists and nothing below differs.
+        self.ada, self.diffaug_p = None, None
+        self.ada_ranks = None             # (set by parallel.attach_ddp: the reducer that sums the measured pair over the ranks)
+        ada = optim.ada_options(opt)
+        # A fixed p of 0 (no controller, so p stays 0) augments no row ever: that is opt.diff_aug = "", and the losses take that path
+        # (_diffaug_policy) -- no draw, no augment launch, and the G loss grouped as the trainer without DiffAugment groups it.
+        self.diffaug_never = ada is not None and ada["target"] is None and ada["p"] == 0.0
+        if ada is not None:
+            if ada["target"] is not None:
+                self.ada = ops.AdaState(opt.device, ada["p"], ada["target"], ada["interval"], ada["kimg"], ada["p_max"])
+                self.diffaug_p = self.ada.p
+            else:
+                self.diffaug_p = torch.tensor([ada["p"]], dtype=torch.float32, device=opt.device)
         # opt.mask_rng: the same choice for the MAE stage's patch masks ("host": utils/masks.py on the CPU RNG, the reference's masks;
         # "device": ops.mask_draw on a second generator, seeded by opt.mask_seed), under the same rules.
         self.mask_rng = None
@@ -144,12 +159,51 @@ class DefectGanModel(BaseModel):
             return live
         return tuple(self.ema.get(label, mod) for label, mod in zip(("G", "E", "mask_token"), live))
 
+    def _diffaug_policy(self):
+        """opt.diff_aug as the D and G losses apply it: "" where a fixed ``opt.diff_aug_p = 0`` says that no row is ever augmented"""
+        return "" if self.diffaug_never else getattr(self.opt, "diff_aug", "")
+
     def _diff_augment(self, x, policy):
         """DiffAugment on one batch the discriminator sees: the torch-op policy functions with host draws, or (diff_aug_rng
         'device') the fused kernels on a device-drawn table"""
         if self.diffaug_rng is None or not policy:
             return diff_augment(x, policy)
-        return ops.diff_augment(x if x.dtype == torch.float32 else x.float(), policy, rng=self.diffaug_rng)
+        x = x if x.dtype == torch.float32 else x.float()
+        if self.diffaug_p is None:
+            return ops.diff_augment(x, policy, rng=self.diffaug_rng)
+        # gated: under an active reducer the rows are this rank's rows of the global batch's table, so that N ranks see the gates
+        # (and parameters) one process sees on the whole batch -- the controller's integer sums then match it exactly
+        red = self.ada_ranks
+        with ops.diffaug_sharded(red.rank, red.world) if red is not None and red.world > 1 else contextlib.nullcontext():
+            return ops.diff_augment(x, policy, rng=self.diffaug_rng, p=self.diffaug_p)
+
+    # ---- checkpoints: the controller's words travel as <epoch>_ada.pth (the RNG stays out, as before) ---------------------
+    def _ada_path(self, run_name, epoch):
+        return self.opt.ckpt_dir / run_name / f"{epoch}_ada.pth"
+
+    def save(self, epoch):
+        super().save(epoch)
+        if self.ada is not None:
+            path = self._ada_path(self.opt.name, epoch)
+            path.parent.mkdir(parents=True, exist_ok=True)
+            torch.save({"p_rt": self.ada.p_rt.cpu(), "acc": self.ada.acc.cpu()}, path)
+
+    def load(self, epoch):
+        super().load(epoch)
+        if self.ada is not None:
+            path = self._ada_path(self.opt.load_model_name, epoch)
+            if path.exists():                 # (a run saved without the controller keeps the initial p)
+                stored = torch.load(path, map_location="cpu", weights_only=True)
+                p, rt = stored["p_rt"].tolist()
+                self.ada.set_state(dict(zip(("sum_sign", "n_logits", "rows", "calls"), stored["acc"].tolist()), p=p, rt=rt))
+
+    def _ada_update(self, rows, *real_logits):
+        """After D saw ``rows`` real images (training only): measure the sign of their logits and let the controller move p --
+        two small launches, and under ``attach_ddp`` one 16-byte SUM between them (``rows`` becomes the count over all ranks)."""
+        self.ada.measure(*real_logits)
+        if self.ada_ranks is not None:
+            rows = self.ada_ranks.ada_exchange(self.ada.pair, rows)
+        self.ada.apply(rows)
 
     def _netD_batched(self, *images):
         """netD(x) for several image batches in ONE pass over their concatenation.  The discriminator has no batch
@@ -380,7 +434,7 @@ class DefectGanModel(BaseModel):
         d_params = [p for p in self.netD.parameters() if p.requires_grad]
         for p in d_params:
             p.requires_grad_(False)
-        policy = getattr(self.opt, "diff_aug", "")            # DiffAugment on what D sees (defectgan_model.py:200-203)
+        policy = self._diffaug_policy()                       # DiffAugment on what D sees (defectgan_model.py:200-203)
         whole = paired and not policy
         try:
             if whole:
@@ -448,11 +502,14 @@ class DefectGanModel(BaseModel):
                     both_labels = torch.cat([df_labels, nm_labels], 0)
                 fakes, _ = self.netG(torch.cat([bg_data, df_data], 0), both_labels, feats)
                 fake_defects, fake_normals = fakes.split([bg_data.shape[0], df_data.shape[0]])
-        policy = getattr(self.opt, "diff_aug", "")            # defectgan_model.py:266-270: fakes first, then the real batches
+        policy = self._diffaug_policy()                       # defectgan_model.py:266-270: fakes first, then the real batches
         fake_defects, fake_normals = self._diff_augment(fake_defects.detach(), policy), self._diff_augment(fake_normals.detach(), policy)
         df_data, bg_data = self._diff_augment(df_data, policy), self._diff_augment(bg_data, policy)
         (fake_defects_src, _), (fake_normals_src, _), (real_defects_src, real_defects_cls), \
             (real_normals_src, real_normals_cls) = self._netD_batched(fake_defects, fake_normals, df_data, bg_data)
+        if self.ada is not None and self.netD.training and torch.is_grad_enabled():
+            # (the *_src outputs are logits: "bce" is ops.bce_logits)  the G step of this iteration draws with the new p
+            self._ada_update(df_data.shape[0] + bg_data.shape[0], real_defects_src, real_normals_src)
         gan_loss = [self._cal_loss(fake_defects_src, 0.0, "bce"), self._cal_loss(fake_normals_src, 0.0, "bce"),
                     self._cal_loss(real_defects_src, 1.0, "bce"), self._cal_loss(real_normals_src, 1.0, "bce")]
         clf_loss = [self._cal_loss(real_defects_cls, df_labels.view_as(real_defects_cls), self.clf_loss_type),

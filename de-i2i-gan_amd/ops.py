@@ -1996,10 +1996,18 @@ class DeviceRng:
 DiffAugRng = DeviceRng          # (the name it was introduced under)
 
 
-def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0):
+def _gate_word(p, device, what):
+    """``p`` of the gated draw: a one-element fp32 tensor on ``device`` (the launch reads it there)"""
+    if not isinstance(p, torch.Tensor) or p.numel() != 1 or p.dtype != torch.float32 or p.device != device or not p.is_contiguous():
+        raise ValueError(f"{what}: p is a one-element fp32 tensor on {device} (the draw launch reads it from device memory)")
+    return p
+
+
+def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0, p=None):
     """One dei2i_diffaug_draw launch on the current stream: -> (tab, runs), ``tab`` a device int32 (len(runs), n, 8) table of struct
     dei2i_diffaug_rec for global rows [row0, row0 + n), ``runs`` the (has_color, cut_h, cut_w) list of utils.diffaug.draw_params.
-    Nothing is read from the host RNG and nothing is uploaded."""
+    Nothing is read from the host RNG and nothing is uploaded.  ``p`` (a one-element fp32 device tensor in [0, 1]): the gated
+    draw dei2i_diffaug_draw_p instead -- each policy applies to a row with probability ``p``, read on the device by the launch."""
     from .utils.diffaug import REC_FIELDS, policy_runs
     names = policy_runs(policy)
     if not 0 < len(names) <= L.DIFFAUG_MAX_RUNS:
@@ -2012,16 +2020,84 @@ def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0):
         runs.append(("color" in run, int(h * 0.5 + 0.5) if cut else 0, int(w * 0.5 + 0.5) if cut else 0))
     tab = torch.empty((len(names), n, REC_FIELDS), dtype=torch.int32, device=rng.device)
     lib = _lib_for(tab)
-    L.check(lib.dei2i_diffaug_draw(rng.seed, _p(rng.counter), len(names), flags, n, int(row0), h, w, _p(tab), _stream()), "diffaug_draw")
+    if p is None:
+        L.check(lib.dei2i_diffaug_draw(rng.seed, _p(rng.counter), len(names), flags, n, int(row0), h, w, _p(tab), _stream()), "diffaug_draw")
+    else:
+        L.check(lib.dei2i_diffaug_draw_p(rng.seed, _p(rng.counter), len(names), flags, n, int(row0), h, w,
+                                         _p(_gate_word(p, rng.device, "diffaug_draw")), _p(tab), _stream()), "diffaug_draw_p")
     return tab, runs
 
 
-def diff_augment(x, policy="", rng=None):
+class AdaState:
+    """The device words of adaptive discriminator augmentation (csrc/ada.hip): ``p`` and ``rt`` (one-element fp32 views of one
+    buffer: the probability the gated draw reads, the last computed r_t = E[sign(D(real))]), the measured ``pair`` (int64: sum of
+    signs, logit count) and the accumulators ``acc`` (int64: sum_sign, n_logits, rows, calls).  All allocated here, outside any
+    capture; they must outlive every graph that recorded a launch on them.  ``measure`` then ``apply`` once per D update, on one
+    stream; between the two a data-parallel run SUMs ``pair`` over its ranks.  ``state()`` / ``set_state()`` synchronise: not for use
+    inside a step."""
+
+    def __init__(self, device, p=0.0, target=0.6, interval=4, kimg=500.0, p_max=1.0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"AdaState runs on the GPU; device {self.device} is not one (there is no CPU fallback)")
+        self.target, self.interval, self.p_max = float(target), int(interval), float(p_max)
+        self.inv_images = ctypes.c_float(1.0 / (float(kimg) * 1000.0)).value     # (once, as fp32: the kernel argument)
+        self.p_rt = torch.tensor([float(p), 0.0], dtype=torch.float32, device=self.device)
+        self.p, self.rt = self.p_rt[0:1], self.p_rt[1:2]
+        self.pair = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self.acc = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self.device = self.p_rt.device                       # (with its index)
+
+    def measure(self, *logits):
+        """``pair`` = (sum of sign, count) over every logit of the tensors: one launch per stretch of memory (tensors that are
+        consecutive slices of one buffer, such as the splits of a batched discriminator pass, are one stretch)"""
+        spans = []
+        for t in logits:
+            t = t.detach()
+            if t.device != self.device:
+                raise ValueError(f"AdaState.measure: the state lives on {self.device}, the logits on {t.device}")
+            t = (t if t.dtype == torch.float32 else t.float()).contiguous()
+            if t.numel() == 0:
+                continue
+            if spans and spans[-1][0].data_ptr() + 4 * spans[-1][1] == t.data_ptr() \
+                    and spans[-1][0].untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+                spans[-1][1] += t.numel()
+            else:
+                spans.append([t, t.numel()])
+        if not spans:
+            raise ValueError("AdaState.measure needs at least one logit")
+        lib = _lib_for(self.pair)
+        for i, (t, count) in enumerate(spans):
+            L.check(lib.dei2i_ada_measure(_p(t), count, _p(self.pair), int(i > 0), _stream()), "ada_measure")
+
+    def apply(self, rows):
+        """Add ``pair`` and ``rows`` (the real images the discriminator saw, over all ranks) to the accumulators; every ``interval``
+        calls move ``p`` by rows / (kimg * 1000) towards the target and start over"""
+        lib = _lib_for(self.pair)
+        L.check(lib.dei2i_ada_apply(_p(self.pair), int(rows), _p(self.p_rt), _p(self.acc), self.interval, self.target, self.inv_images,
+                                    self.p_max, _stream()), "ada_apply")
+
+    def state(self):
+        """-> {"p", "rt" (floats), "sum_sign", "n_logits", "rows", "calls" (ints)}"""
+        p, rt = self.p_rt.tolist()
+        return dict(zip(("sum_sign", "n_logits", "rows", "calls"), self.acc.tolist()), p=p, rt=rt)
+
+    def set_state(self, state):
+        torch.cuda.synchronize(self.device)                  # (launches queued on any stream read the old words)
+        self.p_rt.copy_(torch.tensor([state["p"], state["rt"]], dtype=torch.float32))
+        self.acc.copy_(torch.tensor([int(state[k]) for k in ("sum_sign", "n_logits", "rows", "calls")], dtype=torch.int64))
+        torch.cuda.synchronize(self.device)
+
+
+def diff_augment(x, policy="", rng=None, p=None):
     """DiffAugment(x, policy) of utils/diffaug.py on an NCHW fp32 GPU image batch, one or two launches per canonical-order policy
     run.  ``policy == ""`` returns ``x`` itself.  ``rng=None``: the same draws from the global CPU RNG as utils/diffaug.py, one
     upload of the parameter table per call.  ``rng`` a ``DiffAugRng``: the table is drawn on the device by one more launch
     (``diffaug_draw``) -- the CPU RNG is not touched, nothing is uploaded, and the call can be captured into a graph.
-    Inside ``diffaug_sharded`` ``x`` is one rank's rows of the global batch (above)."""
+    Inside ``diffaug_sharded`` ``x`` is one rank's rows of the global batch (above).  ``p`` (needs ``rng``): a one-element fp32 device
+    tensor, the probability with which each policy applies to a row (``diffaug_draw``); the apply launches are the same."""
+    if p is not None and rng is None:
+        raise ValueError("diff_augment: p gates the device-drawn table; it needs rng (a DiffAugRng)")
     if not policy:
         return x
     _require_gpu(x, "diff_augment")
@@ -2031,7 +2107,7 @@ def diff_augment(x, policy="", rng=None):
     if rng is not None:
         if rng.device != x.device:
             raise ValueError(f"diff_augment: the DiffAugRng lives on {rng.device}, the images on {x.device}")
-        tab, runs = diffaug_draw(rng, policy, n, h, w, row0=diffaug_shard[0] * n if diffaug_shard is not None else 0)
+        tab, runs = diffaug_draw(rng, policy, n, h, w, row0=diffaug_shard[0] * n if diffaug_shard is not None else 0, p=p)
         host = None
     else:
         from .utils.diffaug import draw_params

@@ -421,6 +421,39 @@ def clip_options(opt):
     return float(c)
 
 
+def ada_options(opt, diffaug_stage=True):
+    """-> None (``opt.diff_aug_p`` absent or None and ``opt.ada_target`` absent, None or 0: DiffAugment as it was), or the dict
+    {"p": the initial (or, without a target, the fixed) probability, "target": r_t's target or None (no controller), "interval"
+    (D updates per adjustment, default 4), "kimg" (thousands of real images for p to cross 0..1, default 500), "p_max" (default 1)}.
+    ``diffaug_stage``: whether the asking trainer's stage applies DiffAugment at all (the MAE stage does not)."""
+    p, target = getattr(opt, "diff_aug_p", None), getattr(opt, "ada_target", None)
+    target = None if target is None or target == 0 else target
+    if p is None and target is None:
+        return None
+    on = "diff_aug_p" if p is not None else "ada_target"
+    if not diffaug_stage:
+        raise ValueError(f"|{on}| gates DiffAugment, which the MAE stage does not apply (the defectGAN stage only)")
+    if p is not None and not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"|diff_aug_p {p}| is invalid (0 <= diff_aug_p <= 1; None turns the gate off)")
+    if target is not None and not 0.0 < float(target) < 1.0:
+        raise ValueError(f"|ada_target {target}| is invalid (0 < ada_target < 1; None or 0 turns the controller off)")
+    if not getattr(opt, "diff_aug", ""):
+        raise ValueError(f"|{on}| needs a non-empty diff_aug (the policies it gates)")
+    if getattr(opt, "diff_aug_rng", None) != "device":
+        raise ValueError(f"|{on}| needs diff_aug_rng='device' (the gates are drawn on the GPU, next to the parameters)")
+    interval, kimg, p_max = getattr(opt, "ada_interval", None), getattr(opt, "ada_kimg", None), getattr(opt, "ada_p_max", None)
+    interval, kimg, p_max = 4 if interval is None else interval, 500.0 if kimg is None else kimg, 1.0 if p_max is None else p_max
+    if target is not None:
+        if int(interval) != interval or interval <= 0:
+            raise ValueError(f"|ada_interval {interval}| is invalid (a whole number of D updates > 0)")
+        if not float(kimg) > 0.0:
+            raise ValueError(f"|ada_kimg {kimg}| is invalid (> 0)")
+        if not 0.0 <= float(p_max) <= 1.0:
+            raise ValueError(f"|ada_p_max {p_max}| is invalid (0 <= ada_p_max <= 1)")
+    return {"p": 0.0 if p is None else float(p), "target": None if target is None else float(target), "interval": int(interval),
+            "kimg": float(kimg), "p_max": float(p_max)}
+
+
 def ema_weight(iters, start_iter, beta):
     """The lerp weight of the G update that ends with ``trainer.iters == iters``: 0 (the copy follows the live weights) up to
     ``start_iter``, ``beta`` after it."""

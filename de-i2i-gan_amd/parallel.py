@@ -248,6 +248,16 @@ class GradReducer:
         self.stats["sync_bn_collectives"] += 1
         self.stats["sync_bn_bytes"] += msg.numel() * msg.element_size()
 
+    def ada_exchange(self, pair: torch.Tensor, rows: int) -> int:
+        """SUM ``pair`` (ops.AdaState's measured int64 (sum of signs, logit count): 16 bytes) over the ranks in place, between the
+        controller's two launches and in the current stream's order; -> the number of real images over all ranks (every rank holds
+        ``rows``).  Integers: N ranks on their rows then hold the accumulators and the p of one process on the whole batch."""
+        if not self.active:
+            return rows
+        dist.all_reduce(pair, op=dist.ReduceOp.SUM, group=self.pg)
+        self.stats["ada_collectives"] = self.stats.get("ada_collectives", 0) + 1
+        return rows * self.world
+
     def bn_scope(self):
         """The scope a trainer runs its model calls in: ``ops.bn_sync`` of this reducer with ``sync_bn`` on an active group, else nothing."""
         if self.sync_bn and self.active:
@@ -316,6 +326,8 @@ def attach_ddp(trainer, process_group=None, sync_bn: bool = False, **kw) -> Grad
         red.broadcast_parameters(mask_token)
     if sync_bn and red.world > 1:                                   # the MAE stage's mask draws: the same global draw on every rank
         _broadcast_rng_state(process_group, torch.device(trainer.opt.device))
+    if getattr(trainer.model, "diffaug_p", None) is not None:       # opt.diff_aug_p / opt.ada_target: the global batch's gates on every
+        trainer.model.ada_ranks = red                               # rank (one diff_aug_seed), the measured pair summed over the ranks
     trainer.reducer = red
     return red
 

@@ -8,7 +8,7 @@ import torch
 from torch import optim
 
 from ..models import create_model
-from ..optim import FusedAdam, FusedRMSprop, FusedSGD, clip_options, ema_options
+from ..optim import FusedAdam, FusedRMSprop, FusedSGD, ada_options, clip_options, ema_options
 
 
 # opt.optimizer -> keyword arguments of the fused optimizer (the reference builds torch.optim.Adam(betas=(0.5, 0.999)) /
@@ -25,12 +25,16 @@ class BaseTrainer:
     ``losses`` / ``dis_outputs`` (dict of lists), ``iters`` / ``first_epoch`` (restored from ``iter.txt`` when continuing),
     ``optimizers`` / ``schedulers`` keyed by network name; the schedulers are stepped ``first_epoch`` times at construction
     like the reference does."""
+    diff_augments = False        # whether the trainer's stage applies opt.diff_aug (optim.ada_options)
 
     def __init__(self, opt):
         self.opt = opt
         ema_options(opt)                  # (an invalid opt.ema_beta is refused before anything is built)
         # opt.max_grad_norm > 0: every FusedAdam clips its gradients to this global L2 norm inside the update (optim.FusedAdam)
         self.max_grad_norm = clip_options(opt)
+        # opt.diff_aug_p / opt.ada_target: gated DiffAugment and its controller (the defectGAN stage; refused elsewhere, and an
+        # invalid combination before anything is built)
+        self.ada_opts = ada_options(opt, diffaug_stage=self.diff_augments)
         self.model = create_model(opt)
         # opt.ema_beta > 0: the EMA copies of what the G optimizer trains start from the weights just initialised or restored
         self.model.create_ema(self._restore_or_init_weights(opt))

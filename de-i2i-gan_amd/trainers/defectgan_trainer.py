@@ -15,6 +15,8 @@ from .base_trainer import BaseTrainer
 
 
 class DefectGanTrainer(BaseTrainer):
+    diff_augments = True
+
     def __init__(self, opt):
         super().__init__(opt)
         assert len(opt.loss_weight) == 5, f"length of loss weights must be 5, not {len(opt.loss_weight)}"
@@ -26,6 +28,8 @@ class DefectGanTrainer(BaseTrainer):
             self.loss_types.append("distill")
         if self.max_grad_norm is not None:                # opt.max_grad_norm: the norm before clipping, per update
             self.loss_types.append("grad_norm")
+        if self.model.ada is not None:                    # opt.ada_target: p and r_t after the controller's launch, per D update
+            self.loss_types.append("ada")
         self._init_losses()
         if opt.phase == "val":
             raise NotImplementedError("phase='val' builds FID/LPIPS metric networks (downloaded weights): out of scope")
@@ -79,6 +83,9 @@ class DefectGanTrainer(BaseTrainer):
             self.reducer.reduce(self.model.netD)
         self.optimizers["D"].step()
         norm_keys, norms = self._grad_norm_records("D")
+        ada = self.model.ada
+        if ada is not None:                               # read from device memory like a loss (deferred, or by the replay)
+            norm_keys, norms = norm_keys + [("ada", "p"), ("ada", "rt")], norms + [ada.p[0], ada.rt[0]]
         self._record([("gan", "D"), ("clf", "D")] + norm_keys, [gan_loss, clf_loss] + norms)
 
     def step(self, bg_data, df_labels, df_data):

@@ -318,7 +318,10 @@ int dei2i_ema_lerp_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n
  * tab: device array of N records; a = 1, b = k = beta = 0 without color, ty = tx = 0 without translation, ch = cw = 0 without
  * cutout (the cut window is rows [top, top + ch) x cols [left, left + cw)).  mode 0: forward; 1: forward without beta (linear part);
  * 2: adjoint (input gradient of src = the output gradient).  partial: dei2i_diffaug_partial_floats(N) floats when color != 0.
- * Deterministic (fixed-order reductions, no atomics). */
+ * Deterministic (fixed-order reductions, no atomics).
+ * One row of a run WITH cutout is left uncut by top = H, left = W (ch and cw belong to the run, not to the row): the window
+ * [H, H + ch) x [W, W + cw) lies off the image, and in_hole / fwd_valid of csrc/diffaug.hip only test coordinates inside it, in
+ * all three modes (dei2i_diffaug_draw_p writes such rows). */
 typedef struct dei2i_diffaug_rec {
   float a, b, k, beta;
   int ty, tx, top, left;
@@ -340,6 +343,34 @@ int dei2i_diffaug(int mode, int N, int C, int H, int W, int ch, int cw, int colo
 #define DEI2I_DIFFAUG_MAX_RUNS 16
 int dei2i_diffaug_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
                        dei2i_diffaug_rec* tab, dei2i_stream s);
+/* The same table with a gate per row and policy (adaptive discriminator augmentation): blocks 0 and 1 give the parameters exactly
+ * as above, block 2 (counter word run | 2 << 16) gives three gate floats on the same grid, x0 for color, x1 for translation, x2
+ * for cutout, and a policy of the run applies to the row iff (x >> 8) * 2^-24 < *p_dev (one fp32 word of device memory in [0, 1],
+ * read by the launch: nothing crosses to the host).  A policy that does not apply leaves its identity in the record: a = 1,
+ * b = k = beta = 0; ty = tx = 0; top = H, left = W.  The cut size ch x cw is an argument of dei2i_diffaug for the whole run, so
+ * the empty window is the window moved off the image: rows [H, H + ch) x cols [W, W + cw) hold no pixel (i, j) or source
+ * (i + ty, j + tx) of an H x W image, whatever the mode -- every hole test is made on coordinates inside the image.  p = 1 gives the
+ * table of dei2i_diffaug_draw for the same (seed, call, run, row) bit for bit, p = 0 identity records only, and a row's parameters
+ * do not depend on its gates.  One launch of one workgroup, no atomics; *counter_dev advances by exactly 1 under the ordering rule
+ * above.  BAD_ARG: as dei2i_diffaug_draw, and a null p_dev. */
+int dei2i_diffaug_draw_p(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
+                         const float* p_dev, dei2i_diffaug_rec* tab, dei2i_stream s);
+
+/* ---- the controller of p (csrc/ada.hip; Karras et al. 2020: r_t = E[sign(D(real))] held at a target) ----
+ * dei2i_ada_measure: one workgroup over n fp32 logits; pair_dev[0] = sum of (x > 0) - (x < 0), pair_dev[1] = n, two int64 words,
+ * written, or added to when accumulate != 0.  NaN and +-0 count 0 towards the sum and 1 towards n.  Integer sums: exact and
+ * independent of order (wave shuffles, then LDS; thread 0 stores).  BAD_ARG: null pointers, n <= 0, n >= 2^31.
+ *
+ * dei2i_ada_apply: one thread.  p_rt_dev: two fp32 words (p, rt = the last computed r_t).  acc_dev: four int64 words (sum_sign,
+ * n_logits, rows, calls).  Each call adds pair_dev[0], pair_dev[1], rows and 1 to them; when calls reaches interval:
+ *   rt = (float)sum_sign / (float)n_logits;  step = (float)rows * inv_images;
+ *   p = min(max(p + (rt > target ? step : rt < target ? -step : 0), 0), p_max);  acc_dev[0..3] = 0
+ * in fp32 without contraction (inv_images = 1 / (images per unit of p), computed once by the host).  Launches that share the
+ * words are ordered on one stream or in one captured graph; neither launch reads on the host or allocates.  BAD_ARG: null
+ * pointers, interval <= 0, rows <= 0, p_max outside [0, 1], target outside (-1, 1), inv_images negative or NaN. */
+int dei2i_ada_measure(const float* logits, int64_t n, int64_t* pair_dev, int accumulate, dei2i_stream s);
+int dei2i_ada_apply(const int64_t* pair_dev, int64_t rows, float* p_rt_dev, int64_t* acc_dev, int interval, float target,
+                    float inv_images, float p_max, dei2i_stream s);
 
 /* ---- device-drawn shifted patch masks of the MAE stage (utils/masks.py) and the mask-token fill (csrc/mask.hip) ----
  * The patch grid of an H x W image is GH x GW = (H / patch + 1) x (W / patch + 1) (H, W multiples of patch); pixel (i, j) of row n

@@ -60,6 +60,10 @@ def run(opts, mode, device, clip="off"):
     if opts.diff_aug_rng is not None:
         opt.diff_aug_rng = opts.diff_aug_rng
         opt.diff_aug_seed = opts.diff_aug_seed
+    if opts.diff_aug_p is not None:
+        opt.diff_aug_p = opts.diff_aug_p
+    if opts.ada_target:
+        opt.ada_target = opts.ada_target
     if opts.mask_rng is not None:
         opt.mask_rng = opts.mask_rng
         opt.mask_seed = opts.mask_seed
@@ -119,6 +123,8 @@ def main():
     ap.add_argument("--diff-aug", dest="diff_aug", default="", metavar="POLICY", help="e.g. color,translation,cutout ('' = none)")
     ap.add_argument("--diff-aug-rng", dest="diff_aug_rng", default=None, choices=["host", "device"])
     ap.add_argument("--diff-aug-seed", dest="diff_aug_seed", type=int, default=1234)
+    ap.add_argument("--diff-aug-p", dest="diff_aug_p", type=float, default=None, help="opt.diff_aug_p (needs --diff-aug-rng device)")
+    ap.add_argument("--ada-target", dest="ada_target", type=float, default=None, help="opt.ada_target (the controller; 0 / absent = off)")
     ap.add_argument("--ema-beta", dest="ema_beta", type=float, default=0.0, help="opt.ema_beta (0 = no EMA, the default)")
     ap.add_argument("--ema-start-iter", dest="ema_start_iter", type=int, default=0, help="opt.ema_start_iter")
     ap.add_argument("--max-grad-norm", dest="max_grad_norm", type=float, default=None, help="the global gradient norm --clip torch / fused clip to")
