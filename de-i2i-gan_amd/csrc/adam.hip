@@ -184,11 +184,17 @@ static dim3 table_grid(int64_t max_n, int per_thread, int64_t cap, int count) {
   return dim3((unsigned)bx, (unsigned)count);
 }
 
-template <bool COUPLED, bool DEV, bool CLIP = false>
-static int adam_launch(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2, float eps,
-                       float bias_c1, float bias_c2_sqrt, float grad_scale, float keep, float wd, const float* hyper_dev,
-                       const int* index_dev, int rows, dei2i_stream s, const float* scale_dev = nullptr) {
-  hipLaunchKernelGGL((adam_kernel<COUPLED, DEV, CLIP>), table_grid(max_n, 4, 512, count), dim3(256), 0, (hipStream_t)s, table_dev,
+// The one launch of adam_kernel: the runtime triple (coupled, dev, clip) picks the instance.  A DEV launch needs the rows and their
+// index, a CLIP launch the scale; what a form does not read is whatever its entry point passes for it.
+static int adam_dispatch(bool coupled, bool dev, bool clip, const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr,
+                         float beta1, float beta2, float eps, float bias_c1, float bias_c2_sqrt, float grad_scale, float keep, float wd,
+                         const float* hyper_dev, const int* index_dev, int rows, const float* scale_dev, dei2i_stream s) {
+  if (!table_dev || count <= 0 || max_n <= 0 || (dev && (!hyper_dev || !index_dev || rows <= 0)) || (clip && !scale_dev))
+    return DEI2I_ERR_BAD_ARG;
+  static constexpr decltype(&adam_kernel<false, false, false>) kernels[8] = {
+      adam_kernel<false, false, false>, adam_kernel<false, false, true>, adam_kernel<false, true, false>, adam_kernel<false, true, true>,
+      adam_kernel<true, false, false>,  adam_kernel<true, false, true>,  adam_kernel<true, true, false>,  adam_kernel<true, true, true>};
+  hipLaunchKernelGGL(kernels[4 * coupled + 2 * dev + clip], table_grid(max_n, 4, 512, count), dim3(256), 0, (hipStream_t)s, table_dev,
                      lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, keep, wd, hyper_dev, index_dev, rows, scale_dev);
   return (int)hipGetLastError();
 }
@@ -201,59 +207,48 @@ extern "C" int dei2i_sgd_rmsprop_step(const dei2i_adam_rec* table_dev, int count
   return (int)hipGetLastError();
 }
 
+// (lr, the bias corrections and `keep` as arguments; decoupled: p *= 1 - lr * decoupled_decay, _l2: g += weight_decay * p)
 extern "C" int dei2i_adam_step(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2,
                                float eps, float bias_c1, float bias_c2_sqrt, float grad_scale, float decoupled_decay,
                                dei2i_stream s) {
-  if (!table_dev || count <= 0 || max_n <= 0) return DEI2I_ERR_BAD_ARG;
-  return adam_launch<false, false>(table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale,
-                                   1.f - lr * decoupled_decay, 0.f, nullptr, nullptr, 0, s);
+  return adam_dispatch(false, false, false, table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale,
+                       1.f - lr * decoupled_decay, 0.f, nullptr, nullptr, 0, nullptr, s);
 }
 
 extern "C" int dei2i_adam_step_l2(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2,
                                   float eps, float bias_c1, float bias_c2_sqrt, float grad_scale, float weight_decay, dei2i_stream s) {
-  if (!table_dev || count <= 0 || max_n <= 0) return DEI2I_ERR_BAD_ARG;
-  return adam_launch<true, false>(table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, 1.f,
-                                  weight_decay, nullptr, nullptr, 0, s);
+  return adam_dispatch(true, false, false, table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, grad_scale, 1.f,
+                       weight_decay, nullptr, nullptr, 0, nullptr, s);
 }
 
 // (the _dev forms: lr, the bias corrections and `keep` come from `hyper_dev`; the kernel arguments of those names are not read)
 extern "C" int dei2i_adam_step_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev,
                                    const int* index_dev, int rows, float beta1, float beta2, float eps, float grad_scale,
                                    dei2i_stream s) {
-  if (!table_dev || count <= 0 || max_n <= 0 || !hyper_dev || !index_dev || rows <= 0) return DEI2I_ERR_BAD_ARG;
-  return adam_launch<false, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, 0.f, hyper_dev,
-                                  index_dev, rows, s);
+  return adam_dispatch(false, true, false, table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, 0.f, hyper_dev,
+                       index_dev, rows, nullptr, s);
 }
 
 extern "C" int dei2i_adam_step_l2_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev,
                                       const int* index_dev, int rows, float beta1, float beta2, float eps, float grad_scale,
                                       float weight_decay, dei2i_stream s) {
-  if (!table_dev || count <= 0 || max_n <= 0 || !hyper_dev || !index_dev || rows <= 0) return DEI2I_ERR_BAD_ARG;
-  return adam_launch<true, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, weight_decay,
-                                 hyper_dev, index_dev, rows, s);
+  return adam_dispatch(true, true, false, table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, grad_scale, 1.f, weight_decay,
+                       hyper_dev, index_dev, rows, nullptr, s);
 }
 
 // (the _clip forms: grad_scale comes from *scale_dev, where dei2i_grad_clip_finalize left it; `coupled` selects the _l2 update)
 extern "C" int dei2i_adam_step_clip(const dei2i_adam_rec* table_dev, int count, int64_t max_n, float lr, float beta1, float beta2,
                                     float eps, float bias_c1, float bias_c2_sqrt, const float* scale_dev, int coupled,
                                     float weight_decay, dei2i_stream s) {
-  if (!table_dev || count <= 0 || max_n <= 0 || !scale_dev) return DEI2I_ERR_BAD_ARG;
-  if (coupled)
-    return adam_launch<true, false, true>(table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, 1.f, 1.f,
-                                          weight_decay, nullptr, nullptr, 0, s, scale_dev);
-  return adam_launch<false, false, true>(table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, 1.f,
-                                         1.f - lr * weight_decay, 0.f, nullptr, nullptr, 0, s, scale_dev);
+  return adam_dispatch(coupled != 0, false, true, table_dev, count, max_n, lr, beta1, beta2, eps, bias_c1, bias_c2_sqrt, 1.f,
+                       coupled ? 1.f : 1.f - lr * weight_decay, coupled ? weight_decay : 0.f, nullptr, nullptr, 0, scale_dev, s);
 }
 
 extern "C" int dei2i_adam_step_clip_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev,
                                         const int* index_dev, int rows, float beta1, float beta2, float eps,
                                         const float* scale_dev, int coupled, float weight_decay, dei2i_stream s) {
-  if (!table_dev || count <= 0 || max_n <= 0 || !hyper_dev || !index_dev || rows <= 0 || !scale_dev) return DEI2I_ERR_BAD_ARG;
-  if (coupled)
-    return adam_launch<true, true, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, 1.f, 1.f, weight_decay,
-                                         hyper_dev, index_dev, rows, s, scale_dev);
-  return adam_launch<false, true, true>(table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, 1.f, 1.f, 0.f, hyper_dev,
-                                        index_dev, rows, s, scale_dev);
+  return adam_dispatch(coupled != 0, true, true, table_dev, count, max_n, 0.f, beta1, beta2, eps, 1.f, 1.f, 1.f, 1.f,
+                       coupled ? weight_decay : 0.f, hyper_dev, index_dev, rows, scale_dev, s);
 }
 
 extern "C" int dei2i_grad_sumsq_blocks(int64_t max_n) { return (int)table_grid(max_n, 4, 512, 1).x; }

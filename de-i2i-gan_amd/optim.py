@@ -7,13 +7,15 @@ mae_trainer.py:28,139-158).  Semantics = torch.optim.Adam (no amsgrad), or torch
 ``ema_lerp_`` is stargan-v2's parameter EMA on the same pointer table (csrc/adam.hip); ``EmaGroup`` is the defectGAN / MAE
 trainers' (``opt.ema_beta``): the same launch per G update, buffers included, and a device-read form for captured graphs.
 
-Under graph capture (``torch.cuda.is_current_stream_capturing()``) ``FusedAdam.step`` records the ``_dev`` kernels instead:
-they read (lr, 1 - b1^t, sqrt(1 - b2^t), 1 - lr*wd) from a device table of the next ``HYPER_ROWS`` steps
-(``adam_hyper_rows``, the same host arithmetic as the eager launch), indexed by a device counter that a one-thread kernel
-advances after each update, so a replayed step sees its own step's values without a host wait.  ``graph_take_plan`` hands
-the recorded groups to the owner of the graph, which calls ``graph_prepare`` before and ``graph_finish`` after every replay:
-the host work the graph cannot do (uploading the pointer tables once, rewriting the rows when the lr changed or they run
-out, ``state["step"]`` and the ``_dei2i_epoch`` stamps).
+``FusedAdam.step`` is one path, eager or under graph capture (``torch.cuda.is_current_stream_capturing()``): it gathers the launch
+groups, takes each group's device pointer table from the cache (capturing: from a slot ``graph_reserve`` made) and hands it to
+``_launch``, which picks the entry point.  Captured launches are the ``_dev`` kernels: they read (lr, 1 - b1^t, sqrt(1 - b2^t),
+1 - lr*wd) from a device table of the next ``HYPER_ROWS`` steps (``adam_hyper_rows``, the same host arithmetic as the eager
+launch), indexed by a device counter that a one-thread kernel advances after each update, so a replayed step sees its own step's
+values without a host wait.  ``graph_take_plan`` hands the recorded launches (``_CapturedLaunch``; ``EmaGroup`` keeps the same
+records through the same ``_GraphCapture``) to the owner of the graph, which calls ``graph_prepare`` before and ``graph_finish``
+after every replay: the host work the graph cannot do (uploading the pointer tables once, rewriting the rows when the lr changed
+or they run out, ``state["step"]`` and the ``_dei2i_epoch`` stamps).
 
 ``max_grad_norm`` (``torch.nn.utils.clip_grad_norm_`` over every parameter of the optimizer, L2): the step first sums g^2 over
 each launch group's pointer table (``dei2i_grad_sumsq``, fixed-order partials, no atomics), one more launch turns the partials into
@@ -27,6 +29,10 @@ import torch
 
 from . import _lib as L
 from . import ops
+
+
+def _dev_ptr(tensor, offset=0):
+    return ctypes.c_void_p(tensor.data_ptr() + offset)
 
 
 class _PointerTable:
@@ -67,10 +73,62 @@ class _PointerTable:
 
     def args(self, table_dev):
         """the (table_dev, count, max_n) every entry point of csrc/adam.hip begins with"""
-        return ctypes.c_void_p(table_dev.data_ptr()), len(self.rows), self.max_n
+        return _dev_ptr(table_dev), len(self.rows), self.max_n
 
 
-class FusedAdam(torch.optim.Optimizer):
+class _FusedOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers' ``step`` methods share: the closure and the cache of uploaded pointer tables."""
+
+    @staticmethod
+    def _closure_loss(closure):
+        if closure is None:
+            return None
+        with torch.enable_grad():
+            return closure()
+
+    def _tables(self):
+        return self.__dict__.setdefault("_table_cache", {})
+
+
+class _CapturedLaunch:
+    """One multi-tensor launch recorded into a graph.  ``table``: its pointer table on the host (holding the graph's own gradients
+    or sources, at fixed addresses from replay to replay), which ``upload`` copies into the reserved ``table_dev`` once, after the
+    capture and before the first replay.  ``rows``: the device rows (a ``_RowTable``) the launch reads at a device index, or None.
+    ``info``, FusedAdam's: ``group`` (index), ``params``, ``wd`` (decoupled), ``frozen``: the (max_grad_norm or None, grad_scale)
+    recorded as launch arguments, ``clip``: the clipping buffers the graph reads and writes by address, kept alive with it."""
+
+    def __init__(self, table, table_dev, rows=None, **info):
+        self.table, self.table_dev, self.rows, self.uploaded = table, table_dev, rows, False
+        self.__dict__.update(info)
+
+    def upload(self):
+        if not self.uploaded:
+            self.table.upload(into=self.table_dev)      # (a reserved slot: rows for the whole group)
+            self.uploaded = True
+
+
+class _GraphCapture:
+    """The bookkeeping of the capture protocol, for FusedAdam and EmaGroup.  ``graph_reserve`` leaves ``{key: [slots]}``: device
+    buffers made before the capture (one allocated inside it comes from the graph's pool, whose blocks earlier nodes of the same
+    replay may use as scratch -- they would overwrite what ``graph_prepare`` uploaded).  The recording takes them one by one and
+    notes each launch; ``graph_take_plan`` hands the notes to the owner of the graph."""
+
+    def _take_reserved(self, key, error):
+        slots = self.__dict__.get("_graph_reserve", {}).get(key)
+        if not slots:
+            raise RuntimeError(error)
+        return slots.pop(0)
+
+    def _recorded(self, launch):
+        self.__dict__.setdefault("_graph_plan", []).append(launch)
+
+    def graph_take_plan(self):
+        """-> the launches recorded since the last call (the graph just captured owns them); unused reserved tables are dropped"""
+        self.__dict__.pop("_graph_reserve", None)
+        return self.__dict__.pop("_graph_plan", [])
+
+
+class FusedAdam(_FusedOptimizer, _GraphCapture):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, weight_decay=0.0, decoupled=True,
                  max_grad_norm=None):
         """``decoupled=False``: torch.optim.Adam's weight decay (L2: the gradient becomes g + wd * p before the moments -- what
@@ -116,60 +174,73 @@ class FusedAdam(torch.optim.Optimizer):
     def _table(self, plist):
         return _PointerTable("FusedAdam", [(p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in plist])
 
+    @staticmethod
+    def _reach(p, st):
+        if len(st) == 0:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        st["step"] += 1
+        return st["step"]
+
+    @staticmethod
+    def _reach_captured(p, st):            # (host state is left to graph_finish: the capture runs nothing)
+        if len(st) == 0:                   # zeros_like inside the capture would reset the moments on every replay
+            raise RuntimeError("FusedAdam: a parameter received its first gradient while a graph was being captured "
+                               "(capture after the set of parameters with a gradient has settled: raise graph_warmup)")
+        return st["step"] + 1
+
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        if torch.cuda.is_current_stream_capturing():
-            self._step_captured()
-            return loss
-
-        def reach(p, st):
-            if len(st) == 0:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            st["step"] += 1
-            return st["step"]
-
+        """One pointer table per launch group serves the norm (``max_grad_norm``) and the update, so a gradient that had to be copied
+        is copied once.  Eager, it comes from the cache.  Recorded into a graph, it is a slot ``graph_reserve`` made, which
+        ``graph_prepare`` fills after the capture: the gradients it points to are the graph's own, at fixed addresses."""
+        loss = self._closure_loss(closure)
+        capturing = torch.cuda.is_current_stream_capturing()
         max_norm = self._clip_norm()
-        if max_norm is not None:
-            self._step_clipped(list(self._launch_groups(reach)), max_norm)
-            return loss
-        for _, group, t, plist, wd, coupled in self._launch_groups(reach):
-            b1, b2 = group["betas"]
-            # coupled L2 decay (g*grad_scale + wd*p) inside the kernel: p.grad is left as the caller's
-            self._launch(plist, t, float(group["lr"]), b1, b2, group["eps"], wd, coupled)
+        launches = []
+        for gi, group, t, plist, wd, coupled in self._launch_groups(self._reach_captured if capturing else self._reach):
+            table = self._table(plist)
+            if capturing:
+                table_dev, hyper = self._take_reserved(gi, "FusedAdam: no table reserved for this group (call graph_reserve() "
+                                                           "before the capture)")
+                hyper.t0, hyper.t, hyper.key = t, t, None
+            else:
+                table_dev, hyper = table.cached(self._tables()), None
+            launches.append((gi, group, t, plist, wd, coupled, table, table_dev, hyper))
+        scale = None
+        if launches and max_norm is not None:      # (buffers reserved before a capture, like the tables: never allocated inside it)
+            scale = self._clip_scale(ops._lib_for(launches[0][3][0]), [(table, table_dev) for *_, table, table_dev, _ in launches],
+                                     max_norm, reserve=not capturing)
+        for launch in launches:
+            self._launch(scale, max_norm, *launch)
         return loss
 
-    def _launch(self, plist, t, lr, b1, b2, eps, weight_decay=0.0, coupled=False):
-        lib = ops._lib_for(plist[0])
-        table = self._table(plist)
-        table_dev = table.cached(self.__dict__.setdefault("_table_cache", {}))
-        step = lib.dei2i_adam_step_l2 if coupled else lib.dei2i_adam_step
-        L.check(step(*table.args(table_dev), lr, b1, b2, eps, 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), self.grad_scale,
-                     weight_decay, ops._stream()), "adam_step")
-        ops.mark_written(*plist)
+    def _launch(self, scale, max_norm, gi, group, t, plist, wd, coupled, table, table_dev, hyper):
+        """One group's update.  ``hyper`` None: the step's values go by value; else (under capture) the kernel reads them from
+        ``hyper``'s rows, one more launch advances their index, and the launch is noted for ``graph_prepare``, which checks the
+        arguments frozen into the graph.  ``scale``: where ``_clip_scale`` left the gradient scale, or None: ``grad_scale``.
+        Coupled L2 decay (g*grad_scale + wd*p) happens inside the kernel: p.grad is left as the caller's."""
+        lib, dev = ops._lib_for(plist[0]), hyper is not None
+        b1, b2 = group["betas"]
+        if scale is not None:
+            step, rest = lib.dei2i_adam_step_clip_dev if dev else lib.dei2i_adam_step_clip, (scale, int(coupled), wd)
+        elif coupled:
+            step, rest = lib.dei2i_adam_step_l2_dev if dev else lib.dei2i_adam_step_l2, (self.grad_scale, wd)
+        else:
+            step, rest = (lib.dei2i_adam_step_dev, (self.grad_scale,)) if dev else (lib.dei2i_adam_step, (self.grad_scale, wd))
+        values = ((_dev_ptr(hyper.table), _dev_ptr(hyper.index), hyper.rows, b1, b2, group["eps"]) if dev else
+                  (float(group["lr"]), b1, b2, group["eps"], 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t)))
+        L.check(step(*table.args(table_dev), *values, *rest, ops._stream()),
+                "adam_step" + ("_clip" if scale is not None else "") + ("_dev" if dev else ""))
+        if dev:
+            L.check(lib.dei2i_index_advance(_dev_ptr(hyper.index), ops._stream()), "index_advance")
+            self._recorded(_CapturedLaunch(table, table_dev, hyper, group=gi, params=plist, wd=0.0 if coupled else wd,
+                                           frozen=(max_norm, self.grad_scale),
+                                           clip=self.__dict__.get("_clip_bufs") if scale is not None else None))
+        ops.mark_written(*plist)           # (under capture too: later passes of the capture must repack)
 
     # ---- global-norm clipping -----------------------------------------------------------------------------------------
-    def _step_clipped(self, groups, max_norm):
-        """The eager step with clipping: the norm over every launch group, then each group's update on the shared scale.  One
-        pointer table per group serves both, so a gradient that had to be copied is copied once."""
-        if not groups:
-            return
-        lib = ops._lib_for(groups[0][3][0])
-        cache = self.__dict__.setdefault("_table_cache", {})
-        tables = [self._table(plist) for _, _, _, plist, _, _ in groups]
-        tables = [(table, table.cached(cache)) for table in tables]
-        scale = self._clip_scale(lib, tables, max_norm, reserve=True)
-        for (_, group, t, plist, wd, coupled), (table, table_dev) in zip(groups, tables):
-            b1, b2 = group["betas"]
-            L.check(lib.dei2i_adam_step_clip(*table.args(table_dev), float(group["lr"]), b1, b2, group["eps"], 1.0 - b1 ** t,
-                                             math.sqrt(1.0 - b2 ** t), scale, int(coupled), wd, ops._stream()), "adam_step_clip")
-            ops.mark_written(*plist)
-
     def _clip_buffers(self, reserve):
         """-> (partials, out): room for the partial sums of any split of the parameters into launch groups (a group's grid is no
         wider than its longest parameter's, its rows no more than its parameters), and (norm, scale).  Both persist; ``reserve``
@@ -199,61 +270,13 @@ class FusedAdam(torch.optim.Optimizer):
             cells = lib.dei2i_grad_sumsq_blocks(table.max_n) * len(table.rows)
             if used + cells > partial.numel():
                 raise RuntimeError("FusedAdam: the clipping buffers are too small for this step's launch groups")
-            L.check(lib.dei2i_grad_sumsq(*table.args(table_dev), ctypes.c_void_p(partial.data_ptr() + 4 * used), ops._stream()),
-                    "grad_sumsq")
+            L.check(lib.dei2i_grad_sumsq(*table.args(table_dev), _dev_ptr(partial, 4 * used), ops._stream()), "grad_sumsq")
             used += cells
-        L.check(lib.dei2i_grad_clip_finalize(ctypes.c_void_p(partial.data_ptr()), used, self.grad_scale, max_norm,
-                                             ctypes.c_void_p(out.data_ptr()), ops._stream()), "grad_clip_finalize")
-        return ctypes.c_void_p(out.data_ptr() + 4)
+        L.check(lib.dei2i_grad_clip_finalize(_dev_ptr(partial), used, self.grad_scale, max_norm, _dev_ptr(out), ops._stream()),
+                "grad_clip_finalize")
+        return _dev_ptr(out, 4)
 
     # ---- graph capture ------------------------------------------------------------------------------------------------
-    def _step_captured(self):
-        """The step as recorded into a graph: the eager step's grouping (by the step count each parameter reaches), one
-        ``_dev`` launch + one index advance per group (with ``max_grad_norm``: the norm launches first, then the ``_clip_dev``
-        form; ``max_grad_norm`` and ``grad_scale`` are arguments frozen into the graph, which ``graph_prepare`` checks).  Host
-        state (``state["step"]``) is left to ``graph_finish``: the capture runs nothing.  The pointer tables are uploaded after
-        the capture (``graph_prepare``): the gradients they point to are the graph's own, at fixed addresses from replay to
-        replay."""
-        def reach(p, st):
-            if len(st) == 0:       # zeros_like inside the capture would reset the moments on every replay
-                raise RuntimeError("FusedAdam: a parameter received its first gradient while a graph was being captured "
-                                   "(capture after the set of parameters with a gradient has settled: raise graph_warmup)")
-            return st["step"] + 1
-
-        plan = self.__dict__.setdefault("_graph_plan", [])
-        max_norm = self._clip_norm()
-        recorded = []
-        for gi, group, t, plist, wd, coupled in self._launch_groups(reach):
-            table = self._table(plist)
-            # (reserved before the capture: a buffer allocated inside it comes from the graph's pool, whose blocks earlier
-            #  nodes of the same replay may use as scratch -- they would overwrite what graph_prepare uploaded)
-            slots = self.__dict__.get("_graph_reserve", {}).get(gi)
-            if not slots:
-                raise RuntimeError("FusedAdam: no table reserved for this group (call graph_reserve() before the capture)")
-            table_dev, hyper = slots.pop(0)
-            hyper.t0 = hyper.t = t
-            hyper.key = None
-            recorded.append((gi, group, plist, wd, coupled, table, table_dev, hyper))
-        if not recorded:
-            return
-        lib = ops._lib_for(recorded[0][2][0])
-        scale = None
-        if max_norm is not None:       # (buffers reserved before the capture, like the tables: never allocated inside it)
-            scale = self._clip_scale(lib, [(table, table_dev) for *_, table, table_dev, _ in recorded], max_norm, reserve=False)
-        for gi, group, plist, wd, coupled, table, table_dev, hyper in recorded:
-            b1, b2 = group["betas"]
-            dev_args = (*table.args(table_dev), ctypes.c_void_p(hyper.table.data_ptr()), ctypes.c_void_p(hyper.index.data_ptr()),
-                        hyper.rows, b1, b2, group["eps"])
-            if scale is not None:
-                L.check(lib.dei2i_adam_step_clip_dev(*dev_args, scale, int(coupled), wd, ops._stream()), "adam_step_clip_dev")
-            else:
-                L.check(lib.dei2i_adam_step_l2_dev(*dev_args, self.grad_scale, wd, ops._stream()) if coupled else
-                        lib.dei2i_adam_step_dev(*dev_args, self.grad_scale, ops._stream()), "adam_step_dev")
-            L.check(lib.dei2i_index_advance(ctypes.c_void_p(hyper.index.data_ptr()), ops._stream()), "index_advance")
-            plan.append(_CapturedGroup(gi, plist, table, table_dev, hyper, 0.0 if coupled else wd, (max_norm, self.grad_scale),
-                                       self.__dict__.get("_clip_bufs") if scale is not None else None))
-            ops.mark_written(*plist)      # later passes of the capture must repack
-
     def graph_reserve(self):
         """Before a capture: device tables for every launch group the captured step can make (one per distinct step count
         among the parameters, plus one), and with ``max_grad_norm`` the clipping buffers, outside the graph's memory pool."""
@@ -269,11 +292,6 @@ class FusedAdam(torch.optim.Optimizer):
                             _HyperTable(params[0].device, 0)) for _ in range(len(steps) + 1)]
         self._graph_reserve = reserve
 
-    def graph_take_plan(self):
-        """-> the groups recorded since the last call (the graph just captured owns them); unused reserved tables are dropped"""
-        self.__dict__.pop("_graph_reserve", None)
-        return self.__dict__.pop("_graph_plan", [])
-
     def graph_prepare(self, plan):
         """Before a replay of a graph holding ``plan``: the rows of every group cover this step with the current lr
         (a stream-ordered upload only when they do not)."""
@@ -282,18 +300,16 @@ class FusedAdam(torch.optim.Optimizer):
                 raise RuntimeError(f"FusedAdam: (max_grad_norm, grad_scale) = {(self._clip_norm(), self.grad_scale)} now, but the graph "
                                    f"was captured with {g.frozen}, which are arguments frozen into it (call the trainer's "
                                    "release_graphs(), or capture again)")
-            if not g.uploaded:
-                g.table.upload(into=g.table_dev)      # (a reserved slot: rows for the whole group)
-                g.uploaded = True
+            g.upload()
             group = self.param_groups[g.group]
             b1, b2 = group["betas"]
             # (the step from the state, not the mirror: an eager call between two replays has advanced it)
-            g.hyper.ensure(self.state[g.params[0]]["step"] + 1, float(group["lr"]), b1, b2, g.wd)
+            g.rows.ensure(self.state[g.params[0]]["step"] + 1, float(group["lr"]), b1, b2, g.wd)
 
     def graph_finish(self, plan):
         """After a replay: the host state the eager step would have left (``p.grad`` is the trainer's)."""
         for g in plan:
-            g.hyper.advance()
+            g.rows.advance()
             for p in g.params:
                 self.state[p]["step"] += 1
             ops.mark_written(*g.params)
@@ -319,8 +335,13 @@ def adam_hyper_rows(lr, b1, b2, decoupled_decay, t0, count):
 class _RowTable:
     """``rows`` rows of ``width`` floats + the int32 row index the ``_dev`` kernels read, in one device buffer (one upload).
     ``t0``: the step of row 0; ``t``: the step the next replay runs (host mirror of t0 + index); ``key``: what the rows were
-    computed from.  A subclass's ``_rows(t, key)`` gives the (rows, width) float32 rows from step ``t`` on."""
+    computed from.  A subclass's ``_rows(t, key)`` gives the (rows, width) float32 rows from step ``t`` on.  ``STRIDE``: the
+    distance between the steps of two rows, 1 or (an index into the key) ``key[STRIDE]``."""
     WIDTH = 1
+    STRIDE = None
+
+    def _stride(self, key):
+        return 1 if self.STRIDE is None else key[self.STRIDE]
 
     def __init__(self, device, t, rows):
         self.rows = rows
@@ -344,11 +365,11 @@ class _RowTable:
 
     def ensure(self, t, *key):
         """The device index is at step ``t``'s row, computed from ``key`` (else: rewrite from ``t`` on)."""
-        if self.key != key or t != self.t or t - self.t0 >= self.rows - 1:
+        if self.key != key or t != self.t or (t - self.t0) // self._stride(key) >= self.rows - 1:
             self.refresh(t, *key)
 
     def advance(self):
-        self.t += 1
+        self.t += self._stride(self.key)
 
 
 class _HyperTable(_RowTable):
@@ -361,20 +382,6 @@ class _HyperTable(_RowTable):
     def _rows(self, t, key):
         lr, b1, b2, wd = key
         return adam_hyper_rows(lr, b1, b2, wd, t, self.rows)
-
-
-class _CapturedGroup:
-    """One recorded launch group.  ``table``: its pointer table on the host (holding the graph's own gradients), which
-    ``graph_prepare`` uploads into ``table_dev`` once, after the capture and before the first replay.  The raw-write stamps
-    (``ops.mark_written``) move at capture, so the rest of the capture repacks, and again after every replay, so eager code
-    repacks.  ``frozen``: the (max_grad_norm or None, grad_scale) recorded as launch arguments; ``clip``: the clipping buffers the
-    graph reads and writes by address, kept alive with it."""
-    __slots__ = ("group", "params", "table", "table_dev", "hyper", "wd", "uploaded", "frozen", "clip")
-
-    def __init__(self, group, params, table, table_dev, hyper, wd, frozen, clip=None):
-        self.group, self.params, self.table, self.table_dev, self.hyper, self.wd = group, params, table, table_dev, hyper, wd
-        self.frozen, self.clip = frozen, clip
-        self.uploaded = False
 
 
 def ema_lerp_(ema_params, params, weight):
@@ -470,6 +477,7 @@ def ema_weight_rows(iters, num_critics, start_iter, beta, count):
 class _WeightRows(_RowTable):
     """Device rows of ``ema_weight_rows``: a "step" is the iteration a G update ends at; the key is (num_critics, start_iter, beta),
     whose first entry is also the distance between two steps."""
+    STRIDE = 0
 
     def __init__(self, device, rows=EMA_ROWS):
         super().__init__(device, 0, rows)
@@ -478,24 +486,8 @@ class _WeightRows(_RowTable):
         num_critics, start_iter, beta = key
         return ema_weight_rows(t - num_critics, num_critics, start_iter, beta, self.rows)
 
-    def ensure(self, t, *key):
-        if self.key != key or t != self.t or (t - self.t0) // key[0] >= self.rows - 1:
-            self.refresh(t, *key)
 
-    def advance(self):
-        self.t += self.key[0]
-
-
-class _CapturedEma:
-    """The recorded launches of one EmaGroup in one graph: the host pointer tables, which ``graph_prepare`` uploads into the
-    reserved device tables once, after the capture and before the first replay, and the device weight rows."""
-    __slots__ = ("tables", "tables_dev", "weights", "uploaded")
-
-    def __init__(self, tables, tables_dev, weights):
-        self.tables, self.tables_dev, self.weights, self.uploaded = tables, tables_dev, weights, False
-
-
-class EmaGroup:
+class EmaGroup(_GraphCapture):
     """The EMA copies of a set of trained tensors and the buffers that go with them, updated once per G update by the defectGAN and
     MAE trainers.  ``lerp``: pairs (e, p) of fp32 tensors, ``e = lerp(p, e, weight)`` in one launch of csrc/adam.hip's EMA kernel;
     ``copy``: pairs (e, b) of buffers, ``e = b``: the contiguous fp32 ones in one more launch of that kernel with weight 0, which is
@@ -538,50 +530,46 @@ class EmaGroup:
     # ---- graph capture ------------------------------------------------------------------------------------------------
     def graph_reserve(self):
         """Before a capture: a device pointer table per launch and the weight rows, outside the graph's memory pool."""
-        self._graph_reserve = ([torch.empty((len(pairs), 5), dtype=torch.int64, device=self.device) for pairs, _ in self._launches()],
-                               _WeightRows(self.device))
+        tables = [torch.empty((len(pairs), 5), dtype=torch.int64, device=self.device) for pairs, _ in self._launches()]
+        self._graph_reserve = {"table": tables, "weights": [_WeightRows(self.device)]}
 
     def _update_captured(self):
-        reserve = self.__dict__.pop("_graph_reserve", None)
-        if reserve is None:
-            raise RuntimeError("EmaGroup: no table reserved (call graph_reserve() before the capture; one update per capture)")
-        tables_dev, weights = reserve
+        error = "EmaGroup: no table reserved (call graph_reserve() before the capture; one update per capture)"
         lib = ops._lib_for(self.lerp[0][0])
-        tables = []
-        for (pairs, lerps), table_dev in zip(self._launches(), tables_dev):
-            table = _PointerTable("EmaGroup", [(e, p, None, None) for e, p in pairs])
-            tables.append(table)
+        for pairs, lerps in self._launches():
+            table, table_dev = _PointerTable("EmaGroup", [(e, p, None, None) for e, p in pairs]), self._take_reserved("table", error)
+            weights = self._take_reserved("weights", error) if lerps else None
             if lerps:
-                L.check(lib.dei2i_ema_lerp_dev(*table.args(table_dev), ctypes.c_void_p(weights.table.data_ptr()),
-                                               ctypes.c_void_p(weights.index.data_ptr()), weights.rows, ops._stream()), "ema_lerp_dev")
-                L.check(lib.dei2i_index_advance(ctypes.c_void_p(weights.index.data_ptr()), ops._stream()), "index_advance")
+                L.check(lib.dei2i_ema_lerp_dev(*table.args(table_dev), _dev_ptr(weights.table), _dev_ptr(weights.index), weights.rows,
+                                               ops._stream()), "ema_lerp_dev")
+                L.check(lib.dei2i_index_advance(_dev_ptr(weights.index), ops._stream()), "index_advance")
             else:
                 L.check(lib.dei2i_ema_lerp(*table.args(table_dev), 0.0, ops._stream()), "ema_lerp")
+            self._recorded(_CapturedLaunch(table, table_dev, weights))
         for e, b in self.plain:
             e.copy_(b)
-        self._graph_plan = _CapturedEma(tables, tables_dev, weights)
 
     def graph_take_plan(self):
         """-> the update recorded since the last call (None: none); an unused reservation is dropped"""
-        self.__dict__.pop("_graph_reserve", None)
-        return self.__dict__.pop("_graph_plan", None)
+        return super().graph_take_plan() or None
 
     def graph_prepare(self, plan, iters, num_critics, start_iter, beta):
         """Before a replay, after ``iters`` iterations, of a graph holding ``plan``: the pointer tables are on the device (uploaded
         once) and the device index is at the row of the G update this replay makes, the one that ends iteration ``iters + 1``."""
-        if not plan.uploaded:
-            for table, table_dev in zip(plan.tables, plan.tables_dev):
-                table.upload(into=table_dev)
-            plan.uploaded = True
-        plan.weights.ensure(iters + 1, int(num_critics), int(start_iter), float(beta))
+        for launch in plan:
+            launch.upload()
+            if launch.rows is not None:
+                launch.rows.ensure(iters + 1, int(num_critics), int(start_iter), float(beta))
 
     def graph_finish(self, plan):
         """After a replay: the host mirror of the index, and the stamps the eager update would have moved."""
-        plan.weights.advance()
+        for launch in plan:
+            if launch.rows is not None:
+                launch.rows.advance()
         ops.mark_written(*[e for e, _ in self.lerp + self.copy])
 
 
-class _FusedPlain(torch.optim.Optimizer):
+class _FusedPlain(_FusedOptimizer):
     """torch.optim.SGD / torch.optim.RMSprop as trainers/base_trainer.py:71-74 constructs them (``optim_cls(params, lr=...)``: no
     momentum, no weight decay; RMSprop alpha 0.99, eps 1e-8, not centered) on csrc/adam.hip's second kernel: one launch per step,
     parameters whose ``grad`` is None skipped (no state), ``grad_scale`` like FusedAdam (the data-parallel 1/world)."""
@@ -595,17 +583,14 @@ class _FusedPlain(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+        loss = self._closure_loss(closure)
         for group in self.param_groups:
             plist = [p for p in group["params"] if p.grad is not None]
             if not plist:
                 continue
             lib = ops._lib_for(plist[0])
             table = _PointerTable(type(self).__name__, [(p, p.grad, self._square_avg(p), None) for p in plist])
-            table_dev = table.cached(self.__dict__.setdefault("_table_cache", {}))
+            table_dev = table.cached(self._tables())
             L.check(lib.dei2i_sgd_rmsprop_step(*table.args(table_dev), self.KIND, float(group["lr"]), float(group.get("alpha", 0.0)),
                                                float(group.get("eps", 0.0)), self.grad_scale, ops._stream()), "sgd_rmsprop_step")
             ops.mark_written(*plist)

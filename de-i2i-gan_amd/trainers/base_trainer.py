@@ -54,6 +54,7 @@ class BaseTrainer:
         self.graph_warmup = int(getattr(opt, "graph_warmup", 3))
         self._graphs = None
         self._graph_records = None        # (keys, stacked losses) of the step being captured
+        self.reducer = None               # set by parallel.attach_ddp(): gradient all-reduce across ranks
 
     def _restore_or_init_weights(self, opt):
         """-> the checkpoint epoch the weights were restored from (None: initialised)"""
@@ -84,7 +85,8 @@ class BaseTrainer:
         opt.first_epoch = self.first_epoch
 
     def _init_lr(self, opt):
-        self.lr = opt.lr[0]
+        assert len(opt.lr) in (1, 2), f"length of lr must be 1 or 2, not {len(opt.lr)}"
+        self.lr = {"D": opt.lr[0], "G": opt.lr[1]} if len(opt.lr) == 2 else opt.lr[0]
 
     def _lr_of(self, network_name):
         return self.lr[network_name] if isinstance(self.lr, dict) else self.lr
@@ -119,7 +121,33 @@ class BaseTrainer:
             for scheduler in self.schedulers.values():
                 scheduler.step()
 
+    # ---- the step both stages share: one D update, then (every ``num_critics`` iterations) one G update -------------------
+    def _step(self, *inputs):
+        """``opt.graph_step``: replayed from a captured graph after ``opt.graph_warmup`` eager calls (trainers/graph_step.py)"""
+        if self.graph_step:
+            if self._graphs is None:
+                from .graph_step import GraphStep
+                self._graphs = GraphStep(self)
+            self._graphs.step(*inputs)
+        else:
+            self._eager_step(*inputs)
+
+    def _eager_step(self, *inputs):
+        self.iters += 1
+        self._train_discriminator_once(*inputs)
+        if self.iters % self.opt.num_critics == 0:
+            self._train_generator_once(*inputs)
+
     # ---- loss bookkeeping (self.losses[kind][name] lists, like the reference) ----------------------------------
+    def _set_loss_types(self, own, last=()):
+        """``loss_types``: the stage's ``own`` kinds, "grad_norm" with ``opt.max_grad_norm`` (the norm before clipping, per update),
+        then the stage's ``last`` ones; and their empty lists."""
+        self.loss_types = list(own) + ["grad_norm"] * (self.max_grad_norm is not None) + list(last)
+        self._init_losses()
+
+    def _init_losses(self):
+        self.losses = {loss_type: defaultdict(list) for loss_type in self.loss_types}
+
     def _record(self, keys, tensors):
         stacked = torch.stack([t.detach() for t in tensors])
         if self._graph_records is not None:          # being captured: the replays hand the losses over (graph_step.py)
@@ -164,3 +192,4 @@ class BaseTrainer:
     def _update_per_epoch(self, epoch=None):
         for scheduler in self.schedulers.values():
             scheduler.step()
+        self.model.update_per_epoch(epoch)

@@ -6,10 +6,7 @@ epoch).
 
 TensorBoard logging, progress bars, image grids and FID/IS/LPIPS validation are host-side tooling outside the hot path
  and are not part of this package."""
-from collections import defaultdict
-
 import numpy as np
-import torch
 
 from .base_trainer import BaseTrainer
 
@@ -22,25 +19,11 @@ class DefectGanTrainer(BaseTrainer):
         assert len(opt.loss_weight) == 5, f"length of loss weights must be 5, not {len(opt.loss_weight)}"
         self.loss_weights = {"clf_d": opt.loss_weight[0], "clf_g": opt.loss_weight[1], "rec": opt.loss_weight[2],
                              "sd_cyc": opt.loss_weight[3], "sd_con": opt.loss_weight[4]}
-        self.loss_types = ["gan", "clf", "aux"]
         self.distill = opt.style_norm_block_type == "sean" and getattr(opt, "style_distill", False)      # defectgan_trainer.py:29-30
-        if self.distill:
-            self.loss_types.append("distill")
-        if self.max_grad_norm is not None:                # opt.max_grad_norm: the norm before clipping, per update
-            self.loss_types.append("grad_norm")
-        if self.model.ada is not None:                    # opt.ada_target: p and r_t after the controller's launch, per D update
-            self.loss_types.append("ada")
-        self._init_losses()
+        # (opt.ada_target: p and r_t after the controller's launch, per D update)
+        self._set_loss_types(["gan", "clf", "aux"] + ["distill"] * bool(self.distill), ["ada"] * (self.model.ada is not None))
         if opt.phase == "val":
             raise NotImplementedError("phase='val' builds FID/LPIPS metric networks (downloaded weights): out of scope")
-        self.reducer = None          # set by parallel.attach_ddp(): gradient all-reduce across ranks
-
-    def _init_lr(self, opt):
-        assert len(opt.lr) in (1, 2), f"length of lr must be 1 or 2, not {len(opt.lr)}"
-        self.lr = {"D": opt.lr[0], "G": opt.lr[1]} if len(opt.lr) == 2 else opt.lr[0]
-
-    def _init_losses(self):
-        self.losses = {loss_type: defaultdict(list) for loss_type in self.loss_types}
 
     # ---- the step ---------------------------------------------------------------------------------------------
     def _train_generator_once(self, bg_data, df_labels, df_data):
@@ -91,19 +74,7 @@ class DefectGanTrainer(BaseTrainer):
     def step(self, bg_data, df_labels, df_data):
         """One iteration of the reference's hot loop (defectgan_trainer.py:96-109).  ``opt.graph_step``: replayed from a
         captured graph after ``opt.graph_warmup`` eager calls (trainers/graph_step.py)."""
-        if self.graph_step:
-            if self._graphs is None:
-                from .graph_step import GraphStep
-                self._graphs = GraphStep(self)
-            self._graphs.step(bg_data, df_labels, df_data)
-            return
-        self._eager_step(bg_data, df_labels, df_data)
-
-    def _eager_step(self, bg_data, df_labels, df_data):
-        self.iters += 1
-        self._train_discriminator_once(bg_data, df_labels, df_data)
-        if self.iters % self.opt.num_critics == 0:
-            self._train_generator_once(bg_data, df_labels, df_data)
+        self._step(bg_data, df_labels, df_data)
 
     # ---- the epoch loop with the reference's checkpoint / resume rules (defectgan_trainer.py:75-120) -------------------
     def train(self, train_loaders, val_loaders=None):
@@ -131,7 +102,3 @@ class DefectGanTrainer(BaseTrainer):
         self.model.save("latest")
         self.iter_record_path.parent.mkdir(parents=True, exist_ok=True)
         np.savetxt(self.iter_record_path, (epoch, self.iters), fmt="%i", delimiter=",")
-
-    def _update_per_epoch(self, epoch=None):
-        super()._update_per_epoch(epoch)
-        self.model.update_per_epoch(epoch)

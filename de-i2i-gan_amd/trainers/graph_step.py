@@ -19,6 +19,8 @@ call counter lives in device memory and advances inside the draw launch, so ever
 drawn); with host draws, which a capture would freeze into every replay, it is refused.  The MAE stage's patch masks follow the
 same rule (``opt.mask_rng = "device"``: ops.mask_draw / ops.mask_fill; host-drawn masks are refused), and so does its
 ``opt.grad_scaler``, whose overflow check reads the device once per update."""
+import contextlib
+
 import torch
 
 from .. import ops
@@ -103,7 +105,8 @@ class GraphStep:
         sig = tuple((tuple(t.shape), t.dtype, t.device) for t in inputs)
         if self.calls < int(getattr(tr.opt, "graph_warmup", 3)):
             self.calls += 1
-            self._eager_on_capture_stream(inputs)
+            with self._on_capture_stream():
+                tr._eager_step(*inputs)
             return
         if self.sig is not None and sig != self.sig:
             tr._eager_step(*inputs)      # (the last, smaller batch of an epoch): the graphs stay
@@ -119,18 +122,12 @@ class GraphStep:
         if cap is None:
             cap = self.graphs[with_g] = self._capture(with_g)
             self.stamp = self._stamp()
-        # the table uploads and the replay go on the capture stream, one stream, after the caller's stream (the inputs) and
-        # before its later work
-        st = capture_stream(tr.opt.device)
-        cur = torch.cuda.current_stream(st.device)
-        st.wait_stream(cur)
-        with torch.cuda.stream(st):
+        with self._on_capture_stream():      # the table uploads and the replay, on one stream
             for name, plan in cap.plans.items():
                 tr.optimizers[name].graph_prepare(plan)
             if cap.ema is not None:
                 tr.model.ema_graph_prepare(cap.ema, tr.iters)
             cap.graph.replay()
-        cur.wait_stream(st)
         tr.iters += 1
         for name, plan in cap.plans.items():
             tr.optimizers[name].graph_finish(plan)
@@ -144,12 +141,14 @@ class GraphStep:
             for (kind, name), v in zip(cap.keys, cap.losses.tolist()):      # the one read of the step
                 tr.losses[kind][name].append(v)
 
-    def _eager_on_capture_stream(self, inputs):
+    @contextlib.contextmanager
+    def _on_capture_stream(self):
+        """Work inside goes on the capture stream, after the caller's stream (the inputs) and before its later work."""
         st = capture_stream(self.tr.opt.device)
         cur = torch.cuda.current_stream(st.device)
         st.wait_stream(cur)
         with torch.cuda.stream(st):
-            self.tr._eager_step(*inputs)
+            yield
         cur.wait_stream(st)
 
     def _trained_modules(self):

@@ -16,8 +16,6 @@ more under the scaler: ``GradScaler.step`` has un-scaled the gradients before it
 clipped and logged as ``losses["grad_norm"]`` is that of the un-scaled gradients (an update the scaler skips logs the last norm).
 TensorBoard logging, image grids and FID validation are host-side tooling outside the step and are not part of this
 package."""
-from collections import defaultdict
-
 import torch
 
 from .base_trainer import BaseTrainer
@@ -30,13 +28,8 @@ class MAETrainer(BaseTrainer):
         super().__init__(opt)
         assert len(opt.loss_weight) == 3, f"length of loss weights must be 3, not {len(opt.loss_weight)}"
         self.loss_weights = {"rec": opt.loss_weight[0], "clf_D": opt.loss_weight[1], "clf_G": opt.loss_weight[2]}
-        self.loss_types = ["rec", "gan", "clf"]
         self.distill = opt.style_norm_block_type == "sean" and getattr(opt, "style_distill", False)      # mae_trainer.py:20-21
-        if self.distill:
-            self.loss_types.append("distill")
-        if self.max_grad_norm is not None:                # opt.max_grad_norm: the norm before clipping, per update
-            self.loss_types.append("grad_norm")
-        self._init_losses()
+        self._set_loss_types(["rec", "gan", "clf"] + ["distill"] * bool(self.distill))
         self.data_types = data_types
         if opt.phase == "val":
             raise NotImplementedError("phase='val' builds FID metric networks (downloaded weights): out of scope")
@@ -44,14 +37,6 @@ class MAETrainer(BaseTrainer):
         self.optimizers["G"].add_param_group({"params": list(self.model.mask_token.parameters())})
         device_type = torch.device(opt.device).type
         self.scaler = torch.amp.GradScaler(device_type, enabled=device_type == "cuda" and bool(getattr(opt, "grad_scaler", False)))
-        self.reducer = None          # set by parallel.attach_ddp(): gradient all-reduce across ranks
-
-    def _init_lr(self, opt):
-        assert len(opt.lr) in (1, 2), f"length of lr must be 1 or 2, not {len(opt.lr)}"
-        self.lr = {"D": opt.lr[0], "G": opt.lr[1]} if len(opt.lr) == 2 else opt.lr[0]
-
-    def _init_losses(self):
-        self.losses = {loss_type: defaultdict(list) for loss_type in self.loss_types}
 
     def _scaled_update(self, loss, name):
         net = self.model.networks[name]
@@ -94,20 +79,4 @@ class MAETrainer(BaseTrainer):
         """One iteration of the reference's loop (mae_trainer.py:92-99).  ``opt.graph_step``: replayed from a captured graph after
         ``opt.graph_warmup`` eager calls (trainers/graph_step.py); that needs device-drawn masks (``opt.mask_rng = "device"``) and
         refuses ``opt.grad_scaler``."""
-        if self.graph_step:
-            if self._graphs is None:
-                from .graph_step import GraphStep
-                self._graphs = GraphStep(self)
-            self._graphs.step(data, labels)
-            return
-        self._eager_step(data, labels)
-
-    def _eager_step(self, data, labels):
-        self.iters += 1
-        self._train_discriminator_once(data, labels)
-        if self.iters % self.opt.num_critics == 0:
-            self._train_generator_once(data, labels)
-
-    def _update_per_epoch(self, epoch=None):
-        super()._update_per_epoch(epoch)
-        self.model.update_per_epoch(epoch)
+        self._step(data, labels)

@@ -1,6 +1,7 @@
 """dei2i_adam_step_dev / dei2i_adam_step_l2_dev (csrc/adam.hip): the hyper-parameters from a device table indexed by a device
 counter, bitwise equal to the argument forms over 20 steps with a changing lr, a table refresh in between (8-row tables),
-grad_scale != 1 and weight decay; and torch.optim.Adam within FusedAdam's tolerance."""
+grad_scale != 1 and weight decay; and torch.optim.Adam within FusedAdam's tolerance.  FusedAdam.step() captured and replayed
+equals eager steps bit for bit, also when one param group splits into two launch groups (with and without max_grad_norm)."""
 import ctypes
 
 import pytest
@@ -151,3 +152,73 @@ def test_captured_fused_adam_step_equals_eager(wd, decoupled):
             graph.replay()
             og.graph_finish(plan)
         check(t)
+
+
+SPLIT_NUMELS = [3, 8, 13, 2053]            # the scalar loop only, the float4 loop only, both, and three workgroups in x
+LAGGING = 2                                # the 13-element parameter: no gradient on the first step
+
+
+@pytest.mark.parametrize("max_grad_norm", [None, 0.5])
+@pytest.mark.parametrize("decoupled", [True, False])
+def test_captured_step_of_a_split_param_group_equals_eager(decoupled, max_grad_norm):
+    """One param group whose parameters stand at two step counts (one of them got its first gradient a step late) makes two
+    launch groups, each with its own reserved pointer table and hyper-parameter rows, and with ``max_grad_norm`` one norm over
+    both.  Captured and replayed 5 times with an lr change, against eager steps of a twin: bitwise equal parameters, moments,
+    ``state["step"]`` and ``grad_norm``.  (|0.5 g| is about 23 x the step's amplitude: on both sides of 0.5.)"""
+    from de_i2i_gan_amd.optim import FusedAdam
+    torch.manual_seed(7)
+    p0 = [torch.randn(n, device=DEV) for n in SPLIT_NUMELS]
+    pe = [torch.nn.Parameter(t.clone()) for t in p0]
+    pg = [torch.nn.Parameter(t.clone()) for t in p0]
+    kw = dict(lr=2e-4, betas=(0.5, 0.999), weight_decay=1e-2, decoupled=decoupled, grad_scale=0.5, max_grad_norm=max_grad_norm)
+    oe, og = FusedAdam(pe, **kw), FusedAdam(pg, **kw)
+    grads = [torch.empty_like(t) for t in p0]
+
+    def new_grads(t, skip=()):
+        gen = torch.Generator(device=DEV).manual_seed(200 + t)
+        for i, (a, b, g) in enumerate(zip(pe, pg, grads)):
+            g.copy_(torch.randn(g.shape, device=DEV, generator=gen) * (1.0 if t % 2 else 0.01))
+            a.grad = None if i in skip else g.clone()
+            b.grad = None if i in skip else g       # (the captured tables point at these buffers)
+
+    def check(t):
+        torch.cuda.synchronize()
+        if max_grad_norm is None:
+            assert oe.grad_norm is None and og.grad_norm is None
+        else:
+            assert torch.equal(oe.grad_norm, og.grad_norm), t
+        for a, b in zip(pe, pg):
+            assert torch.equal(a, b), t
+            sa, sb = oe.state[a], og.state[b]
+            assert sa["step"] == sb["step"], t
+            assert torch.equal(sa["exp_avg"], sb["exp_avg"]) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"]), t
+
+    for t in range(1, 3):                  # eager warm-up: every parameter has its state before the capture
+        new_grads(t, skip=(LAGGING,) if t == 1 else ())
+        oe.step()
+        og.step()
+    check(2)
+    assert [og.state[p]["step"] for p in pg] == [2, 2, 1, 2]
+    graph = torch.cuda.CUDAGraph()
+    og.graph_reserve()
+    with torch.cuda.graph(graph):
+        og.step()
+    plan = og.graph_take_plan()
+    assert len(plan) == 2                                                # two launch groups of one param group
+    assert [og.state[p]["step"] for p in pg] == [2, 2, 1, 2]             # the capture ran nothing
+    seen = []
+    for t in range(3, 8):
+        if t == 5:
+            for o in (oe, og):
+                o.param_groups[0]["lr"] = 5e-5
+        new_grads(t)
+        oe.step()
+        og.graph_prepare(plan)
+        graph.replay()
+        og.graph_finish(plan)
+        check(t)
+        if max_grad_norm is not None:
+            seen.append(float(og.grad_norm))
+    assert [og.state[p]["step"] for p in pg] == [7, 7, 6, 7]
+    if max_grad_norm is not None:
+        assert any(n > max_grad_norm for n in seen) and any(n < max_grad_norm for n in seen)
