@@ -3,6 +3,8 @@
 import torch.nn as nn
 from torch.nn import init
 
+from .. import ops
+
 # init_type -> filler of a Conv* / Linear* weight (the reference's choices, base_network.py:36-51)
 _WEIGHT_FILL = {
     "normal": lambda w, gain: init.normal_(w, 0.0, gain),
@@ -62,6 +64,9 @@ class BaseNetwork(nn.Module):
         for child in self.children():
             if hasattr(child, "init_weights"):
                 child.init_weights(init_type, gain)
+        # the fillers write through ``.data``, which moves no version counter: stamp the tree, or a network that ran a forward
+        # before it was initialised keeps convolving with the packed copies (and SPADE tables) of its old weights
+        ops.mark_written(*self.parameters(), *self.buffers())
 
     def train(self, mode: bool = True):
         """nn.Module.train, without its per-module recursion through ``__setattr__``: the trainers flip the generator between eval and

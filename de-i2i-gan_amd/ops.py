@@ -95,14 +95,27 @@ fuse_bwd = True
 # wraps it): the forward leaves attribute -> value here, the public wrapper clears the record before .apply and moves whatever
 # is present onto the output afterwards.  _dei2i_fp8: the e4m3 copy a normalisation kernel wrote beside its output;
 # _dei2i_stats: (partial records, records per image) of a producer (see _stats_of); _dei2i_bwd_hint: see _NormBwdHint.
+# _dei2i_stats and _dei2i_fp8 DESCRIBE the tensor's values, so they are bound to its autograd version counter at hand-over
+# (_dei2i_at_version): after an in-place write (y.mul_(2), y.add_(res)) the consumer ignores them and measures the tensor itself (_handed).
 _handover = {}
 
 
 def _attach(out):
-    for name, value in _handover.items():
-        setattr(out, name, value)
-    _handover.clear()
+    if _handover:
+        for name, value in _handover.items():
+            setattr(out, name, value)
+        out._dei2i_at_version = out._version
+        _handover.clear()
     return out
+
+
+def _handed(t, name):
+    """The value a producer left on ``t`` under ``name``, or None: nothing left, or ``t`` was written in place since (reading
+    ``_version`` is host-only, ~0.1 us)."""
+    value = getattr(t, name, None)
+    if value is not None and getattr(t, "_dei2i_at_version", None) != t._version:
+        return None
+    return value
 
 
 def _fp8_copy_wanted(prec, c: int) -> bool:
@@ -506,7 +519,7 @@ class PackedWeights:
 
 def _stats_of(t, n, hw, c):
     """The statistics records a producer kernel left for tensor ``t`` ((N, chunks, 2, C) fp32, chunks), or None."""
-    st = getattr(t, "_dei2i_stats", None)
+    st = _handed(t, "_dei2i_stats")
     if st is None:
         return None
     partial, chunks = st
@@ -903,7 +916,7 @@ class _Conv2d(torch.autograd.Function):
         stats_fused = bool(want_stats and fuse_norm and not use_fp8 and prec is BF16 and lib.dei2i_conv2d_fused_supported(byref(d), 0))
         if use_fp8:
             wq, dequant = cache.get_fp8(weight, sources, prec, geom, cins, couts)
-            xq = getattr(x, "_dei2i_fp8", None)      # written by the producing normalisation kernel in the same pass
+            xq = _handed(x, "_dei2i_fp8")            # written by the producing normalisation kernel in the same pass
             if xq is not None and xq.numel() == x.numel():
                 del x._dei2i_fp8                     # one consumer: release the copy after this launch
             else:

@@ -222,8 +222,9 @@ class GradReducer:
 
     def broadcast_parameters(self, net: torch.nn.Module, src: int = 0) -> None:
         """Rank ``src``'s parameters and buffers to every rank, one flat message per dtype (torch DDP does this when it
-        wraps a module).  Parameters are written through ``.data`` and stamped so that packed weight copies refresh."""
-        if self.world <= 1:
+        wraps a module).  Parameters are written through ``.data`` and stamped so that packed weight copies refresh.  Like every
+        other collective of the reducer it runs on a one-rank group too when ``force_collectives`` asks for it (tests)."""
+        if not self.active:
             return
         with torch.no_grad():
             tensors = [p.data for p in net.parameters()] + [b for b in net.buffers()]

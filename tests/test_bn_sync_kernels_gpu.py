@@ -205,7 +205,7 @@ def test_resblock_shaped_conv_bn_conv_with_epilogue_records(ops):
         y1 = ops.conv2d(x[sl], w1, None, caches[0], geom, "none", stats=True)
         records = y1._dei2i_stats                                          # the moments records of the conv epilogue ...
         y1 = y1.detach().requires_grad_(True)
-        y1._dei2i_stats = records                                          # ... travel with the leaf the BatchNorm is given
+        y1._dei2i_stats, y1._dei2i_at_version = records, y1._version       # ... travel with the leaf the BatchNorm is given
         with ops.bn_sync(exchange, rank=s, world=W):
             z = ops.batchnorm_act(y1, wg, bg, rm, rv, True, "leaky_relu")
             y2 = ops.conv2d(z, w2, None, caches[1], geom, "none")
