@@ -127,6 +127,8 @@ SIGNATURES = {
     "dei2i_grad_clip_finalize": (c_int, [_P, c_int, c_float, c_float, _P, _P]),
     "dei2i_adam_step_clip": (c_int, [_P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, _P, c_int, c_float, _P]),
     "dei2i_adam_step_clip_dev": (c_int, [_P, c_int, c_int64, _P, _P, c_int, c_float, c_float, c_float, _P, c_int, c_float, _P]),
+    "dei2i_state_digest_blocks": (c_int, [c_int64]),
+    "dei2i_state_digest": (c_int, [_P, c_int, c_int64, c_int64, _P, c_int, _P, _P]),
     "dei2i_index_advance": (c_int, [_P, _P]),
     "dei2i_ema_lerp": (c_int, [_P, c_int, c_int64, c_float, _P]),
     "dei2i_ema_lerp_dev": (c_int, [_P, c_int, c_int64, _P, _P, c_int, _P]),

@@ -126,6 +126,64 @@ __global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const float* __
   }
 }
 
+// ---- state digest: every 32-bit word of a list of tensors reduced to one 64-bit word, in integers mod 2^64 ----
+//   digest = sum_k sum_i splitmix64(splitmix64((k << 32) | i) + w[k][i])      (k: the tensor's place in the list, i: the word's in it)
+// A sum of integers: any order of the additions gives the same bits, so the grid, the two loops and the tree below are free.
+DEI2I_D uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// The sum of 256 threads' words through LDS; the result is valid in thread 0.
+DEI2I_D uint64_t block_sum_u64(uint64_t v, uint64_t* tree) {
+  tree[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) tree[threadIdx.x] += tree[threadIdx.x + o];
+    __syncthreads();
+  }
+  return tree[0];
+}
+
+// Workgroup (x, y) hashes its grid-stride share of row y's rec.n words at rec.p (only these two fields are read): 16 bytes a lane
+// where the row is 16-byte aligned, word by word otherwise and for the tail.  Like grad_sumsq_kernel every workgroup stores its
+// partial (0 when it had no word): nothing is cleared beforehand, nothing is atomic.
+__global__ __launch_bounds__(256) void state_digest_kernel(const dei2i_adam_rec* __restrict__ table, uint32_t row0,
+                                                           uint64_t* __restrict__ partial) {
+  __shared__ uint64_t tree[256];
+  const dei2i_adam_rec rec = table[blockIdx.y];
+  const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(rec.p);
+  const uint64_t hi = (uint64_t)(row0 + blockIdx.y) << 32;
+  const int64_t n = rec.n;
+  const int64_t n4 = (reinterpret_cast<uintptr_t>(w) & 15) == 0 ? n / 4 : 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  uint64_t acc = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const uint4 v = reinterpret_cast<const uint4*>(w)[i];
+    const uint64_t at = hi | (uint64_t)(4 * i);
+    acc += splitmix64(splitmix64(at) + v.x);
+    acc += splitmix64(splitmix64(at + 1) + v.y);
+    acc += splitmix64(splitmix64(at + 2) + v.z);
+    acc += splitmix64(splitmix64(at + 3) + v.w);
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    acc += splitmix64(splitmix64(hi | (uint64_t)i) + w[i]);
+  acc = block_sum_u64(acc, tree);
+  if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
+}
+
+// One workgroup: out[0] = (accumulate ? out[0] : 0) + the sum of the n partials.
+__global__ __launch_bounds__(256) void state_digest_finalize_kernel(const uint64_t* __restrict__ partial, int n, int accumulate,
+                                                                    uint64_t* __restrict__ out) {
+  __shared__ uint64_t tree[256];
+  uint64_t s = 0;
+  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
+  s = block_sum_u64(s, tree);
+  if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0) + s;
+}
+
 // torch.optim.SGD / torch.optim.RMSprop with the defaults the reference constructs them with (trainers/base_trainer.py:71-74: only
 // lr is passed -- no momentum, no weight decay, RMSprop alpha 0.99, eps 1e-8, not centered), same pointer table (RMSprop's
 // square average lives in rec.m; rec.v is not touched):
@@ -264,6 +322,21 @@ extern "C" int dei2i_grad_clip_finalize(const float* partial_dev, int n_partials
   if (!partial_dev || n_partials <= 0 || !(max_norm > 0.f) || !out_dev) return DEI2I_ERR_BAD_ARG;
   hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, partial_dev, n_partials, grad_scale, max_norm,
                      out_dev);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dei2i_state_digest_blocks(int64_t max_n) { return (int)table_grid(max_n, 4, 512, 1).x; }
+
+extern "C" int dei2i_state_digest(const dei2i_adam_rec* table_dev, int count, int64_t max_n, int64_t row0, uint64_t* partial_dev,
+                                  int accumulate, uint64_t* out_dev, dei2i_stream s) {
+  // (a word's index and a row's place share one 64-bit key: 32 bits each)
+  if (!table_dev || count <= 0 || count > 65535 || max_n <= 0 || max_n > ((int64_t)1 << 32) || row0 < 0 || row0 + count > ((int64_t)1 << 32) ||
+      !partial_dev || !out_dev)
+    return DEI2I_ERR_BAD_ARG;
+  const dim3 grid = table_grid(max_n, 4, 512, count);
+  hipLaunchKernelGGL(state_digest_kernel, grid, dim3(256), 0, (hipStream_t)s, table_dev, (uint32_t)row0, partial_dev);
+  hipLaunchKernelGGL(state_digest_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, partial_dev, (int)(grid.x * grid.y),
+                     accumulate, out_dev);
   return (int)hipGetLastError();
 }
 

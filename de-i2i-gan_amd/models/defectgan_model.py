@@ -44,8 +44,8 @@ class DefectGanModel(BaseModel):
             self.mask_token = MaskToken(opt).to(opt.device, non_blocking=True)
         # opt.diff_aug_rng: "host" (or absent) draws DiffAugment's parameters from the global CPU RNG like the reference; "device"
         # draws them on the GPU from a counter-based generator (ops.DiffAugRng), which a captured step (opt.graph_step) can replay.
-        # The generator is no network: checkpoints do not carry it (the reference's carry no RNG state either) and it outlives
-        # checkpoint loads and released graphs.
+        # The generator is no network: the weight files do not carry it (the reference's carry no RNG state either) and it outlives
+        # checkpoint loads and released graphs; opt.train_state saves and restores (seed, calls) in the train-state file.
         self.diffaug_rng = None
         where = getattr(opt, "diff_aug_rng", None) or "host"
         if where == "device":
@@ -177,7 +177,7 @@ class DefectGanModel(BaseModel):
         with ops.diffaug_sharded(red.rank, red.world) if red is not None and red.world > 1 else contextlib.nullcontext():
             return ops.diff_augment(x, policy, rng=self.diffaug_rng, p=self.diffaug_p)
 
-    # ---- checkpoints: the controller's words travel as <epoch>_ada.pth (the RNG stays out, as before) ---------------------
+    # ---- checkpoints: the controller's words travel as <epoch>_ada.pth (the RNG: opt.train_state, train_state.py) ---------------------
     def _ada_path(self, run_name, epoch):
         return self.opt.ckpt_dir / run_name / f"{epoch}_ada.pth"
 

@@ -161,6 +161,22 @@ class DefectGanGenerator(BaseNetwork):
             mods = self.__dict__["_table_modules_list"] = [m for m in self.modules() if hasattr(m, "_gb_cache")]
         return mods
 
+    def table_marks(self):
+        """-> which table modules run in class mode, in module order -- what the first forward found out and ``prime_spade`` batches
+        its launches by -- or None before that forward.  Host state that decides launches: a resumed run restores it
+        (``set_table_marks``), so that its first step makes the launches of the run it continues, not those of a first step."""
+        if not self.__dict__.get("_marked_table_modules"):
+            return None
+        return [bool(m._ran_class_mode) for m in self._table_modules()]
+
+    def set_table_marks(self, marks):
+        mods = self._table_modules()
+        if len(marks) != len(mods):
+            raise RuntimeError(f"table marks for {len(marks)} modules, this generator has {len(mods)}")
+        for m, ran in zip(mods, marks):
+            m._ran_class_mode = bool(ran)
+        self.__dict__["_marked_table_modules"] = True
+
     def update_per_epoch(self, epoch):
         """generator.py:277-284"""
         super().update_per_epoch(epoch)

@@ -2102,6 +2102,55 @@ class AdaState:
         torch.cuda.synchronize(self.device)
 
 
+# ---- state digest (csrc/adam.hip: state_digest_kernel) -----------------------------------------------------------------------
+DIGEST_ROWS_PER_LAUNCH = 4096
+
+
+def state_digest(tensors, rows_per_launch=None):
+    """-> a one-element int64 device tensor: the bits of the 64-bit digest of a list of device tensors,
+    ``sum_k sum_i splitmix64(splitmix64((k << 32) | i) + w[k][i])`` mod 2^64 over the 32-bit words ``w[k][i]`` of tensor k's memory
+    (include/dei2i_hip.h).  It depends on every bit, on a word's place in its tensor and on a tensor's place in the list.  One
+    multi-tensor launch and a one-workgroup sum per ``rows_per_launch`` tensors (default ``DIGEST_ROWS_PER_LAUNCH``), queued on the
+    current stream: nothing waits for the device.  Tensors that are not contiguous are copied; one that is not on the GPU, whose
+    byte size is no multiple of 4 or that holds more than 2^32 words raises."""
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("state_digest needs at least one tensor")
+    per = DIGEST_ROWS_PER_LAUNCH if rows_per_launch is None else int(rows_per_launch)
+    if not 0 < per <= 65535:
+        raise ValueError(f"state_digest: |rows_per_launch {rows_per_launch}| is invalid (1..65535)")
+    rows, hold = [], []
+    device = tensors[0].device
+    for k, t in enumerate(tensors):
+        _require_gpu(t, "state_digest")
+        if t.device != device:
+            raise ValueError(f"state_digest: tensor {k} is on {t.device}, tensor 0 on {device}")
+        nbytes = t.numel() * t.element_size()
+        if nbytes % 4:
+            raise ValueError(f"state_digest: tensor {k} ({tuple(t.shape)}, {t.dtype}) holds {nbytes} bytes, not a whole number of "
+                             "32-bit words")
+        if nbytes // 4 > 2 ** 32:
+            raise ValueError(f"state_digest: tensor {k} holds more than 2^32 words")
+        t = t.detach()
+        t = t if t.is_contiguous() else t.contiguous()
+        if nbytes and t.data_ptr() % 4:
+            raise ValueError(f"state_digest: tensor {k} does not start at a 4-byte boundary")
+        hold.append(t)                                       # (a copy lives until its launch is queued)
+        rows.append((t.data_ptr() if nbytes else 0, 0, 0, 0, nbytes // 4))
+    lib = _lib_for(tensors[0])
+    host = torch.empty((len(rows), 5), dtype=torch.int64, pin_memory=True)
+    host.copy_(torch.tensor(rows, dtype=torch.int64))
+    table = host.to(device, non_blocking=True)
+    out = torch.empty(1, dtype=torch.int64, device=device)
+    for row0 in range(0, len(rows), per):
+        count = min(per, len(rows) - row0)
+        max_n = max(1, max(r[4] for r in rows[row0:row0 + count]))
+        partial = torch.empty(lib.dei2i_state_digest_blocks(max_n) * count, dtype=torch.int64, device=device)
+        L.check(lib.dei2i_state_digest(c_void_p(table.data_ptr() + 40 * row0), count, max_n, row0, _p(partial), int(row0 > 0),
+                                       _p(out), _stream()), "state_digest")
+    return out
+
+
 def diff_augment(x, policy="", rng=None, p=None):
     """DiffAugment(x, policy) of utils/diffaug.py on an NCHW fp32 GPU image batch, one or two launches per canonical-order policy
     run.  ``policy == ""`` returns ``x`` itself.  ``rng=None``: the same draws from the global CPU RNG as utils/diffaug.py, one

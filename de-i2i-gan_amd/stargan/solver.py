@@ -17,12 +17,14 @@ statistics and every loss term is a mean over samples, so the SUM of the ranks' 
 gradient; DiffAugment draws the global batch's parameters on every rank and applies the rank's rows (``ops.diffaug_sharded``); the
 reported losses are the global batch's (``global_means``)."""
 import contextlib
+from pathlib import Path
 from types import SimpleNamespace
 
 import torch
 import torch.distributed as dist
 
 from .. import ops
+from .. import train_state as TS
 from ..optim import FusedAdam, ema_lerp_
 
 _reducer = None         # the attached GradReducer while Solver.train_iteration runs data-parallel: the loss reads become global_means
@@ -138,6 +140,50 @@ class Solver:
             lr = args.f_lr if name == "mapping_network" else args.lr
             setattr(self.optims, name, FusedAdam(net.parameters(), lr=lr, betas=(args.beta1, args.beta2), weight_decay=args.weight_decay,
                                                  decoupled=False))
+
+    # ---- checkpoints: the reference CheckpointIO's three files (solver.py:58-63: nets, nets_ema, optims; each a dict from network
+    # name to state_dict) and a train-state file (train_state.py) that makes the resumed run the uninterrupted one ----------------
+    def _ckpt_paths(self, step):
+        root = Path(self.args.checkpoint_dir)
+        return {kind: root / f"{step:06d}_{kind}.ckpt" for kind in ("nets", "nets_ema", "optims", "train_state")}
+
+    def _ckpt_tensors(self):
+        """{file kind: its tensors, network by network in name order of the namespace} from the live objects"""
+        return {"nets": [v for net in vars(self.nets).values() for v in net.state_dict().values()],
+                "nets_ema": [v for net in vars(self.nets_ema).values() for v in net.state_dict().values()],
+                "optims": [t for o in vars(self.optims).values() for t in TS.optimizer_tensors(o)]}
+
+    def save(self, step):
+        """``{step:06d}_nets.ckpt``, ``_nets_ema.ckpt``, ``_optims.ckpt`` under ``args.checkpoint_dir``, then ``_train_state.ckpt``:
+        the decayed ``args.lambda_ds`` (and the initial one its decay step comes from), the CPU and device RNG states and the
+        digests of the three files' tensors, written last and atomically."""
+        paths = self._ckpt_paths(step)
+        paths["nets"].parent.mkdir(parents=True, exist_ok=True)
+        torch.save({name: net.state_dict() for name, net in vars(self.nets).items()}, paths["nets"])
+        torch.save({name: net.state_dict() for name, net in vars(self.nets_ema).items()}, paths["nets_ema"])
+        torch.save({name: o.state_dict() for name, o in vars(self.optims).items()}, paths["optims"])
+        TS.write({"step": int(step), "lambda_ds": float(self.args.lambda_ds), "initial_lambda_ds": float(self.initial_lambda_ds),
+                  "rng": TS.rng_state(self.device), "digests": TS.digests(self._ckpt_tensors())}, paths["train_state"])
+
+    def load(self, step):
+        """The inverse of ``save``.  The optimizers take their per-parameter state (moments, step counts) from the file and keep
+        their own hyper-parameters.  After the load the digests of the loaded tensors are compared with the stored ones: a file of
+        another save, or a damaged one, raises RuntimeError naming it."""
+        paths = self._ckpt_paths(step)
+        state = TS.read(paths["train_state"])
+        for kind, ns in (("nets", self.nets), ("nets_ema", self.nets_ema)):
+            stored = torch.load(paths[kind], map_location="cpu", weights_only=True)
+            for name, net in vars(ns).items():
+                net.load_state_dict(stored[name])
+                ops.mark_written(*net.parameters())
+        stored = torch.load(paths["optims"], map_location="cpu", weights_only=True)
+        for name, o in vars(self.optims).items():
+            groups = o.state_dict()["param_groups"]          # (this solver's lr, betas, weight decay)
+            o.load_state_dict({"state": stored[name]["state"], "param_groups": groups})
+        TS.check_digests(state["digests"], TS.digests(self._ckpt_tensors()), lambda kind: paths[kind])
+        self.args.lambda_ds = float(state["lambda_ds"])
+        self.initial_lambda_ds = float(state["initial_lambda_ds"])
+        TS.set_rng_state(state["rng"], self.device)
 
     def _reset_grad(self):
         for opt in vars(self.optims).values():

@@ -7,6 +7,8 @@ import numpy as np
 import torch
 from torch import optim
 
+from .. import ops
+from .. import train_state as TS
 from ..models import create_model
 from ..optim import FusedAdam, FusedRMSprop, FusedSGD, ada_options, clip_options, ema_options
 
@@ -30,6 +32,10 @@ class BaseTrainer:
     def __init__(self, opt):
         self.opt = opt
         ema_options(opt)                  # (an invalid opt.ema_beta is refused before anything is built)
+        # opt.train_state: every save also writes <epoch>_train_state.pth (optimizers, GradScaler, RNG states, the digests of the
+        # sibling files) and a resume restores it, so that a stopped and continued run is the uninterrupted run bit for bit
+        self.train_state = TS.train_state_option(opt)
+        self.train_state_restored = None  # True: resumed from a train-state file; False: from weights only; None: no resume asked
         # opt.max_grad_norm > 0: every FusedAdam clips its gradients to this global L2 norm inside the update (optim.FusedAdam)
         self.max_grad_norm = clip_options(opt)
         # opt.diff_aug_p / opt.ada_target: gated DiffAugment and its controller (the defectGAN stage; refused elsewhere, and an
@@ -188,6 +194,121 @@ class BaseTrainer:
         """Drop the captured graphs of ``graph_step`` (the next step() warms up and captures again)."""
         if self._graphs is not None:
             self._graphs.release()
+
+    # ---- checkpoints: weights as the reference writes them; with opt.train_state one more file, written last --------------------
+    def save_checkpoint(self, label, epoch, latest=False):
+        """The one place that writes a checkpoint: the weight files of ``label`` ("latest" or an epoch number; ``model.save``),
+        ``iter.txt`` = (epoch, iters) for ``latest`` (what ``--continue_training`` restores), and with ``opt.train_state``
+        ``<label>_train_state.pth`` last of all, whose digests tie the other files to it."""
+        self.model.save(label)
+        if latest:
+            self.iter_record_path.parent.mkdir(parents=True, exist_ok=True)
+            np.savetxt(self.iter_record_path, (epoch, self.iters), fmt="%i", delimiter=",")
+        if self.train_state:
+            TS.write(self._train_state(epoch), self._train_state_path(self.opt.name, label))
+
+    def save_latest(self, epoch):
+        """``latest_net_{G,D}.pth`` + ``iter.txt`` = (epoch, iters), what ``--continue_training`` restores
+        (defectgan_trainer.py:111-113, base_trainer.py:38-44).  The reference saves no optimizer state; with ``opt.train_state``
+        ``latest_train_state.pth`` carries it, with the RNG states and the digests of the other files (train_state.py)."""
+        self.save_checkpoint("latest", epoch, latest=True)
+
+    def _train_state_path(self, run_name, label):
+        return self.opt.ckpt_dir / run_name / f"{label}_train_state.pth"
+
+    def _extra_modules(self):
+        """{name: module}: what an optimizer trains outside ``model.networks`` and therefore outside the weight files -- the MAE
+        stage's mask token where it has a parameter.  The train-state file carries their ``state_dict``s."""
+        token = getattr(self.model, "mask_token", None)
+        if isinstance(token, torch.nn.Module) and next(token.parameters(), None) is not None:
+            return {"mask_token": token}
+        return {}
+
+    def _sibling_tensors(self):
+        """{name: tensors}: what each sibling file of a checkpoint holds, from the live modules -- ``net_<label>`` and
+        ``net_<label>_ema`` (``state_dict()`` values in key order), ``ada`` (p_rt, acc); file ``<epoch>_<name>.pth``"""
+        model = self.model
+        out = {f"net_{label}": list(net.state_dict().values()) for label, net in model.networks.items()}
+        out.update({f"net_{label}_ema": list(net.state_dict().values()) for label, net in model.ema.items()})
+        ada = getattr(model, "ada", None)
+        if ada is not None:
+            out["ada"] = [ada.p_rt, ada.acc]
+        return out
+
+    def state_digest(self):
+        """{name: 64-bit int}: one digest (ops.state_digest) per network, EMA copy and ADA word pair (the names of
+        ``_sibling_tensors``), per module of ``_extra_modules`` and per optimizer (``optim_<name>``: its moments in parameter
+        order).  Computed on the device, ONE host read in total: two runs, or two ranks, compare their whole state by it."""
+        groups = self._sibling_tensors()
+        groups.update({name: list(mod.state_dict().values()) for name, mod in self._extra_modules().items()})
+        groups.update({f"optim_{name}": TS.optimizer_tensors(o) for name, o in self.optimizers.items()})
+        return TS.digests(groups)
+
+    def _train_state(self, epoch):
+        model, device = self.model, self.opt.device
+        state = {"iters": int(self.iters), "epoch": int(epoch),
+                 "optimizers": {name: TS.optimizer_state(o) for name, o in self.optimizers.items()},
+                 "modules": {name: {k: v.detach().cpu() for k, v in mod.state_dict().items()}
+                             for name, mod in self._extra_modules().items()},
+                 # (host state that decides launches: which SPADE table modules the generator's first forward found running)
+                 "table_marks": {label: net.table_marks() for label, net in model.networks.items() if hasattr(net, "table_marks")},
+                 "rng": TS.rng_state(device), "digests": TS.digests(self._sibling_tensors())}
+        scaler = getattr(self, "scaler", None)
+        if scaler is not None and scaler.is_enabled():
+            state["grad_scaler"] = scaler.state_dict()
+        for key in ("diffaug_rng", "mask_rng"):
+            rng = getattr(model, key, None)
+            if rng is not None:
+                state[key] = list(rng.state())
+        return state
+
+    def resume_train_state(self):
+        """With ``opt.train_state``, under ``continue_training`` (label "latest") or ``load_model_name`` + ``which_epoch``, once the
+        weights are loaded and the optimizers (and the MAE stage's GradScaler) exist: check the loaded modules against the digests
+        of ``<label>_train_state.pth`` (RuntimeError naming the file that does not belong), then restore the optimizers' state,
+        the modules no weight file holds, the GradScaler and every RNG.  Learning rates are not stored (TS.optimizer_state), and
+        under ``load_model_name`` alone ``iters`` and the epoch stay the new run's.  Without the file the run resumes from the
+        weights alone, as it did before, and says so.  Captured graphs are released."""
+        opt = self.opt
+        if not self.train_state:
+            return
+        if opt.continue_training:
+            label = "latest"
+        elif opt.load_model_name is not None:
+            label = opt.which_epoch
+        else:
+            return
+        path = self._train_state_path(opt.load_model_name, label)
+        if not path.exists():
+            print(f"no train state at {path}: resuming from the weights only (optimizers and RNGs start anew)")
+            self.train_state_restored = False
+            return
+        state = TS.read(path)
+        if opt.continue_training and int(state["iters"]) != int(self.iters):
+            raise RuntimeError(f"{self.iter_record_path} does not belong to this checkpoint: it records iteration {int(self.iters)}, "
+                               f"{path.name} was saved at iteration {int(state['iters'])}")
+        TS.check_digests(state["digests"], TS.digests(self._sibling_tensors()), lambda name: path.with_name(f"{label}_{name}.pth"))
+        if sorted(state["optimizers"]) != sorted(self.optimizers):
+            raise RuntimeError(f"{path}: saved with optimizers {sorted(state['optimizers'])}, this trainer has {sorted(self.optimizers)}")
+        self.release_graphs()
+        for name, o in self.optimizers.items():
+            TS.load_optimizer_state(o, state["optimizers"][name], name)
+        for name, mod in self._extra_modules().items():
+            if name in state["modules"]:
+                mod.load_state_dict(state["modules"][name])
+                ops.mark_written(*mod.parameters())
+        for label, marks in state.get("table_marks", {}).items():
+            if marks is not None and label in self.model.networks:
+                self.model.networks[label].set_table_marks(marks)
+        scaler = getattr(self, "scaler", None)
+        if scaler is not None and scaler.is_enabled() and "grad_scaler" in state:
+            scaler.load_state_dict(state["grad_scaler"])
+        for key in ("diffaug_rng", "mask_rng"):
+            rng = getattr(self.model, key, None)
+            if rng is not None and key in state:
+                rng.set_state(tuple(state[key]))
+        TS.set_rng_state(state["rng"], opt.device)
+        self.train_state_restored = True
 
     def _update_per_epoch(self, epoch=None):
         for scheduler in self.schedulers.values():

@@ -6,8 +6,6 @@ epoch).
 
 TensorBoard logging, progress bars, image grids and FID/IS/LPIPS validation are host-side tooling outside the hot path
  and are not part of this package."""
-import numpy as np
-
 from .base_trainer import BaseTrainer
 
 
@@ -24,6 +22,7 @@ class DefectGanTrainer(BaseTrainer):
         self._set_loss_types(["gan", "clf", "aux"] + ["distill"] * bool(self.distill), ["ada"] * (self.model.ada is not None))
         if opt.phase == "val":
             raise NotImplementedError("phase='val' builds FID/LPIPS metric networks (downloaded weights): out of scope")
+        self.resume_train_state()         # (opt.train_state: the optimizers exist now)
 
     # ---- the step ---------------------------------------------------------------------------------------------
     def _train_generator_once(self, bg_data, df_labels, df_data):
@@ -85,7 +84,7 @@ class DefectGanTrainer(BaseTrainer):
             self._init_losses()
             self._train_epoch(train_loaders, epoch)
             if epoch % getattr(self.opt, "save_ckpt_freq", 10 ** 9) == 0:
-                self.model.save(epoch)
+                self.save_checkpoint(epoch, epoch)
             self._update_per_epoch(epoch)
 
     def _train_epoch(self, data_loaders, epoch):
@@ -95,10 +94,3 @@ class DefectGanTrainer(BaseTrainer):
             self.step(bg_data, df_labels, df_data)
             if self.iters % self.opt.save_latest_freq == 0:
                 self.save_latest(epoch)
-
-    def save_latest(self, epoch):
-        """``latest_net_{G,D}.pth`` + ``iter.txt`` = (epoch, iters), what ``--continue_training`` restores
-        (defectgan_trainer.py:111-113, base_trainer.py:38-44).  Optimizer state is not saved -- the reference does not."""
-        self.model.save("latest")
-        self.iter_record_path.parent.mkdir(parents=True, exist_ok=True)
-        np.savetxt(self.iter_record_path, (epoch, self.iters), fmt="%i", delimiter=",")

@@ -37,6 +37,7 @@ class MAETrainer(BaseTrainer):
         self.optimizers["G"].add_param_group({"params": list(self.model.mask_token.parameters())})
         device_type = torch.device(opt.device).type
         self.scaler = torch.amp.GradScaler(device_type, enabled=device_type == "cuda" and bool(getattr(opt, "grad_scaler", False)))
+        self.resume_train_state()         # (opt.train_state: the mask token's param group and the scaler exist now)
 
     def _scaled_update(self, loss, name):
         net = self.model.networks[name]

@@ -302,6 +302,17 @@ int dei2i_adam_step_clip(const dei2i_adam_rec* table_dev, int count, int64_t max
 int dei2i_adam_step_clip_dev(const dei2i_adam_rec* table_dev, int count, int64_t max_n, const float* hyper_dev, const int* index_dev,
                              int rows, float beta1, float beta2, float eps, const float* scale_dev, int coupled, float weight_decay,
                              dei2i_stream s);
+/* ---- state digest: every 32-bit word of a list of device tensors reduced to one 64-bit word, integer arithmetic mod 2^64:
+ *   digest = sum_k sum_i splitmix64(splitmix64((k << 32) | i) + w[k][i]),  splitmix64(x): x += 0x9E3779B97F4A7C15;
+ *   x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^= x >> 31
+ * Row r of the table is tensor k = row0 + r: rec.p its memory (4-byte aligned), rec.n its count of 32-bit words (<= 2^32, like
+ * max_n); rec.g / m / v are not read.  One launch over the table, grid = dei2i_state_digest_blocks(max_n) x count (count <= 65535),
+ * every workgroup storing its partial to partial_dev[row * blocks + block] (count * blocks words of scratch; no clearing, no
+ * atomics), then one workgroup: out_dev[0] = (accumulate ? out_dev[0] : 0) + the sum of the partials.  A long list goes out in
+ * several calls on one stream: row0 = the rows before, accumulate = 1 from the second call on; partial_dev may be the same. */
+int dei2i_state_digest_blocks(int64_t max_n);
+int dei2i_state_digest(const dei2i_adam_rec* table_dev, int count, int64_t max_n, int64_t row0, uint64_t* partial_dev, int accumulate,
+                       uint64_t* out_dev, dei2i_stream s);
 /* *index_dev += 1 (one thread): captured after a _dev update, it moves the next replay to the next row */
 int dei2i_index_advance(int* index_dev, dei2i_stream s);
 /* EMA of a network's parameters in place, one launch (stargan-v2 moving_average, core/solver.py:549-551): rec.p = the EMA copy,
