@@ -865,8 +865,6 @@ __global__ __launch_bounds__(256) void affine_act_stats_kernel(const T* __restri
 //     tensor [N][ring_pixels][C] (geom.h) the conv kernels read instead of x there.
 // gb: the (N, 5, 5, 2C) border-class table (normalization.py:24-37 on a constant label map).  grid (blocks, N): every
 // block of an image recomputes the image's statistics (a few KB of L2-resident records), block 0 stores them.
-DEI2I_D int prep_border_class(int i, int extent) { return i < 2 ? i : (i >= extent - 2 ? 4 - (extent - 1 - i) : 2); }
-
 template <typename T>
 __global__ __launch_bounds__(256) void spade_prep_kernel(const T* __restrict__ x, const float* __restrict__ partial,
                                                          const T* __restrict__ gb, float* __restrict__ mean,
@@ -906,7 +904,7 @@ __global__ __launch_bounds__(256) void spade_prep_kernel(const T* __restrict__ x
     ring_coord(r, H, W, y, xx);
     float xv[VEC], gm[VEC], bt[VEC], o[VEC];
     Elem<T>::unpack(*reinterpret_cast<const u32x4*>(x + (((size_t)n * Hs + (y >> up)) * Ws + (xx >> up)) * C + c), xv);
-    const size_t gpix = ((size_t)n * 5 + prep_border_class(y, H)) * 5 + prep_border_class(xx, W);
+    const size_t gpix = ((size_t)n * 5 + border_class(y, H)) * 5 + border_class(xx, W);
     Elem<T>::unpack(*reinterpret_cast<const u32x4*>(gb + gpix * 2 * C + c), gm);
     Elem<T>::unpack(*reinterpret_cast<const u32x4*>(gb + gpix * 2 * C + C + c), bt);
 #pragma unroll
@@ -1158,6 +1156,7 @@ int dei2i_spade_bwd_partial(int dtype, int N, int H, int W, int C, int up, const
   if (N <= 0 || H <= 0 || W <= 0 || !cv_ok(dtype, C) || up < 0 || up > 1 || !dz || !x || !mean || !rstd || !gb || !partial)
     return DEI2I_ERR_BAD_ARG;
   if (gb_mode != 1 && !dgb) return DEI2I_ERR_BAD_ARG;        // dense mode: the streaming pass stores the gradient itself
+  if (up && ((H | W) & 1)) return DEI2I_ERR_BAD_ARG;         // x lives on (H >> up, W >> up): as dei2i_spade_act_fwd
   if (gb_mode == 1 && (H < 4 || W < 4)) return DEI2I_ERR_BAD_ARG;
   const int chunks = dei2i_moments_chunks(H * W);
   by_dtype(dtype, [&](auto t) {
@@ -1175,6 +1174,7 @@ int dei2i_spade_bwd_border(int dtype, int N, int H, int W, int C, int up, const 
                            const float* rstd, const void* gb, float slope, void* dgb_cls, dei2i_stream s) {
   if (N <= 0 || H < 4 || W < 4 || !cv_ok(dtype, C) || up < 0 || up > 1 || !dz || !x || !mean || !rstd || !gb || !dgb_cls)
     return DEI2I_ERR_BAD_ARG;
+  if (up && ((H | W) & 1)) return DEI2I_ERR_BAD_ARG;
   by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(spade_bwd_border_kernel<T>, dim3(25, N), dim3(256), combine_lds(dtype, 2), (hipStream_t)s, (const T*)dz,
@@ -1191,6 +1191,8 @@ int dei2i_spade_bwd_apply(int dtype, int N, int H, int W, int C, int up, const v
   if (N <= 0 || H <= 0 || W <= 0 || !cv_ok(dtype, C) || up < 0 || up > 1 || !dz || !x || !mean || !rstd || !gb || !partial ||
       !coef || !dx)
     return DEI2I_ERR_BAD_ARG;
+  if (up && ((H | W) & 1)) return DEI2I_ERR_BAD_ARG;
+  if (gb_mode == 1 && (H < 4 || W < 4)) return DEI2I_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(spade_bwd_finalize_kernel, dim3(C, N), dim3(combine_threads(chunks)), 0, st, partial, N, chunks, C,
                      (double)H * (double)W, coef, dgb_cls, dtype);
