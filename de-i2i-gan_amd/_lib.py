@@ -141,6 +141,8 @@ SIGNATURES = {
     "dei2i_mask_draw": (c_int, [c_uint64, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),
     "dei2i_mask_fill": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, POINTER(c_int64), _P, _P, _P]),
     "dei2i_mask_fill_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "dei2i_embed_draw": (c_int, [c_uint64, _P, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P, _P]),
+    "dei2i_embed_gather": (c_int, [c_int64, c_int, _P, _P, c_int64, _P, _P]),
     "dei2i_prof_enable": (c_int, [c_int, c_int]),
     "dei2i_prof_collect": (c_int, [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
     "dei2i_prof_collect_timed": (c_int, [c_int, POINTER(c_int64), POINTER(c_double)]),

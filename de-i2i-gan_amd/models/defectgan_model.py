@@ -15,6 +15,23 @@ from ..utils.masks import draw_shifted_mask, expand_shifted_mask
 from .base_model import BaseModel
 
 
+def embed_rng_option(opt):
+    """-> ``opt.embed_rng`` as "host" (absent or None too) or "device".  "device" draws SEAN's style embeddings on the GPU: it needs
+    a GPU device, ``style_norm_block_type == "sean"`` and ``sean_alpha != 0`` (ValueError naming what is missing)."""
+    where = getattr(opt, "embed_rng", None) or "host"
+    if where == "host":
+        return where
+    if where != "device":
+        raise ValueError(f"|embed_rng {where}| is invalid (host | device)")
+    if torch.device(opt.device).type != "cuda":
+        raise ValueError(f"embed_rng='device' draws on the GPU; opt.device is {opt.device}")
+    if opt.style_norm_block_type != "sean":
+        raise ValueError(f"embed_rng='device' draws SEAN's style embeddings; style_norm_block_type is {opt.style_norm_block_type!r}")
+    if opt.sean_alpha == 0:
+        raise ValueError("embed_rng='device' with sean_alpha=0: that generator takes no style embeddings, there is nothing to draw")
+    return where
+
+
 class DefectGanModel(BaseModel):
     def __init__(self, opt):
         super().__init__(opt)
@@ -22,8 +39,14 @@ class DefectGanModel(BaseModel):
         assert image_size & (image_size - 1) == 0, "Image size must be a power of 2"
         if opt.style_norm_block_type not in ("spade", "adain", "sean"):
             raise ValueError(f"|style_norm_block_type {opt.style_norm_block_type}| is invalid")
+        embed_where = embed_rng_option(opt)               # (an invalid combination is refused before anything is built)
         self.netG = DefectGanGenerator(opt).to(opt.device, non_blocking=True)
         self.netD = DefectGanDiscriminator(opt).to(opt.device, non_blocking=True)
+        # opt.embed_rng: "host" (or absent) draws SEAN's style embeddings per sample with python's random.choices like the reference,
+        # which reads every label row on the host; "device" packs the embeddings file into one device tensor (ops.EmbedBank) and
+        # draws them on the GPU from a third counter-based generator, seeded by opt.embed_seed, under the rules of diff_aug_rng below.
+        self.embed_rng = self.embed_bank = None
+        self.embed_ranks = None           # (set by parallel.attach_ddp: the rank whose rows of the global batch's draw these are)
         if opt.style_norm_block_type == "sean":          # style embeddings (defectgan_model.py:34-45)
             if opt.sean_alpha is not None:
                 self.netG.set_sean_alpha(opt.sean_alpha)
@@ -31,9 +54,17 @@ class DefectGanModel(BaseModel):
                 assert opt.embed_path is not None, ("embed_path should be initialized if style_norm_block_type is sean and "
                                                     "sean_alpha is not 0")
                 # {label tuple: [embedding (embed_nc,), ...]} -- the user's own file; loaded without executing anything from it
-                self.embeddings = torch.load(opt.embed_path, weights_only=True)
-                for label, embeds in self.embeddings.items():
-                    self.embeddings[label] = [e.to(opt.device, non_blocking=True) for e in embeds]
+                embeddings = torch.load(opt.embed_path, weights_only=True)
+                if embed_where == "device":
+                    seed = getattr(opt, "embed_seed", None)
+                    if seed is None:
+                        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+                    self.embed_bank = ops.EmbedBank(embeddings, opt.label_nc, opt.embed_nc, seed, opt.device)
+                    self.embed_rng = self.embed_bank.rng
+                else:
+                    self.embeddings = embeddings
+                    for label, embeds in self.embeddings.items():
+                        self.embeddings[label] = [e.to(opt.device, non_blocking=True) for e in embeds]
         if opt.style_norm_block_type == "adain":         # style embedding network, trained by the G loss (defectgan_model.py:46-47)
             from ..networks.extractor import StyleExtractor
             self.netE = StyleExtractor(opt).to(opt.device, non_blocking=True)
@@ -533,10 +564,16 @@ class DefectGanModel(BaseModel):
 
     def _get_style_embeds(self, labels):
         """defectgan_model.py:394-411: per sample ``num_embeds`` embeddings drawn (python's ``random.choices``, like the
-        reference) from the list stored for its label tuple -- zeros when that list is empty; None with --sean_alpha 0."""
+        reference) from the list stored for its label tuple -- zeros when that list is empty; None with --sean_alpha 0.
+        embed_rng 'device': the same draw on the GPU (ops.embed_draw, two launches per call, no host read); under ``attach_ddp`` the
+        rows are this rank's rows of the global batch's draw, so that N ranks on one seed draw what one process draws."""
         if self.opt.sean_alpha == 0:
             return None
         num_embeds = self.opt.num_embeds
+        if self.embed_bank is not None:
+            red = self.embed_ranks
+            row0 = red.rank * labels.size(0) if red is not None and red.world > 1 else 0
+            return ops.embed_draw(self.embed_bank, labels, num_embeds, row0=row0)[0]
         embed_list = []
         for label in labels.reshape(labels.size(0), -1):
             tuple_label = tuple(label.int().tolist())

@@ -18,10 +18,20 @@ def _reference_key(key):
     return key.replace("spade_", "").replace("sean_", "")
 
 
+def _dropped_on_load(key):
+    return "mlp_latent" in key
+
+
+def tensors_dropped_on_load(net):
+    """{key: tensor} of ``net.state_dict()`` that ``load_network`` leaves as they are (SEAN's label-latent layers): what an exact
+    resume has to carry next to the weight file (the train-state file does)"""
+    return {k: v for k, v in net.state_dict().items() if _dropped_on_load(k)}
+
+
 def load_network(net, net_label, epoch, opt):
     """Tensors only (``weights_only=True``); 'mlp_latent' entries are dropped and missing / unexpected keys tolerated
     (``strict=False``) exactly as the reference does (:21-22).  Returns the network on ``opt.device``."""
     stored = torch.load(_checkpoint_path(opt, opt.load_model_name, net_label, epoch), map_location="cpu", weights_only=True)
-    state = {_reference_key(k): v for k, v in stored.items() if "mlp_latent" not in k}
+    state = {_reference_key(k): v for k, v in stored.items() if not _dropped_on_load(k)}
     net.load_state_dict(state, strict=False)
     return net.to(opt.device, non_blocking=True)

@@ -7,7 +7,8 @@ parameters, gradients, state_dict), as in the reference.  Every op requires a GP
 Random numbers: ``NoiseInjection`` draws with torch's device RNG; ``diff_augment`` draws its per-sample parameters from the global
 CPU RNG and uploads them (the reference's draws), or, given a ``DiffAugRng``, on the device from a counter-based generator whose
 call count lives in device memory -- the form a captured graph can replay.  The MAE stage's patch masks have the same two sources
-(utils/masks.py on the host; ``mask_draw`` with a ``DeviceRng`` of its own).
+(utils/masks.py on the host; ``mask_draw`` with a ``DeviceRng`` of its own), and so have SEAN's style embeddings (python's
+``random.choices`` in the model; ``embed_draw`` on an ``EmbedBank``).
 """
 from __future__ import annotations
 
@@ -2274,6 +2275,108 @@ def mask_fill(imgs, keep, shift, patch, token=None):
             raise ValueError(f"mask_fill: a token of shape {tuple(token.shape)} does not broadcast to one image")
         torch.broadcast_shapes(tuple(token.shape), (1,) + tuple(imgs.shape[1:]))       # (raises when it does not)
     return _MaskFill.apply(imgs, token, keep, shift, patch)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Device-drawn style embeddings of the SEAN generator (csrc/embed.hip).  The reference draws them per sample with python's
+# ``random.choices`` from the list stored for the sample's label tuple, which reads every label row on the host.  ``EmbedBank`` packs
+# the lists into one device tensor once; ``embed_draw`` draws the rows' indices on the device from the bank's own ``DeviceRng`` (the
+# counter-word layout: include/dei2i_hip.h) and gathers them -- two launches that can be captured into a graph, and every replay
+# draws other embeddings.
+# --------------------------------------------------------------------------------------------------------------
+EMBED_MAX_LABEL_NC = 16
+
+
+def embed_pack(embeddings, label_nc, embed_nc):
+    """The host half of ``EmbedBank``: ``{label tuple: [tensor (embed_nc,), ...]}`` -> (bank, table) on the CPU.  ``bank``: fp32
+    (total, embed_nc), the lists in ascending combination index (``sum_i label[i] << (label_nc - 1 - i)``: the first label is the
+    slowest digit, torch.cartesian_prod order), each in its own order; ``table``: int32 (1 << label_nc, 2) of (offset, count), a
+    combination the file does not hold counting as an empty list.  ValueError naming the key: a key that is no tuple of ``label_nc``
+    zeros and ones, an embedding that is not an fp32 (embed_nc,) tensor."""
+    label_nc, embed_nc = int(label_nc), int(embed_nc)
+    if not 1 <= label_nc <= EMBED_MAX_LABEL_NC:
+        raise ValueError(f"EmbedBank: |label_nc {label_nc}| is invalid (1..{EMBED_MAX_LABEL_NC}: the table has 2^label_nc rows)")
+    if embed_nc <= 0:
+        raise ValueError(f"EmbedBank: |embed_nc {embed_nc}| is invalid")
+    lists = {}
+    for key, embeds in embeddings.items():
+        bits = tuple(key) if isinstance(key, (tuple, list)) else None
+        if bits is None or len(bits) != label_nc or any(b not in (0, 1) for b in bits):
+            raise ValueError(f"EmbedBank: key {key!r} is not a tuple of {label_nc} labels, each 0 or 1")
+        for j, e in enumerate(embeds):
+            if not isinstance(e, torch.Tensor) or tuple(e.shape) != (embed_nc,) or e.dtype != torch.float32:
+                what = f"{tuple(e.shape)} {e.dtype}" if isinstance(e, torch.Tensor) else type(e).__name__
+                raise ValueError(f"EmbedBank: embedding {j} of key {key!r} is {what}, not an fp32 ({embed_nc},) tensor")
+        combo = 0
+        for b in bits:
+            combo = (combo << 1) | int(b)
+        lists[combo] = list(embeds)
+    table = torch.zeros((1 << label_nc, 2), dtype=torch.int32)
+    rows = []
+    for combo in sorted(c for c in lists if lists[c]):       # (an empty list stays (0, 0), like a missing key)
+        table[combo, 0], table[combo, 1] = len(rows), len(lists[combo])
+        rows.extend(e.detach().cpu() for e in lists[combo])
+    if len(rows) >= 2 ** 31:
+        raise ValueError(f"EmbedBank: {len(rows)} embeddings; the index is 32 bits wide")
+    bank = torch.stack(rows) if rows else torch.zeros((0, embed_nc), dtype=torch.float32)
+    return bank, table
+
+
+class EmbedBank:
+    """The embeddings of ``opt.embed_path`` packed for ``embed_draw`` (``embed_pack``): ``bank`` fp32 (max(total, 1), embed_nc) and
+    ``table`` int32 (1 << label_nc, 2) on the device, the generator ``rng`` (a ``DeviceRng``: seed and call counter) and the
+    ``invalid`` word, the count of label rows with an entry that is neither 0 nor 1 (their embeddings are zeros).  All allocated
+    here, outside any capture; they must outlive every graph that recorded a draw on them.  ``invalid()`` synchronises: not for use
+    inside a step."""
+
+    def __init__(self, embeddings, label_nc, embed_nc, seed, device):
+        self.rng = DeviceRng(seed, device)                   # (refuses a CPU device)
+        self.device = self.rng.device
+        self.label_nc, self.embed_nc = int(label_nc), int(embed_nc)
+        bank, table = embed_pack(embeddings, label_nc, embed_nc)
+        self.total = bank.shape[0]
+        if self.total == 0:                                  # (every list empty: one row that no index ever names)
+            bank = torch.zeros((1, self.embed_nc), dtype=torch.float32)
+        self.bank = bank.to(self.device)
+        self.table = table.to(self.device)
+        self.invalid_word = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def invalid(self):
+        """-> the number of invalid label rows drawn for so far"""
+        return int(self.invalid_word.item()) & (2 ** 64 - 1)
+
+    def digest(self):
+        """``state_digest`` over the bank and the table: a one-element int64 device tensor"""
+        return state_digest([self.bank, self.table])
+
+
+def embed_draw(bank: EmbedBank, labels, num_embeds, row0=0):
+    """SEAN's style embeddings for a batch of label rows: -> (feat, index), ``feat`` fp32 (N, num_embeds, embed_nc), ``index`` int32
+    (N, num_embeds) the bank rows they are (-1: zeros -- the row's combination has no embeddings, or the row is invalid), for global
+    rows [row0, row0 + N).  ``labels``: (N, label_nc) or (N, label_nc, 1, 1) on the bank's device, any float or integer dtype.  One
+    dei2i_embed_draw and one dei2i_embed_gather launch on the current stream: nothing is read on the host and nothing is uploaded."""
+    _require_gpu(labels, "embed_draw")
+    if labels.device != bank.device:
+        raise ValueError(f"embed_draw: the bank lives on {bank.device}, the labels on {labels.device}")
+    if labels.dim() == 4 and tuple(labels.shape[2:]) == (1, 1):
+        labels = labels.reshape(labels.shape[0], labels.shape[1])
+    if labels.dim() != 2 or labels.shape[1] != bank.label_nc or labels.shape[0] == 0:
+        raise ValueError(f"embed_draw: labels of shape {tuple(labels.shape)}; expected (N, {bank.label_nc}) or (N, {bank.label_nc}, 1, 1)")
+    if labels.dtype == torch.bool or labels.is_complex():
+        raise TypeError(f"embed_draw: labels of dtype {labels.dtype}; expected a float or integer dtype")
+    num_embeds = int(num_embeds)
+    if num_embeds <= 0:
+        raise ValueError(f"embed_draw: |num_embeds {num_embeds}| is invalid")
+    n = labels.shape[0]
+    labels = _f32c(labels.detach())
+    index = torch.empty((n, num_embeds), dtype=torch.int32, device=bank.device)
+    feat = torch.empty((n, num_embeds, bank.embed_nc), dtype=torch.float32, device=bank.device)
+    lib = _lib_for(feat)
+    L.check(lib.dei2i_embed_draw(bank.rng.seed, _p(bank.rng.counter), n, int(row0), bank.label_nc, num_embeds, _p(labels), _p(bank.table),
+                                 bank.total, _p(index), _p(bank.invalid_word), _stream()), "embed_draw")
+    L.check(lib.dei2i_embed_gather(n * num_embeds, bank.embed_nc, _p(index), _p(bank.bank), bank.bank.shape[0], _p(feat), _stream()),
+            "embed_gather")
+    return feat, index
 
 
 # --------------------------------------------------------------------------------------------------------------

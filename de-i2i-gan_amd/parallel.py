@@ -28,8 +28,9 @@ MI355X node (8 GPUs, point-to-point xGMI, no switch):
   computes the same running statistics from the same summed message, so ``broadcast_buffers`` does nothing.  The MAE stage draws its
   patch mask for the global batch on every rank (same RNG consumption; rank 0's CPU RNG state is broadcast at attach) and keeps its
   rows.  Every rank must hold the same number of rows.  The equality covers the SPADE generator with the default options,
-  ``use_spectral`` and ``cycle_gan``; ``add_noise``, ``diff_aug`` and the SEAN blocks draw per-rank random numbers: they run with
-  ``sync_bn`` but equal no single-process run.  Counted apart from the gradients: ``stats["sync_bn_collectives"]`` / ``["sync_bn_bytes"]``.
+  ``use_spectral`` and ``cycle_gan``; ``add_noise``, ``diff_aug`` and the SEAN blocks' host-drawn embeddings are per-rank random numbers: they run with
+  ``sync_bn`` but equal no single-process run (``opt.embed_rng = "device"`` with one ``embed_seed`` draws the global batch's embeddings,
+  each rank its rows: ops.embed_draw's ``row0``).  Counted apart from the gradients: ``stats["sync_bn_collectives"]`` / ``["sync_bn_bytes"]``.
   Off (the default): nothing changes -- same kernels, same launches, same bits.  Eval-mode BatchNorm never exchanges.
 * ``attach_ddp`` broadcasts rank 0's parameters and buffers (spectral-norm u / v included) once, one flat message per
   network, like torch DDP does at construction: replicas start identical whatever each rank's seed or checkpoint was.
@@ -303,7 +304,7 @@ def attach_ddp(trainer, process_group=None, sync_bn: bool = False, **kw) -> Grad
     backward and averaged inside the fused Adam kernel.  The two trainers: generator BatchNorm statistics stay per rank and the
     buffers follow rank 0 -- or, with ``sync_bn=True``, are taken over the global batch, which makes N ranks on their rows equal ONE
     process on the whole batch (module docstring: mechanism, and which options the equality covers -- ``add_noise``, ``diff_aug`` and
-    SEAN draw per-rank random numbers and equal no single-process run).  Solver: see ``_attach_solver`` (it has no batch statistics:
+    SEAN's host-drawn embeddings are per-rank random numbers and equal no single-process run).  Solver: see ``_attach_solver`` (it has no batch statistics:
     ``sync_bn`` is a ValueError)."""
     from .stargan import Solver
     if isinstance(trainer, Solver):
@@ -329,6 +330,8 @@ def attach_ddp(trainer, process_group=None, sync_bn: bool = False, **kw) -> Grad
         _broadcast_rng_state(process_group, torch.device(trainer.opt.device))
     if getattr(trainer.model, "diffaug_p", None) is not None:       # opt.diff_aug_p / opt.ada_target: the global batch's gates on every
         trainer.model.ada_ranks = red                               # rank (one diff_aug_seed), the measured pair summed over the ranks
+    if getattr(trainer.model, "embed_bank", None) is not None:      # opt.embed_rng = "device": SEAN's embeddings drawn for the global
+        trainer.model.embed_ranks = red                             # batch's rows (one embed_seed on every rank)
     trainer.reducer = red
     return red
 

@@ -128,16 +128,21 @@ def check_digests(stored, now, file_of):
 # ---- the option --------------------------------------------------------------------------------------------------------------
 def train_state_option(opt):
     """-> ``opt.train_state`` as a bool (absent, None or False: off -- no file is written or read and no launch is made).  Refused
-    before anything is built: SEAN generators (their per-epoch embedding lists and ``random.choices`` draws live in Python objects,
-    the line ``graph_step`` draws too) and a CPU device (the digests are computed on the GPU)."""
+    before anything is built: SEAN generators with host-drawn embeddings (the ``random.choices`` draws live in Python's RNG) or with
+    ``use_running_stats`` (the tracked codes live in Python lists) -- ``opt.embed_rng = "device"`` draws from a counter the file
+    carries -- and a CPU device (the digests are computed on the GPU)."""
     on = getattr(opt, "train_state", None)
     if on is None or on is False:
         return False
     if on is not True:
         raise ValueError(f"|train_state {on!r}| is invalid (True or False)")
     if getattr(opt, "style_norm_block_type", None) == "sean":
-        raise NotImplementedError("train_state with style_norm_block_type='sean' (its embedding lists and the host's random.choices "
-                                  "draws are not part of a checkpoint)")
+        if getattr(opt, "embed_rng", None) != "device":
+            raise NotImplementedError("train_state with style_norm_block_type='sean' (its embedding lists and the host's random.choices "
+                                      "draws are not part of a checkpoint; build the trainer with embed_rng='device')")
+        if getattr(opt, "use_running_stats", False):
+            raise NotImplementedError("train_state with style_norm_block_type='sean' and use_running_stats=True (the tracked codes "
+                                      "live in Python lists that are not part of a checkpoint)")
     if torch.device(opt.device).type != "cuda":
         raise ValueError(f"train_state computes its digests on the GPU; opt.device is {opt.device}")
     return True

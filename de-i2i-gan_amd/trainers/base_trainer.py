@@ -10,6 +10,7 @@ from torch import optim
 from .. import ops
 from .. import train_state as TS
 from ..models import create_model
+from ..networks import tensors_dropped_on_load
 from ..optim import FusedAdam, FusedRMSprop, FusedSGD, ada_options, clip_options, ema_options
 
 
@@ -224,12 +225,17 @@ class BaseTrainer:
             return {"mask_token": token}
         return {}
 
+    def _sibling_networks(self):
+        """{name: module} of the weight files: ``net_<label>`` the networks, ``net_<label>_ema`` their EMA copies"""
+        out = {f"net_{label}": net for label, net in self.model.networks.items()}
+        out.update({f"net_{label}_ema": net for label, net in self.model.ema.items()})
+        return out
+
     def _sibling_tensors(self):
         """{name: tensors}: what each sibling file of a checkpoint holds, from the live modules -- ``net_<label>`` and
         ``net_<label>_ema`` (``state_dict()`` values in key order), ``ada`` (p_rt, acc); file ``<epoch>_<name>.pth``"""
         model = self.model
-        out = {f"net_{label}": list(net.state_dict().values()) for label, net in model.networks.items()}
-        out.update({f"net_{label}_ema": list(net.state_dict().values()) for label, net in model.ema.items()})
+        out = {name: list(net.state_dict().values()) for name, net in self._sibling_networks().items()}
         ada = getattr(model, "ada", None)
         if ada is not None:
             out["ada"] = [ada.p_rt, ada.acc]
@@ -253,13 +259,21 @@ class BaseTrainer:
                  # (host state that decides launches: which SPADE table modules the generator's first forward found running)
                  "table_marks": {label: net.table_marks() for label, net in model.networks.items() if hasattr(net, "table_marks")},
                  "rng": TS.rng_state(device), "digests": TS.digests(self._sibling_tensors())}
+        # (what load_network drops from a weight file -- SEAN's label-latent layers, like the reference: a resumed run needs them)
+        dropped = {name: {k: v.detach().cpu() for k, v in tensors_dropped_on_load(net).items()}
+                   for name, net in self._sibling_networks().items()}
+        if any(dropped.values()):
+            state["dropped_on_load"] = {name: tensors for name, tensors in dropped.items() if tensors}
         scaler = getattr(self, "scaler", None)
         if scaler is not None and scaler.is_enabled():
             state["grad_scaler"] = scaler.state_dict()
-        for key in ("diffaug_rng", "mask_rng"):
+        for key in ("diffaug_rng", "mask_rng", "embed_rng"):
             rng = getattr(model, key, None)
             if rng is not None:
                 state[key] = list(rng.state())
+        bank = getattr(model, "embed_bank", None)
+        if bank is not None:              # (the draws index the packed embeddings file: a resumed run must pack the same one)
+            state["embed_digest"] = int(bank.digest().item()) & (2 ** 64 - 1)
         return state
 
     def resume_train_state(self):
@@ -287,9 +301,21 @@ class BaseTrainer:
         if opt.continue_training and int(state["iters"]) != int(self.iters):
             raise RuntimeError(f"{self.iter_record_path} does not belong to this checkpoint: it records iteration {int(self.iters)}, "
                                f"{path.name} was saved at iteration {int(state['iters'])}")
+        for name, tensors in state.get("dropped_on_load", {}).items():       # (before the digests: they cover these tensors too)
+            net = self._sibling_networks().get(name)
+            if net is not None:
+                net.load_state_dict(tensors, strict=False)
+                ops.mark_written(*net.parameters())
         TS.check_digests(state["digests"], TS.digests(self._sibling_tensors()), lambda name: path.with_name(f"{label}_{name}.pth"))
         if sorted(state["optimizers"]) != sorted(self.optimizers):
             raise RuntimeError(f"{path}: saved with optimizers {sorted(state['optimizers'])}, this trainer has {sorted(self.optimizers)}")
+        bank = getattr(self.model, "embed_bank", None)
+        if bank is not None and "embed_digest" in state:
+            now = int(bank.digest().item()) & (2 ** 64 - 1)
+            if now != int(state["embed_digest"]):
+                raise RuntimeError(f"opt.embed_path ({opt.embed_path}) does not hold the embeddings this checkpoint was saved with: "
+                                   f"{path.name} records digest {int(state['embed_digest']):#018x} of the packed file, this one gives "
+                                   f"{now:#018x} (the embeddings file changed between the save and the resume)")
         self.release_graphs()
         for name, o in self.optimizers.items():
             TS.load_optimizer_state(o, state["optimizers"][name], name)
@@ -303,7 +329,7 @@ class BaseTrainer:
         scaler = getattr(self, "scaler", None)
         if scaler is not None and scaler.is_enabled() and "grad_scaler" in state:
             scaler.load_state_dict(state["grad_scaler"])
-        for key in ("diffaug_rng", "mask_rng"):
+        for key in ("diffaug_rng", "mask_rng", "embed_rng"):
             rng = getattr(self.model, key, None)
             if rng is not None and key in state:
                 rng.set_state(tuple(state[key]))

@@ -18,7 +18,10 @@ What the capture cannot honour raises ``NotImplementedError`` (``unsupported``).
 call counter lives in device memory and advances inside the draw launch, so every replay draws what the eager call would have
 drawn); with host draws, which a capture would freeze into every replay, it is refused.  The MAE stage's patch masks follow the
 same rule (``opt.mask_rng = "device"``: ops.mask_draw / ops.mask_fill; host-drawn masks are refused), and so does its
-``opt.grad_scaler``, whose overflow check reads the device once per update."""
+``opt.grad_scaler``, whose overflow check reads the device once per update.  The SEAN generator is captured with device-drawn
+style embeddings (``opt.embed_rng = "device"``: ops.embed_draw on the model's ``EmbedBank``, which the model owns and which
+outlives the graphs); with host draws, with ``use_running_stats`` (per-sample host reads) and with ``style_distill`` (a backward
+inside the forward) it is refused.  Its four generator passes run one after another: the capture stays one chain."""
 import contextlib
 
 import torch
@@ -52,9 +55,16 @@ def unsupported(trainer):
         return ("diff_aug with host draws (its parameters are drawn from the CPU RNG and uploaded per call; build the trainer with "
                 "diff_aug_rng='device' to draw them on the GPU)")
     if opt.style_norm_block_type == "sean":
-        return "style_norm_block_type='sean' (it draws style embeddings with the host's random.choices)"
-    if opt.style_norm_block_type != "spade":
-        return f"style_norm_block_type={opt.style_norm_block_type!r} (only the SPADE generator is captured)"
+        if getattr(opt, "use_running_stats", False):
+            return ("style_norm_block_type='sean' with use_running_stats=True (its tracked codes are read per sample with .item() "
+                    "into Python lists)")
+        if getattr(opt, "style_distill", False):
+            return "style_norm_block_type='sean' with style_distill=True (its backward runs inside the SEAN layers' forward)"
+        if getattr(trainer.model, "embed_bank", None) is None:
+            return ("style_norm_block_type='sean' (it draws style embeddings with the host's random.choices; build the trainer with "
+                    "embed_rng='device' to draw them on the GPU)")
+    elif opt.style_norm_block_type != "spade":
+        return f"style_norm_block_type={opt.style_norm_block_type!r} (only the SPADE and SEAN generators are captured)"
     if getattr(trainer, "reducer", None) is not None:
         return "an attached GradReducer (collectives inside a capture)"
     if not all(type(o) is FusedAdam for o in trainer.optimizers.values()):

@@ -409,6 +409,28 @@ int dei2i_mask_fill(int N, int C, int H, int W, int patch, const int* shift_dev,
 int dei2i_mask_fill_bwd(int N, int C, int H, int W, int patch, const int* shift_dev, const unsigned char* keep_dev,
                         const float* grad_out, float* grad_full, dei2i_stream s);
 
+/* ---- device-drawn style embeddings of the SEAN generator (csrc/embed.hip) ----
+ * The embeddings file {label combination: list of embeddings} is packed into one fp32 bank (bank_rows x embed_nc), the lists in
+ * ascending combination index, and an int32 table (1 << label_nc) x 2 of (offset, count) per combination.  The combination index
+ * of a label row is sum_i b_i << (label_nc - 1 - i), b_i = (int)labels[n][i]: the first label is the slowest digit
+ * (torch.cartesian_prod order).  A row with some b_i outside {0, 1} is invalid.
+ *
+ * dei2i_embed_draw fills index_out[N][num_embeds] (int32) for global rows [row0, row0 + N) from Philox4x32-10: key = seed, counter
+ * words = (call low 32, call high 32, 0xA0000000 | e / 4, row0 + n), call = *counter_dev as the launch finds it; slot e takes word
+ * x[e % 4]: index = offset + mulhi(x, count).  A combination with count == 0 (the reference feeds zeros for an empty list), an
+ * invalid row and a table entry that does not lie inside [0, table_total) write -1.  labels: contiguous fp32 N x label_nc.
+ * *invalid_dev (one 64-bit word) grows by the number of invalid rows of the call.  One launch of one workgroup, no global atomics;
+ * it leaves *counter_dev greater by exactly 1 (the ordering rule of dei2i_diffaug_draw holds, for invalid_dev too).  The draw is a
+ * pure function of (seed, call, e, row0 + n, the row's labels).  BAD_ARG: null pointers, N <= 0, row0 < 0, row0 + N > 2^31,
+ * label_nc outside 1..16, num_embeds <= 0 or > 2^28, table_total < 0.
+ *
+ * dei2i_embed_gather: out[r][:] = bank[index[r]][:] for r < rows (rows = N * num_embeds), zeros for an index outside
+ * [0, bank_rows) -- no address is formed from such an index.  float4 copies when embed_nc % 4 == 0 and bank and out are 16-byte
+ * aligned, scalar ones otherwise.  BAD_ARG: null pointers, a size <= 0, rows * embed_nc or bank_rows * embed_nc >= 2^40. */
+int dei2i_embed_draw(uint64_t seed, uint64_t* counter_dev, int N, int row0, int label_nc, int num_embeds, const float* labels,
+                     const int* table, int64_t table_total, int* index_out, uint64_t* invalid_dev, dei2i_stream s);
+int dei2i_embed_gather(int64_t rows, int embed_nc, const int* index, const float* bank, int64_t bank_rows, float* out, dei2i_stream s);
+
 /* ---- spectral normalisation of a conv weight (--use_spectral; torch.nn.utils.spectral_norm semantics, one power
  * iteration per training-mode forward) ----  W = weight_orig as a (Cout, K) fp32 matrix, u (Cout) / v (K) the module's
  * buffers (updated in place when iterate != 0); u_used / v_used receive the vectors sigma was computed with (the backward

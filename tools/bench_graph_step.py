@@ -16,6 +16,8 @@ host time of a ``step()`` call, ``wall_ms_per_step`` the whole timed region divi
 
     python tools/bench_graph_step.py --max-grad-norm 1.0 --clip off --clip torch --clip fused [--repeat 2]
 
+    python tools/bench_graph_step.py --sean --use-spectral --add-noise --embed-rng host --embed-rng device [--repeat 2]
+
 ``--diff-aug-rng host`` draws DiffAugment's parameters on the host like the reference (graph mode refuses it), ``device`` on the
 GPU (``ops.DiffAugRng``).  ``--stage mae`` runs ``MAETrainer`` (bench.py's MAE option set) on the background batch and its labels;
 ``--mask-rng host`` draws its patch masks on the host like the reference (graph mode refuses it), ``device`` on the GPU
@@ -24,7 +26,10 @@ buffer copies per G update), averaging from the first update unless ``--ema-star
 ``--max-grad-norm X`` is applied: ``fused`` is ``opt.max_grad_norm`` (the norm and the clip inside the fused Adam, eager or captured),
 ``torch`` is what a user would write without it -- ``torch.nn.utils.clip_grad_norm_(params, X, foreach=True)`` right before every
 ``optimizer.step()``, eager only --, ``off`` no clipping.  Every (clip, mode) pair is one column; ``--repeat N`` runs the columns N
-times in turn, so that a run shows its own spread."""
+times in turn, so that a run shows its own spread.  ``--sean`` is the README's SEAN recipe: ``style_norm_block_type = "sean"`` on a
+synthetic embeddings file (``--embeds-per-label`` N(0, 1) embeddings of ``embed_nc`` = 768 for every label combination with one or two
+labels set, ``--num-embeds`` drawn per sample); ``--embed-rng`` (repeatable) is where they are drawn: ``host`` with python's
+``random.choices`` like the reference (eager only: graph mode refuses it), ``device`` on the GPU (``ops.embed_draw``)."""
 import argparse
 import json
 import os
@@ -51,7 +56,21 @@ def clip_before_step(optimizer, max_norm):
     optimizer.step = clipped_step
 
 
-def run(opts, mode, device, clip="off"):
+def synthetic_embeddings_file(opts):
+    """{label tuple: [embedding (768,), ...]} for the combinations with one or two labels set, as a file -> its path"""
+    import itertools
+    import tempfile
+    from pathlib import Path
+    g = torch.Generator().manual_seed(99)
+    emb = {}
+    for key in itertools.product((0, 1), repeat=6):
+        emb[key] = list(torch.randn(opts.embeds_per_label, 768, generator=g).unbind(0)) if 1 <= sum(key) <= 2 else []
+    path = Path(tempfile.mkdtemp()) / "embeds.pth"
+    torch.save(emb, path)
+    return path
+
+
+def run(opts, mode, device, clip="off", embed_rng=None):
     from de_i2i_gan_amd.trainers.defectgan_trainer import DefectGanTrainer
     from de_i2i_gan_amd.trainers.mae_trainer import MAETrainer
     mae = opts.stage == "mae"
@@ -69,6 +88,9 @@ def run(opts, mode, device, clip="off"):
         opt.mask_seed = opts.mask_seed
     if opts.ema_beta:
         opt.ema_beta, opt.ema_start_iter = opts.ema_beta, opts.ema_start_iter
+    if opts.sean:
+        opt.style_norm_block_type, opt.num_embeds, opt.embed_path = "sean", opts.num_embeds, opts.embed_path
+        opt.embed_rng, opt.embed_seed = embed_rng, opts.embed_seed
     if clip == "fused":
         opt.max_grad_norm = opts.max_grad_norm
     if mode == "graph":
@@ -96,7 +118,7 @@ def run(opts, mode, device, clip="off"):
     wall = 1e3 * (time.perf_counter() - t_start) / opts.steps
     gaps = [events[i].elapsed_time(events[i + 1]) for i in range(opts.steps)]
     tr.flush_losses()
-    res = {"mode": mode, "clip": clip, "ms_per_step": round(statistics.median(gaps), 3), "ms_min": round(min(gaps), 3), "ms_max": round(max(gaps), 3),
+    res = {"mode": mode, "clip": clip, "embed_rng": embed_rng, "ms_per_step": round(statistics.median(gaps), 3), "ms_min": round(min(gaps), 3), "ms_max": round(max(gaps), 3),
            "wall_ms_per_step": round(wall, 3), "host_enqueue_ms": round(statistics.median(host), 3),
            "graphs": len(tr._graphs.graphs) if tr._graphs is not None else 0,
            "d_gan_last": round(tr.losses["gan"]["D"][-1], 6)}
@@ -131,6 +153,12 @@ def main():
     ap.add_argument("--clip", action="append", default=None, choices=["off", "torch", "fused"],
                     help="repeatable; how --max-grad-norm is applied (torch: clip_grad_norm_ before every optimizer.step, eager only; "
                          "fused: opt.max_grad_norm); default: off")
+    ap.add_argument("--sean", action="store_true", help="the SEAN generator on a synthetic embeddings file (the README's SEAN recipe with --use-spectral --add-noise)")
+    ap.add_argument("--embed-rng", dest="embed_rng", action="append", default=None, choices=["host", "device"],
+                    help="--sean, repeatable: where the style embeddings are drawn (host: eager only); default: host")
+    ap.add_argument("--embed-seed", dest="embed_seed", type=int, default=5678)
+    ap.add_argument("--num-embeds", dest="num_embeds", type=int, default=3, help="--sean: embeddings drawn per sample")
+    ap.add_argument("--embeds-per-label", dest="embeds_per_label", type=int, default=64, help="--sean: embeddings stored per label combination")
     ap.add_argument("--repeat", type=int, default=1, help="run every (clip, mode) column this many times, in turn")
     ap.add_argument("--mode", action="append", default=None, choices=["eager", "graph"], help="repeatable; default: eager, then graph")
     opts = ap.parse_args()
@@ -144,19 +172,25 @@ def main():
     if any(c != "off" for c in clips) and not (opts.max_grad_norm and opts.max_grad_norm > 0):
         ap.error("--clip torch / fused need --max-grad-norm X with X > 0")
     # (clip_grad_norm_ between backward and step is host code a capture would freeze: the yardstick is eager only)
-    columns = [(c, m) for c in clips for m in (opts.mode or ["eager", "graph"]) if not (c == "torch" and m == "graph")]
+    if opts.embed_rng and not opts.sean:
+        ap.error("--embed-rng needs --sean")
+    draws = (opts.embed_rng or ["host"]) if opts.sean else [None]
+    # (... and so are host-drawn style embeddings: graph mode refuses them)
+    columns = [(c, m, e) for e in draws for c in clips for m in (opts.mode or ["eager", "graph"])
+               if not (c == "torch" and m == "graph") and not (e == "host" and m == "graph")]
     if not columns or opts.repeat < 1:
-        ap.error("nothing to run (--clip torch is eager only)")
+        ap.error("nothing to run (--clip torch and --embed-rng host are eager only)")
     torch.cuda.set_device(0)
+    opts.embed_path = synthetic_embeddings_file(opts) if opts.sean else None
     runs = []
     for _ in range(opts.repeat):
-        for clip, mode in columns:
-            res = run(opts, mode, "cuda:0", clip)
+        for clip, mode, embed_rng in columns:
+            res = run(opts, mode, "cuda:0", clip, embed_rng)
             runs.append(res)
             print("[bench_graph_step]", json.dumps(res), file=sys.stderr, flush=True)
     print(json.dumps({"workload": "MAE-GAN MAETrainer.step" if opts.stage == "mae" else "defectGAN DefectGanTrainer.step", "device": torch.cuda.get_device_name(0), "image_size": opts.image_size,
                       "batch": opts.batch, "dtype": opts.dtype, "use_spectral": opts.use_spectral, "add_noise": opts.add_noise,
-                      "diff_aug": opts.diff_aug, "diff_aug_rng": opts.diff_aug_rng or "host", "mask_rng": opts.mask_rng or "host", "ema_beta": opts.ema_beta,
+                      "diff_aug": opts.diff_aug, "diff_aug_rng": opts.diff_aug_rng or "host", "mask_rng": opts.mask_rng or "host", "sean": opts.sean, "ema_beta": opts.ema_beta,
                       "ema_start_iter": opts.ema_start_iter, "max_grad_norm": opts.max_grad_norm, "steps": opts.steps,
                       "warmup": opts.warmup, "runs": runs}))
 
