@@ -10,6 +10,7 @@ BF16, F32 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 PAD_ZERO, PAD_REFLECT = 0, 1
 DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT, DIFFAUG_MAX_RUNS = 1, 2, 4, 16
+BLIT_FLIP, BLIT_ROT90 = 1, 2
 PROF_GATHER_GEMM, PROF_WGRAD, PROF_HALO_CONV, PROF_HALO_FOLD = 0, 1, 2, 3
 
 
@@ -136,6 +137,9 @@ SIGNATURES = {
     "dei2i_diffaug": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dei2i_diffaug_draw": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, c_int, c_int, _P, _P]),
     "dei2i_diffaug_draw_p": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "dei2i_blit": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
+    "dei2i_blit_draw": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, _P, _P]),
+    "dei2i_blit_draw_p": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, _P, _P, _P]),
     "dei2i_ada_measure": (c_int, [_P, c_int64, _P, c_int, _P]),
     "dei2i_ada_apply": (c_int, [_P, c_int64, _P, _P, c_int, c_float, c_float, c_float, _P]),
     "dei2i_mask_draw": (c_int, [c_uint64, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),

@@ -1963,6 +1963,44 @@ class _DiffAugAdjoint(torch.autograd.Function):
         return _DiffAug.apply(gg, ctx.tab, ctx.run, 1, None), None, None
 
 
+# The blit runs (flip -> rot90, csrc/blit.hip): a permutation of the pixels per sample, whose input gradient is the inverse
+# permutation of the output gradient and whose own gradient is the forward again -- exact to any order.  Nothing is saved but the codes.
+def _blit_run(x, codes, inverse: int):
+    x = x.contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    n, c, h, w = x.shape
+    out = torch.empty_like(x)
+    L.check(_lib_for(x).dei2i_blit(n, c, h, w, _p(codes), inverse, _p(x), _p(out), _stream()), "blit")
+    return out
+
+
+class _Blit(torch.autograd.Function):
+    """y = B x, B the sample's dihedral element"""
+
+    @staticmethod
+    def forward(ctx, x, codes, host):
+        ctx.codes, ctx.host = codes, host                  # (host: the pinned source of the codes' upload, alive while the graph is)
+        return _blit_run(x, codes, 0)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _BlitInverse.apply(g, ctx.codes), None, None
+
+
+class _BlitInverse(torch.autograd.Function):
+    """B^T g = B^-1 g; its transpose is the forward"""
+
+    @staticmethod
+    def forward(ctx, g, codes):
+        ctx.codes = codes
+        return _blit_run(g, codes, 1)
+
+    @staticmethod
+    def backward(ctx, gg):
+        return _Blit.apply(gg, ctx.codes, None), None
+
+
 # Data-parallel stargan-v2 (stargan.Solver under parallel.attach_ddp): each rank holds rows [rank * n, (rank + 1) * n) of the global
 # batch, and the reference augments the whole global batch with one draw per function.  Inside ``diffaug_sharded(rank, world)`` the
 # draws are those of the global batch (utils.diffaug.draw_params(shard=...)) and only the rank's rows are uploaded and applied.
@@ -2021,17 +2059,25 @@ def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0, p=None):
     """One dei2i_diffaug_draw launch on the current stream: -> (tab, runs), ``tab`` a device int32 (len(runs), n, 8) table of struct
     dei2i_diffaug_rec for global rows [row0, row0 + n), ``runs`` the (has_color, cut_h, cut_w) list of utils.diffaug.draw_params.
     Nothing is read from the host RNG and nothing is uploaded.  ``p`` (a one-element fp32 device tensor in [0, 1]): the gated
-    draw dei2i_diffaug_draw_p instead -- each policy applies to a row with probability ``p``, read on the device by the launch."""
-    from .utils.diffaug import REC_FIELDS, policy_runs
-    names = policy_runs(policy)
-    if not 0 < len(names) <= L.DIFFAUG_MAX_RUNS:
-        raise ValueError(f"diff_augment with a device RNG takes 1..{L.DIFFAUG_MAX_RUNS} canonical-order runs; {policy!r} has {len(names)}")
+    draw dei2i_diffaug_draw_p instead -- each policy applies to a row with probability ``p``, read on the device by the launch.
+    A policy with blit runs (flip -> rot90): ``runs`` holds ``utils.diffaug.BLIT`` at their places and ``tab`` the records of the
+    other runs in order (``None``, and no launch, when there is none); ``blit_draw`` draws the codes, after this call."""
+    from .utils.diffaug import BLIT, REC_FIELDS, check_policy, is_blit_run, policy_runs
+    check_policy(policy, h, w)
+    whole = policy_runs(policy)
+    if not 0 < len(whole) <= L.DIFFAUG_MAX_RUNS:
+        raise ValueError(f"diff_augment with a device RNG takes 1..{L.DIFFAUG_MAX_RUNS} canonical-order runs; {policy!r} has {len(whole)}")
+    names = [run for run in whole if not is_blit_run(run)]
     bit = {"color": L.DIFFAUG_COLOR, "translation": L.DIFFAUG_TRANSLATION, "cutout": L.DIFFAUG_CUTOUT}
     flags, runs = 0, []
     for r, run in enumerate(names):
         flags |= sum(bit[name] for name in run) << (3 * r)
         cut = "cutout" in run
         runs.append(("color" in run, int(h * 0.5 + 0.5) if cut else 0, int(w * 0.5 + 0.5) if cut else 0))
+    affine = iter(runs)
+    runs = [BLIT if is_blit_run(run) else next(affine) for run in whole]
+    if not names:
+        return None, runs
     tab = torch.empty((len(names), n, REC_FIELDS), dtype=torch.int32, device=rng.device)
     lib = _lib_for(tab)
     if p is None:
@@ -2040,6 +2086,32 @@ def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0, p=None):
         L.check(lib.dei2i_diffaug_draw_p(rng.seed, _p(rng.counter), len(names), flags, n, int(row0), h, w,
                                          _p(_gate_word(p, rng.device, "diffaug_draw")), _p(tab), _stream()), "diffaug_draw_p")
     return tab, runs
+
+
+def blit_draw(rng: DiffAugRng, policy, n, row0=0, p=None):
+    """One dei2i_blit_draw launch on the current stream: -> a device int32 (blit runs, n) table, row b the codes f | k << 1 of the
+    b-th blit run of ``policy`` for global rows [row0, row0 + n) (the counter-word layout: include/dei2i_hip.h -- the run word is the
+    run's index in the whole list).  ``p``: the gated draw dei2i_blit_draw_p.  A policy without a blit run raises ValueError."""
+    from .utils.diffaug import is_blit_run, policy_runs
+    whole = policy_runs(policy)
+    if not 0 < len(whole) <= L.DIFFAUG_MAX_RUNS:
+        raise ValueError(f"diff_augment with a device RNG takes 1..{L.DIFFAUG_MAX_RUNS} canonical-order runs; {policy!r} has {len(whole)}")
+    bit = {"flip": L.BLIT_FLIP, "rot90": L.BLIT_ROT90}
+    flags = count = 0
+    for r, run in enumerate(whole):
+        if is_blit_run(run):
+            flags |= sum(bit[name] for name in run) << (2 * r)
+            count += 1
+    if not count:
+        raise ValueError(f"blit_draw: {policy!r} holds no flip or rot90")
+    codes = torch.empty((count, n), dtype=torch.int32, device=rng.device)
+    lib = _lib_for(codes)
+    if p is None:
+        L.check(lib.dei2i_blit_draw(rng.seed, _p(rng.counter), len(whole), flags, n, int(row0), _p(codes), _stream()), "blit_draw")
+    else:
+        L.check(lib.dei2i_blit_draw_p(rng.seed, _p(rng.counter), len(whole), flags, n, int(row0),
+                                      _p(_gate_word(p, rng.device, "blit_draw")), _p(codes), _stream()), "blit_draw_p")
+    return codes
 
 
 class AdaState:
@@ -2154,11 +2226,13 @@ def state_digest(tensors, rows_per_launch=None):
 
 def diff_augment(x, policy="", rng=None, p=None):
     """DiffAugment(x, policy) of utils/diffaug.py on an NCHW fp32 GPU image batch, one or two launches per canonical-order policy
-    run.  ``policy == ""`` returns ``x`` itself.  ``rng=None``: the same draws from the global CPU RNG as utils/diffaug.py, one
-    upload of the parameter table per call.  ``rng`` a ``DiffAugRng``: the table is drawn on the device by one more launch
-    (``diffaug_draw``) -- the CPU RNG is not touched, nothing is uploaded, and the call can be captured into a graph.
+    run (one per blit run: flip -> rot90, csrc/blit.hip).  ``policy == ""`` returns ``x`` itself.  ``rng=None``: the same draws from
+    the global CPU RNG as utils/diffaug.py, one upload of the parameter table per call.  ``rng`` a ``DiffAugRng``: the table is drawn
+    on the device by one more launch (``diffaug_draw``), and the codes of the blit runs by one more (``blit_draw``, after it) -- the
+    CPU RNG is not touched, nothing is uploaded, and the call can be captured into a graph.
     Inside ``diffaug_sharded`` ``x`` is one rank's rows of the global batch (above).  ``p`` (needs ``rng``): a one-element fp32 device
-    tensor, the probability with which each policy applies to a row (``diffaug_draw``); the apply launches are the same."""
+    tensor, the probability with which each policy applies to a row (``diffaug_draw``); the apply launches are the same.
+    An unknown policy name raises KeyError and rot90 on a non-square batch ValueError, before anything is drawn."""
     if p is not None and rng is None:
         raise ValueError("diff_augment: p gates the device-drawn table; it needs rng (a DiffAugRng)")
     if not policy:
@@ -2166,20 +2240,36 @@ def diff_augment(x, policy="", rng=None, p=None):
     _require_gpu(x, "diff_augment")
     if x.dim() != 4 or x.dtype != torch.float32:
         raise TypeError("diff_augment expects an NCHW fp32 image batch")
+    from .utils.diffaug import BLIT, check_policy, draw_params
     n, _, h, w = x.shape
+    check_policy(policy, h, w)
     if rng is not None:
         if rng.device != x.device:
             raise ValueError(f"diff_augment: the DiffAugRng lives on {rng.device}, the images on {x.device}")
-        tab, runs = diffaug_draw(rng, policy, n, h, w, row0=diffaug_shard[0] * n if diffaug_shard is not None else 0, p=p)
+        row0 = diffaug_shard[0] * n if diffaug_shard is not None else 0
+        tab, runs = diffaug_draw(rng, policy, n, h, w, row0=row0, p=p)
+        codes = blit_draw(rng, policy, n, row0=row0, p=p) if BLIT in runs else None
         host = None
     else:
-        from .utils.diffaug import draw_params
         rec, runs = draw_params(policy, n, h, w, shard=diffaug_shard)
+        blits = [r for r, run in enumerate(runs) if run == BLIT]
+        if blits:                                            # (the other runs' records, then one code word per sample: one upload)
+            import numpy as np
+            others = [r for r in range(len(runs)) if r not in blits]
+            rec = np.concatenate([rec[others].reshape(-1), rec[blits, :, 0].reshape(-1)])
         host = torch.empty(rec.shape, dtype=torch.int32, pin_memory=True)
         host.copy_(torch.from_numpy(rec))
         tab = host.to(x.device, non_blocking=True)
-    for i, run in enumerate(runs):
-        x = _DiffAug.apply(x, tab[i], run, 0, host)
+        if blits:
+            tab, codes = tab[:len(others) * n * 8].view(len(others), n, 8), tab[len(others) * n * 8:].view(len(blits), n)
+    affine = blit = 0
+    for run in runs:
+        if run == BLIT:
+            x = _Blit.apply(x, codes[blit], host)
+            blit += 1
+        else:
+            x = _DiffAug.apply(x, tab[affine], run, 0, host)
+            affine += 1
     return x
 
 

@@ -1,7 +1,9 @@
 """DiffAugment (Zhao et al. 2020, "Differentiable Augmentation for Data-Efficient GAN Training") as the reference applies it
 to the images the discriminator sees (utils/diffaug.py:9-76; call sites defectgan_model.py:200-203,266-270): policies
 'color' (brightness, saturation, contrast), 'translation' (random shift by up to 1/8 of the side, zero fill) and 'cutout'
-(a random half-size square set to zero), all differentiable w.r.t. the image.
+(a random half-size square set to zero), all differentiable w.r.t. the image.  Beyond the reference: 'flip' (mirror left-right)
+and 'rot90' (quarter turns), the pixel-blitting augmentations of Karras et al. 2020 that the integer translation lacked -- per
+sample one permutation of the pixels (csrc/blit.hip), in runs of their own (``policy_runs``).
 
 NCHW fp32 images.  The policy functions below are plain torch ops and define the semantics (the defectGAN model calls
 them); ``ops.diff_augment`` is the same map as fused HIP kernels (csrc/diffaug.hip), differentiable to any order, whose
@@ -67,15 +69,38 @@ def cutout(x, ratio=0.5):
     return x * (~hole).unsqueeze(1).to(x.dtype)
 
 
-POLICIES = {"color": (brightness, saturation, contrast), "translation": (translation,), "cutout": (cutout,)}
+def flip(x):
+    """mirror a sample left-right when its bit is 1 (the x-flip of Karras et al. 2020, one of the pixel-blitting augmentations)"""
+    f = _randint(0, 2, x.size(0), x)
+    return torch.where(f.unsqueeze(1) == 1, x.flip(3), x)
+
+
+def rot90(x):
+    """k quarter turns per sample, k uniform in {0, 1, 2, 3}: torch.rot90(x[i], k_i, dims=(1, 2)); square images only"""
+    k = torch.randint(0, 4, size=[x.size(0), 1, 1]).view(-1).tolist()          # (drawn on the host, as _randint draws)
+    return torch.stack([torch.rot90(x[i], k[i], dims=(1, 2)) for i in range(x.size(0))])
+
+
+POLICIES = {"color": (brightness, saturation, contrast), "translation": (translation,), "cutout": (cutout,), "flip": (flip,),
+            "rot90": (rot90,)}
+
+
+def check_policy(policy, h, w):
+    """-> the names of ``policy``; an unknown name raises KeyError and rot90 on a non-square image ValueError, before anything is
+    drawn"""
+    names = policy.split(",") if policy else []
+    for name in names:
+        if name not in POLICIES:
+            raise KeyError(f"DiffAugment policy [{name}] is not defined (color | translation | cutout | flip | rot90)")
+    if "rot90" in names and h != w:
+        raise ValueError(f"DiffAugment policy [rot90] needs square images; these are {h} x {w}")
+    return names
 
 
 def diff_augment(x, policy=""):
     if not policy:
         return x
-    for name in policy.split(","):
-        if name not in POLICIES:
-            raise KeyError(f"DiffAugment policy [{name}] is not defined (color | translation | cutout)")
+    for name in check_policy(policy, x.size(2), x.size(3)):
         for fn in POLICIES[name]:
             x = fn(x)
     return x.contiguous()
@@ -83,19 +108,24 @@ def diff_augment(x, policy=""):
 
 # ---- host half of the fused HIP op (ops.diff_augment, csrc/diffaug.hip) ----------------------------------------------------------
 CANONICAL = ("color", "translation", "cutout")
+BLIT_CANONICAL = ("flip", "rot90")          # the pixel-blitting policies: runs of their own kind (csrc/blit.hip), one code per sample
 REC_FIELDS = 8          # struct dei2i_diffaug_rec: a, b, k, beta (fp32), ty, tx, top, left (int32)
+BLIT = "blit"           # the entry of a blit run in the run list of draw_params / ops.diffaug_draw
+
+
+def is_blit_run(names):
+    return names[0] in BLIT_CANONICAL
 
 
 def policy_runs(policy):
-    """the policy list split into maximal runs in canonical order (color -> translation -> cutout), each launched as one operator;
-    an unknown name raises KeyError before anything is drawn"""
-    names = policy.split(",") if policy else []
-    for name in names:
-        if name not in POLICIES:
-            raise KeyError(f"DiffAugment policy [{name}] is not defined (color | translation | cutout)")
+    """the policy list split into maximal runs in canonical order (color -> translation -> cutout, or flip -> rot90: a blit run is
+    never merged with a run of the other kind), each launched as one operator; an unknown name raises KeyError before anything is
+    drawn"""
+    names = check_policy(policy, 0, 0)
     runs = []
     for name in names:
-        if runs and CANONICAL.index(name) > CANONICAL.index(runs[-1][-1]):
+        order = BLIT_CANONICAL if name in BLIT_CANONICAL else CANONICAL
+        if runs and runs[-1][-1] in order and order.index(name) > order.index(runs[-1][-1]):
             runs[-1].append(name)
         else:
             runs.append([name])
@@ -106,7 +136,9 @@ def draw_params(policy, n, h, w, shard=None):
     """Draw the per-sample parameters of ``policy`` for an (n, *, h, w) batch from the global CPU torch RNG, in the order and shapes
     of the policy functions above (one (n,1,1,1) float draw per color function, two (n,1,1) integer draws per translation / cutout).
     Returns (records, runs): records an int32 (len(runs), n, 8) array of struct dei2i_diffaug_rec (the four floats stored bitwise),
-    runs a list of (has_color, cut_h, cut_w) -- cut_h = cut_w = 0 when the run has no cutout.
+    runs a list of (has_color, cut_h, cut_w) -- cut_h = cut_w = 0 when the run has no cutout.  A blit run (flip -> rot90) draws one
+    (n,1,1) integer per policy; its entry in runs is ``BLIT`` and its records hold the code f | k << 1 of csrc/blit.hip in word 0,
+    zeros elsewhere.  rot90 on a non-square image raises ValueError before anything is drawn.
 
     ``shard=(rank, world)``: n is one rank's share of a global batch of n * world rows.  The parameters of the whole global batch are
     drawn, exactly as the unsharded call for n * world draws them (same RNG consumption), and rows [rank * n, (rank + 1) * n) are
@@ -115,11 +147,18 @@ def draw_params(policy, n, h, w, shard=None):
         rank, world = shard
         rec, meta = draw_params(policy, n * world, h, w)
         return np.ascontiguousarray(rec[:, rank * n:(rank + 1) * n]), meta
+    check_policy(policy, h, w)
     runs = policy_runs(policy)
     rec = np.zeros((len(runs), n, REC_FIELDS), dtype=np.int32)
     f = rec.view(np.float32)
     meta = []
     for r, names in enumerate(runs):
+        if is_blit_run(names):
+            for name in names:
+                draw = torch.randint(0, 2 if name == "flip" else 4, size=[n, 1, 1]).view(n).numpy().astype(np.int32)
+                rec[r, :, 0] |= draw if name == "flip" else draw << 1
+            meta.append(BLIT)
+            continue
         f[r, :, 0] = 1.0
         ch = cw = 0
         for name in names:

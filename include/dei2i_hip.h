@@ -367,6 +367,35 @@ int dei2i_diffaug_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t 
 int dei2i_diffaug_draw_p(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int H, int W,
                          const float* p_dev, dei2i_diffaug_rec* tab, dei2i_stream s);
 
+/* ---- the pixel-blitting policies (utils/diffaug.py: flip -> rot90; csrc/blit.hip) on fp32 NCHW images: per sample one element of
+ * the dihedral group, code = f | k << 1 -- f = 1 mirrors left-right, then k quarter turns as torch.rot90(x, k, dims=(2, 3)).
+ * codes_dev: N int32 words of device memory; the launch uses word & 7 and takes k = 0 when H != W, so no table, whatever it holds,
+ * moves a read or a write outside the two N*C*H*W buffers.  inverse != 0 applies each sample's inverse element ((1, k) when f = 1,
+ * (0, (4 - k) & 3) when f = 0): the adjoint of the forward, which is a permutation.  Even k copies rows (reversed or not; float4
+ * when W % 4 == 0 and both pointers are 16-byte aligned), odd k transposes 32 x 32 tiles through LDS; the pattern is uniform within
+ * a workgroup.  Deterministic, no atomics, one launch.  BAD_ARG: null pointers, N, C, H, W <= 0, N*C*H*W >= 2^40,
+ * C*H*W >= 2^31 (the limits of dei2i_diffaug), and src and dst that overlap (in place is not supported). */
+int dei2i_blit(int N, int C, int H, int W, const int* codes_dev, int inverse, const float* src, float* dst, dei2i_stream s);
+/* Fill codes[b][n] (blit runs x N words, b counting the blit runs of the list in order, n in [0, N)) on the device from
+ * Philox4x32-10: key = seed, counter words = (call low 32, call high 32, run | 3 << 16, row0 + n), run the run's index in the WHOLE
+ * run list of the policy (blocks 0..2 of that word belong to dei2i_diffaug_draw); f = x0 >> 31, k = mulhi(x1, 4).  run_flags: 2 bits
+ * per run of the whole list, run r at bits [2r, 2r + 2): the blit policies the run holds, 0 for a color / translation / cutout run
+ * (no row in the table); a policy that is absent leaves its bits 0.  One launch of one workgroup, no atomics; it leaves *counter_dev
+ * greater by exactly 1 under the ordering rule of dei2i_diffaug_draw, whose counter it shares: a diff_augment call with both kinds
+ * of run launches dei2i_diffaug_draw FIRST (it sees call) and dei2i_blit_draw SECOND (it sees call + 1); a call with blit runs only
+ * launches dei2i_blit_draw alone (call).  A pure function of (seed, call, run, row0 + n): rows [row0, row0 + N) are that slice of the
+ * whole-batch call.  BAD_ARG: null pointers, runs outside 1..DEI2I_DIFFAUG_MAX_RUNS, flag bits beyond the runs, no blit run, N <= 0,
+ * row0 < 0, row0 + N > 2^31, runs * N >= 2^24. */
+#define DEI2I_BLIT_FLIP 1
+#define DEI2I_BLIT_ROT90 2
+int dei2i_blit_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, int* codes, dei2i_stream s);
+/* The same table with a gate per row and policy: flip applies iff (x2 >> 8) * 2^-24 < *p_dev and rot90 iff (x3 >> 8) * 2^-24 <
+ * *p_dev, x2 and x3 of the same Philox block; a policy that does not apply leaves its bits 0.  p = 1 gives the table of
+ * dei2i_blit_draw bit for bit, p = 0 zeros only, and a row's f and k do not depend on its gates.  BAD_ARG: as dei2i_blit_draw, and a
+ * null p_dev. */
+int dei2i_blit_draw_p(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, const float* p_dev,
+                      int* codes, dei2i_stream s);
+
 /* ---- the controller of p (csrc/ada.hip; Karras et al. 2020: r_t = E[sign(D(real))] held at a target) ----
  * dei2i_ada_measure: one workgroup over n fp32 logits; pair_dev[0] = sum of (x > 0) - (x < 0), pair_dev[1] = n, two int64 words,
  * written, or added to when accumulate != 0.  NaN and +-0 count 0 towards the sum and 1 towards n.  Integer sums: exact and
