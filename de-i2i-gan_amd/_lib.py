@@ -1,176 +1,95 @@
-"""ctypes binding of libdei2i_hip.so (C ABI: include/dei2i_hip.h).  Fails loudly when the library is missing."""
+"""ctypes binding of libdei2i_hip.so, derived at import from its C ABI, include/dei2i_hip.h: every prototype -> SIGNATURES, every
+struct -> a ctypes.Structure, every integer `#define DEI2I_<NAME>` -> <NAME>.  Fails loudly when the header or the library is missing."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
+import re
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_longlong, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdei2i_hip.so")
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "dei2i_hip.h"))
 
-BF16, F32 = 0, 1
-ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
-PAD_ZERO, PAD_REFLECT = 0, 1
-DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT, DIFFAUG_MAX_RUNS = 1, 2, 4, 16
-BLIT_FLIP, BLIT_ROT90 = 1, 2
-PROF_GATHER_GEMM, PROF_WGRAD, PROF_HALO_CONV, PROF_HALO_FOLD = 0, 1, 2, 3
-
-
-class ConvDesc(Structure):
-    """struct dei2i_conv"""
-    _fields_ = [("dtype", c_int), ("N", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("Cout", c_int),
-                ("CinS", c_int), ("CoutS", c_int), ("kh", c_int), ("kw", c_int), ("stride", c_int), ("pad", c_int),
-                ("pad_mode", c_int), ("up", c_int)]
+# The header's whole type vocabulary; a token outside it raises (it never defaults to a pointer or an int).
+_SCALARS = {"int": c_int, "float": c_float, "double": c_double, "size_t": c_size_t, "int64_t": c_int64, "uint64_t": c_uint64,
+            "long long": c_longlong, "dei2i_stream": c_void_p}
+_POINTEES = {"void", "unsigned char"} | set(_SCALARS)            # what a plain pointer (-> c_void_p) may point at
+_WORDS = {word for base in _POINTEES for word in base.split()}
+# The descriptors a caller hands over one at a time with byref(): pointers to them are typed.  The other structs are rows of tables
+# that are passed by address (most live in device memory), so pointers to them are c_void_p like every other pointer.
+_BYREF_STRUCTS = {"dei2i_conv", "dei2i_pro", "dei2i_epi_norm"}
 
 
-class ProDesc(Structure):
-    """struct dei2i_pro: operand-path normalisation of a conv's input (fused conv + norm + act)"""
-    _fields_ = [("A", c_void_p), ("B", c_void_p), ("n_stride", c_int), ("slope", c_float), ("ring", c_void_p)]
+def _ctype(tokens, structs, where):
+    """The ctypes type of a C type given as tokens: descriptor pointer -> POINTER(Structure), const char* -> c_char_p, other
+    pointers -> c_void_p, scalars by value."""
+    words = [t for t in tokens if t not in ("const", "*")]
+    for t in words:
+        if t not in _WORDS and t not in structs:
+            raise ValueError(f"{where}: unknown type token {t!r}")
+    base, stars = " ".join(words), tokens.count("*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and base in structs and base in _BYREF_STRUCTS:
+        return POINTER(structs[base])
+    if stars == 1 and base == "char" and "const" in tokens:
+        return c_char_p
+    if stars >= 1 and (base in _POINTEES or base in structs):
+        return c_void_p
+    raise ValueError(f"{where}: unsupported type {' '.join(tokens)!r}")
 
 
-class EpiNormDesc(Structure):
-    """struct dei2i_epi_norm: the backward reductions of the norm layer in front of a conv, from that conv's dgrad epilogue"""
-    _fields_ = [("kind", c_int), ("up", c_int), ("act", c_int), ("group_images", c_int), ("x", c_void_p), ("mean", c_void_p),
-                ("rstd", c_void_p), ("gb", c_void_p), ("a", c_void_p), ("b", c_void_p), ("partial", c_void_p)]
+def _named(tokens, structs, where):
+    """(name, ctypes type) of a `type name` declarator given as tokens"""
+    if len(tokens) < 2 or not re.fullmatch(r"[A-Za-z_]\w*", tokens[-1]) or tokens[-1] in _WORDS | {"const"} or tokens[-1] in structs:
+        raise ValueError(f"{where}: no type or no name in {' '.join(tokens)!r}")
+    return tokens[-1], _ctype(tokens[:-1], structs, f"{where} {tokens[-1]}")
 
 
-class LabelMod(Structure):
-    """struct dei2i_label_mod: one SPADE module's entry in the batched label-path launches (csrc/label_path.hip)"""
-    _fields_ = [("gamma_weight", c_void_p), ("beta_weight", c_void_p), ("gamma_bias", c_void_p), ("beta_bias", c_void_p),
-                ("packed_fwd", c_void_p), ("packed_dgrad", c_void_p), ("gb", c_void_p), ("d_gamma_weight", c_void_p),
-                ("d_beta_weight", c_void_p), ("d_gamma_bias", c_void_p), ("d_beta_bias", c_void_p), ("C", c_int), ("in_off", c_int),
-                ("live", c_int), ("reserved", c_int)]
+def parse_header(text):
+    """C header text -> (constants {NAME: int}, structs {dei2i_x: Structure}, signatures {dei2i_f: (restype, argtypes)})"""
+    tokens = re.compile(r"\w+|\S").findall
+    constants, structs, signatures = {}, {}, {}
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+DEI2I_(\w+)[ \t]+(\S.*?)[ \t]*$", text, flags=re.M):
+        if not re.fullmatch(r"-?\d+|\(-?\d+\)", value):
+            raise ValueError(f"#define DEI2I_{name}: {value!r} is not an integer")
+        constants[name] = int(value.strip("()"))
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|typedef\s+void\s*\*\s*dei2i_stream\s*;|^\s*\}\s*$', " ", text, flags=re.M)
+
+    def struct(m):
+        fields = []
+        for decl in filter(None, map(str.strip, m[2].split(";"))):       # `type a, b, c` shares the first declarator's type
+            first, *more = map(str.strip, decl.split(","))
+            name, ctype = _named(tokens(first), structs, f"struct {m[1]} field")
+            for extra in more:
+                if not re.fullmatch(r"[A-Za-z_]\w*", extra):
+                    raise ValueError(f"struct {m[1]} field {name}: unsupported declarator {extra!r}")
+            fields += [(n, ctype) for n in [name] + more]
+        structs[m[1]] = type(m[1], (Structure,), {"_fields_": fields})
+        return " "
+
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", struct, text, flags=re.S)
+    *decls, tail = text.split(";")
+    if tail.strip():
+        raise ValueError(f"expected ';' after {tail.split()[-1]!r} at the end of the header")
+    for decl in filter(str.strip, decls):
+        m = re.match(r"\s*([\w\s*]+?)\b(dei2i_\w+)\s*\(([^()]*)\)\s*", decl)
+        if not m or m.end() != len(decl):
+            raise ValueError(f"{m[2] if m else 'header'}: expected ';' before {(decl[m.end():] if m else decl).split()[0]!r}")
+        params = [] if m[3].strip() in ("", "void") else m[3].split(",")
+        res = None if tokens(m[1]) == ["void"] else _ctype(tokens(m[1]), structs, f"{m[2]} return type")
+        signatures[m[2]] = (res, [_named(tokens(p), structs, f"{m[2]} parameter")[1] for p in params])
+    return constants, structs, signatures
 
 
-class AdamRec(Structure):
-    """struct dei2i_adam_rec"""
-    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64)]
-
-
-_P = c_void_p
-_CD = POINTER(ConvDesc)
-_PD = POINTER(ProDesc)
-_ED = POINTER(EpiNormDesc)
-
-# name -> (restype, argtypes); every symbol include/dei2i_hip.h declares
-SIGNATURES = {
-    "dei2i_version": (c_int, []),
-    "dei2i_init": (c_int, [c_int]),
-    "dei2i_error_string": (c_char_p, [c_int]),
-    "dei2i_set_option": (c_int, [c_char_p, c_int]),
-    "dei2i_packed_fwd_elems": (c_size_t, [_CD]),
-    "dei2i_wgrad_slab_elems": (c_size_t, [_CD]),
-    "dei2i_packed_dgrad_elems": (c_size_t, [_CD]),
-    "dei2i_pack_weight_fwd": (c_int, [_CD, _P, _P, _P]),
-    "dei2i_pack_weight_dgrad": (c_int, [_CD, _P, _P, _P]),
-    "dei2i_pack_weight_both": (c_int, [_CD, _P, _P, _P, _P]),
-    "dei2i_conv2d_out_shape": (None, [_CD, POINTER(c_int), POINTER(c_int)]),
-    "dei2i_conv2d_dgrad_shape": (None, [_CD, POINTER(c_int), POINTER(c_int)]),
-    "dei2i_conv2d_workspace_bytes": (c_size_t, [_CD]),
-    "dei2i_conv2d_fwd": (c_int, [_CD, _P, _P, _P, c_int, _P, _P, c_size_t, _P]),
-    "dei2i_conv2d_dgrad": (c_int, [_CD, _P, _P, _P, _P, c_size_t, _P]),
-    "dei2i_conv2d_dgrad_input": (c_int, [_CD, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "dei2i_quantize_fp8": (c_int, [c_size_t, _P, c_float, _P, _P]),
-    "dei2i_pack_weight_fwd_fp8": (c_int, [_CD, _P, _P, c_float, _P, _P, _P]),
-    "dei2i_conv2d_fp8_supported": (c_int, [_CD]),
-    "dei2i_conv2d_fwd_fp8": (c_int, [_CD, _P, _P, _P, _P, c_int, _P, _P]),
-    "dei2i_conv2d_wgrad_oihw": (c_int, [_CD, _P, _P, _P, c_size_t, _P, c_int, _P]),
-    "dei2i_fold_pad": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "dei2i_nchw_to_nhwc": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_nhwc_to_nchw": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_nchw_to_nhwc_resize": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_moments_chunks": (c_int, [c_int]),
-    "dei2i_moments_partial": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_bn_finalize_train": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P]),
-    "dei2i_bn_finalize_eval": (c_int, [c_int, _P, _P, _P, _P, c_float, _P, _P, _P]),
-    "dei2i_in_finalize": (c_int, [c_int, c_int, c_int, c_int, _P, c_float, _P, _P, _P]),
-    "dei2i_affine_act_fwd": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, c_int, _P, _P, c_float, _P]),
-    "dei2i_spade_act_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, c_float, _P]),
-    "dei2i_act_bwd": (c_int, [c_int, c_size_t, _P, _P, c_int, _P, _P]),
-    "dei2i_colsum_blocks": (c_int, [c_size_t]),
-    "dei2i_colsum": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P]),
-    "dei2i_bn_bwd_chunks": (c_int, [c_size_t]),
-    "dei2i_bn_bwd_partial": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P]),
-    "dei2i_bn_bwd_apply": (c_int, [c_int, c_int, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, _P]),
-    "dei2i_bn_sync_fwd_sums": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_bn_sync_fwd_finalize": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P]),
-    "dei2i_bn_sync_bwd_sums": (c_int, [c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P]),
-    "dei2i_bn_sync_bwd_apply": (c_int, [c_int, c_int, c_size_t, c_size_t, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
-    "dei2i_spade_bwd_partial": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, _P, _P, _P]),
-    "dei2i_spade_bwd_apply": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_float, _P, c_int, _P, _P, _P, _P, _P]),
-    "dei2i_compose_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "dei2i_compose_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "dei2i_nan_guard": (c_int, [c_int, c_size_t, _P, _P, _P]),
-    "dei2i_bce_logits_fwd": (c_int, [c_size_t, _P, _P, c_float, _P, _P]),
-    "dei2i_bce_logits_bwd": (c_int, [c_size_t, _P, _P, c_float, _P, _P, _P]),
-    "dei2i_l1_fwd": (c_int, [c_size_t, _P, _P, _P, _P]),
-    "dei2i_l1_bwd": (c_int, [c_size_t, _P, _P, _P, _P, _P, _P]),
-    "dei2i_mse_fwd": (c_int, [c_size_t, _P, _P, c_float, _P, _P]),
-    "dei2i_mse_bwd": (c_int, [c_size_t, _P, _P, c_float, _P, _P, _P, _P]),
-    "dei2i_cce_logits_fwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P]),
-    "dei2i_cce_logits_bwd": (c_int, [c_size_t, c_int, _P, _P, _P, _P, _P]),
-    "dei2i_noise_fwd": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P, _P]),
-    "dei2i_noise_bwd": (c_int, [c_int, c_size_t, c_int, _P, _P, _P, _P, c_int, _P]),
-    "dei2i_spectral_scratch_floats": (c_size_t, [c_int, c_int]),
-    "dei2i_spectral_fwd": (c_int, [c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P]),
-    "dei2i_spectral_bwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
-    "dei2i_fold_bn_weight": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P, _P]),
-    "dei2i_label_gb_packed_elems": (c_size_t, [c_int, c_int]),
-    "dei2i_label_gb_pack": (c_int, [_P, c_int, c_int, _P]),
-    "dei2i_label_gb_fwd": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
-    "dei2i_label_gb_dgrad": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
-    "dei2i_label_gb_wgrad": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
-    "dei2i_adam_step": (c_int, [_P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, _P]),
-    "dei2i_sgd_rmsprop_step": (c_int, [_P, c_int, c_int64, c_int, c_float, c_float, c_float, c_float, _P]),
-    "dei2i_adam_step_l2": (c_int, [_P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, _P]),
-    "dei2i_adam_step_dev": (c_int, [_P, c_int, c_int64, _P, _P, c_int, c_float, c_float, c_float, c_float, _P]),
-    "dei2i_adam_step_l2_dev": (c_int, [_P, c_int, c_int64, _P, _P, c_int, c_float, c_float, c_float, c_float, c_float, _P]),
-    "dei2i_grad_sumsq_blocks": (c_int, [c_int64]),
-    "dei2i_grad_sumsq": (c_int, [_P, c_int, c_int64, _P, _P]),
-    "dei2i_grad_clip_finalize": (c_int, [_P, c_int, c_float, c_float, _P, _P]),
-    "dei2i_adam_step_clip": (c_int, [_P, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, _P, c_int, c_float, _P]),
-    "dei2i_adam_step_clip_dev": (c_int, [_P, c_int, c_int64, _P, _P, c_int, c_float, c_float, c_float, _P, c_int, c_float, _P]),
-    "dei2i_state_digest_blocks": (c_int, [c_int64]),
-    "dei2i_state_digest": (c_int, [_P, c_int, c_int64, c_int64, _P, c_int, _P, _P]),
-    "dei2i_index_advance": (c_int, [_P, _P]),
-    "dei2i_ema_lerp": (c_int, [_P, c_int, c_int64, c_float, _P]),
-    "dei2i_ema_lerp_dev": (c_int, [_P, c_int, c_int64, _P, _P, c_int, _P]),
-    "dei2i_diffaug_partial_floats": (c_size_t, [c_int]),
-    "dei2i_diffaug": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "dei2i_diffaug_draw": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, c_int, c_int, _P, _P]),
-    "dei2i_diffaug_draw_p": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_blit": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
-    "dei2i_blit_draw": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, _P, _P]),
-    "dei2i_blit_draw_p": (c_int, [c_uint64, _P, c_int, c_uint64, c_int, c_int, _P, _P, _P]),
-    "dei2i_ada_measure": (c_int, [_P, c_int64, _P, c_int, _P]),
-    "dei2i_ada_apply": (c_int, [_P, c_int64, _P, _P, c_int, c_float, c_float, c_float, _P]),
-    "dei2i_mask_draw": (c_int, [c_uint64, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P]),
-    "dei2i_mask_fill": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, POINTER(c_int64), _P, _P, _P]),
-    "dei2i_mask_fill_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
-    "dei2i_embed_draw": (c_int, [c_uint64, _P, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, _P, _P]),
-    "dei2i_embed_gather": (c_int, [c_int64, c_int, _P, _P, c_int64, _P, _P]),
-    "dei2i_prof_enable": (c_int, [c_int, c_int]),
-    "dei2i_prof_collect": (c_int, [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]),
-    "dei2i_prof_collect_timed": (c_int, [c_int, POINTER(c_int64), POINTER(c_double)]),
-    "dei2i_conv2d_fused_supported": (c_int, [_CD, c_int]),
-    "dei2i_conv2d_stats_chunks": (c_int, [_CD]),
-    "dei2i_conv2d_fwd_fused": (c_int, [_CD, _P, _P, _P, c_int, _P, _PD, _P, _P]),
-    "dei2i_conv2d_wgrad_pro_supported": (c_int, [_CD]),
-    "dei2i_conv2d_wgrad_oihw_pro": (c_int, [_CD, _P, _P, _P, c_size_t, _P, c_int, _PD, _P]),
-    "dei2i_ring_pixels": (c_size_t, [c_int, c_int]),
-    "dei2i_conv2d_ring_supported": (c_int, [_CD]),
-    "dei2i_conv2d_dgrad_norm_supported": (c_int, [_CD]),
-    "dei2i_conv2d_dgrad_norm_chunks": (c_int, [_CD]),
-    "dei2i_conv2d_dgrad_input_norm": (c_int, [_CD, _P, _P, _P, _ED, _P]),
-    "dei2i_avgpool2_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_avgpool2_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    "dei2i_spade_bwd_border": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P]),
-    "dei2i_conv2d_fwd_ring": (c_int, [_CD, _P, _P, _P, _P, c_int, _P, _P, _P]),
-    "dei2i_affine_act_img_fwd": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P]),
-    "dei2i_spade_prep": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "dei2i_affine_act_stats_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P]),
-    "dei2i_launch_counts": (c_int, [POINTER(c_int64), c_int]),
-    "dei2i_launch_counts_reset": (None, []),
-    "dei2i_kernel_name": (c_char_p, [c_int]),
-}
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(f"the C ABI header {HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(HEADER_PATH) as _f:
+    CONSTANTS, STRUCTS, SIGNATURES = parse_header(_f.read())
+globals().update(CONSTANTS)          # BF16, ACT_*, PAD_*, ERR_*, DIFFAUG_*, BLIT_*, PROF_*, EMBED_MAX_LABEL_NC, DIGEST_MAX_ROWS
+ConvDesc, ProDesc, EpiNormDesc, LabelMod, AdamRec, DiffAugRec = (
+    STRUCTS["dei2i_" + n] for n in ("conv", "pro", "epi_norm", "label_mod", "adam_rec", "diffaug_rec"))
+ADAM_REC_WORDS = ctypes.sizeof(AdamRec) // 8          # int64 words in one row of a device table of dei2i_adam_rec
 
 _lib = None
 

@@ -330,7 +330,7 @@ extern "C" int dei2i_state_digest_blocks(int64_t max_n) { return (int)table_grid
 extern "C" int dei2i_state_digest(const dei2i_adam_rec* table_dev, int count, int64_t max_n, int64_t row0, uint64_t* partial_dev,
                                   int accumulate, uint64_t* out_dev, dei2i_stream s) {
   // (a word's index and a row's place share one 64-bit key: 32 bits each)
-  if (!table_dev || count <= 0 || count > 65535 || max_n <= 0 || max_n > ((int64_t)1 << 32) || row0 < 0 || row0 + count > ((int64_t)1 << 32) ||
+  if (!table_dev || count <= 0 || count > DEI2I_DIGEST_MAX_ROWS || max_n <= 0 || max_n > ((int64_t)1 << 32) || row0 < 0 || row0 + count > ((int64_t)1 << 32) ||
       !partial_dev || !out_dev)
     return DEI2I_ERR_BAD_ARG;
   const dim3 grid = table_grid(max_n, 4, 512, count);

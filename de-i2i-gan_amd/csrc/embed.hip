@@ -107,7 +107,7 @@ extern "C" int dei2i_embed_draw(uint64_t seed, uint64_t* counter_dev, int N, int
                                 dei2i_stream s) {
   if (!counter_dev || !labels || !table || !index_out || !invalid_dev || N <= 0 || row0 < 0 || num_embeds <= 0 || table_total < 0)
     return DEI2I_ERR_BAD_ARG;
-  if ((long long)row0 + N > (1ll << 31) || label_nc < 1 || label_nc > 16 || num_embeds > (1 << 28)) return DEI2I_ERR_BAD_ARG;
+  if ((long long)row0 + N > (1ll << 31) || label_nc < 1 || label_nc > DEI2I_EMBED_MAX_LABEL_NC || num_embeds > (1 << 28)) return DEI2I_ERR_BAD_ARG;
   hipLaunchKernelGGL(embed_draw_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)s, (unsigned long long)seed,
                      reinterpret_cast<unsigned long long*>(counter_dev), N, (unsigned)row0, label_nc, num_embeds, labels, table,
                      (long long)table_total, index_out, reinterpret_cast<unsigned long long*>(invalid_dev));

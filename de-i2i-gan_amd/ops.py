@@ -2190,8 +2190,8 @@ def state_digest(tensors, rows_per_launch=None):
     if not tensors:
         raise ValueError("state_digest needs at least one tensor")
     per = DIGEST_ROWS_PER_LAUNCH if rows_per_launch is None else int(rows_per_launch)
-    if not 0 < per <= 65535:
-        raise ValueError(f"state_digest: |rows_per_launch {rows_per_launch}| is invalid (1..65535)")
+    if not 0 < per <= L.DIGEST_MAX_ROWS:
+        raise ValueError(f"state_digest: |rows_per_launch {rows_per_launch}| is invalid (1..{L.DIGEST_MAX_ROWS})")
     rows, hold = [], []
     device = tensors[0].device
     for k, t in enumerate(tensors):
@@ -2211,7 +2211,7 @@ def state_digest(tensors, rows_per_launch=None):
         hold.append(t)                                       # (a copy lives until its launch is queued)
         rows.append((t.data_ptr() if nbytes else 0, 0, 0, 0, nbytes // 4))
     lib = _lib_for(tensors[0])
-    host = torch.empty((len(rows), 5), dtype=torch.int64, pin_memory=True)
+    host = torch.empty((len(rows), L.ADAM_REC_WORDS), dtype=torch.int64, pin_memory=True)
     host.copy_(torch.tensor(rows, dtype=torch.int64))
     table = host.to(device, non_blocking=True)
     out = torch.empty(1, dtype=torch.int64, device=device)
@@ -2219,7 +2219,7 @@ def state_digest(tensors, rows_per_launch=None):
         count = min(per, len(rows) - row0)
         max_n = max(1, max(r[4] for r in rows[row0:row0 + count]))
         partial = torch.empty(lib.dei2i_state_digest_blocks(max_n) * count, dtype=torch.int64, device=device)
-        L.check(lib.dei2i_state_digest(c_void_p(table.data_ptr() + 40 * row0), count, max_n, row0, _p(partial), int(row0 > 0),
+        L.check(lib.dei2i_state_digest(c_void_p(table[row0].data_ptr()), count, max_n, row0, _p(partial), int(row0 > 0),
                                        _p(out), _stream()), "state_digest")
     return out
 
@@ -2374,7 +2374,7 @@ def mask_fill(imgs, keep, shift, patch, token=None):
 # counter-word layout: include/dei2i_hip.h) and gathers them -- two launches that can be captured into a graph, and every replay
 # draws other embeddings.
 # --------------------------------------------------------------------------------------------------------------
-EMBED_MAX_LABEL_NC = 16
+EMBED_MAX_LABEL_NC = L.EMBED_MAX_LABEL_NC
 
 
 def embed_pack(embeddings, label_nc, embed_nc):

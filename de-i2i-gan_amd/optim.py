@@ -55,7 +55,7 @@ class _PointerTable:
 
     def upload(self, into=None):
         """-> the rows on the device, through pinned memory and stream-ordered: in the first rows of ``into``, or a new tensor"""
-        host = torch.empty((len(self.rows), 5), dtype=torch.int64, pin_memory=True)
+        host = torch.empty((len(self.rows), L.ADAM_REC_WORDS), dtype=torch.int64, pin_memory=True)
         host.copy_(torch.tensor(self.rows, dtype=torch.int64))
         if into is None:
             return host.to(self.device, non_blocking=True)
@@ -288,7 +288,7 @@ class FusedAdam(_FusedOptimizer, _GraphCapture):
             if not params:
                 continue
             steps = {self.state[p]["step"] for p in params if self.state.get(p)}
-            reserve[gi] = [(torch.empty((len(params), 5), dtype=torch.int64, device=params[0].device),
+            reserve[gi] = [(torch.empty((len(params), L.ADAM_REC_WORDS), dtype=torch.int64, device=params[0].device),
                             _HyperTable(params[0].device, 0)) for _ in range(len(steps) + 1)]
         self._graph_reserve = reserve
 
@@ -530,7 +530,7 @@ class EmaGroup(_GraphCapture):
     # ---- graph capture ------------------------------------------------------------------------------------------------
     def graph_reserve(self):
         """Before a capture: a device pointer table per launch and the weight rows, outside the graph's memory pool."""
-        tables = [torch.empty((len(pairs), 5), dtype=torch.int64, device=self.device) for pairs, _ in self._launches()]
+        tables = [torch.empty((len(pairs), L.ADAM_REC_WORDS), dtype=torch.int64, device=self.device) for pairs, _ in self._launches()]
         self._graph_reserve = {"table": tables, "weights": [_WeightRows(self.device)]}
 
     def _update_captured(self):

@@ -15,8 +15,12 @@ values per sample).
 rng=ops.DiffAugRng)``, whose table is filled on the device by a counter-based generator with the formulas of ``draw_params``
 (csrc/diffaug.hip dei2i_diffaug_draw) -- the same distributions, not the reference's draws, and nothing a graph capture would
 freeze.  ``policy_runs`` serves both."""
+import ctypes
+
 import numpy as np
 import torch
+
+from .. import _lib
 
 
 def _rand(n, x):
@@ -109,7 +113,7 @@ def diff_augment(x, policy=""):
 # ---- host half of the fused HIP op (ops.diff_augment, csrc/diffaug.hip) ----------------------------------------------------------
 CANONICAL = ("color", "translation", "cutout")
 BLIT_CANONICAL = ("flip", "rot90")          # the pixel-blitting policies: runs of their own kind (csrc/blit.hip), one code per sample
-REC_FIELDS = 8          # struct dei2i_diffaug_rec: a, b, k, beta (fp32), ty, tx, top, left (int32)
+REC_FIELDS = ctypes.sizeof(_lib.DiffAugRec) // 4       # 32-bit words of a dei2i_diffaug_rec: a, b, k, beta (fp32), ty, tx, top, left (int32)
 BLIT = "blit"           # the entry of a blit run in the run list of draw_params / ops.diffaug_draw
 
 

@@ -33,6 +33,10 @@ typedef void* dei2i_stream;   /* hipStream_t */
 #define DEI2I_ERR_BAD_ARG (-2)
 #define DEI2I_ERR_WORKSPACE (-3)
 
+/* argument limits that the host code on both sides of this ABI checks */
+#define DEI2I_EMBED_MAX_LABEL_NC 16   /* dei2i_embed_draw: the combination table has 1 << label_nc rows */
+#define DEI2I_DIGEST_MAX_ROWS 65535   /* dei2i_state_digest: rows per launch (the grid's y extent) */
+
 /* nn.Conv2d geometry (architecture.py:51-56,95-100,228-233,320-337; normalization.py:17-22;
  * discriminator.py:60-90).  `up` = 1 fuses the preceding nn.Upsample(scale_factor=2) (architecture.py:203). */
 typedef struct dei2i_conv {
@@ -306,7 +310,7 @@ int dei2i_adam_step_clip_dev(const dei2i_adam_rec* table_dev, int count, int64_t
  *   digest = sum_k sum_i splitmix64(splitmix64((k << 32) | i) + w[k][i]),  splitmix64(x): x += 0x9E3779B97F4A7C15;
  *   x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^= x >> 31
  * Row r of the table is tensor k = row0 + r: rec.p its memory (4-byte aligned), rec.n its count of 32-bit words (<= 2^32, like
- * max_n); rec.g / m / v are not read.  One launch over the table, grid = dei2i_state_digest_blocks(max_n) x count (count <= 65535),
+ * max_n); rec.g / m / v are not read.  One launch over the table, grid = dei2i_state_digest_blocks(max_n) x count (count <= DEI2I_DIGEST_MAX_ROWS),
  * every workgroup storing its partial to partial_dev[row * blocks + block] (count * blocks words of scratch; no clearing, no
  * atomics), then one workgroup: out_dev[0] = (accumulate ? out_dev[0] : 0) + the sum of the partials.  A long list goes out in
  * several calls on one stream: row0 = the rows before, accumulate = 1 from the second call on; partial_dev may be the same. */
@@ -451,7 +455,7 @@ int dei2i_mask_fill_bwd(int N, int C, int H, int W, int patch, const int* shift_
  * *invalid_dev (one 64-bit word) grows by the number of invalid rows of the call.  One launch of one workgroup, no global atomics;
  * it leaves *counter_dev greater by exactly 1 (the ordering rule of dei2i_diffaug_draw holds, for invalid_dev too).  The draw is a
  * pure function of (seed, call, e, row0 + n, the row's labels).  BAD_ARG: null pointers, N <= 0, row0 < 0, row0 + N > 2^31,
- * label_nc outside 1..16, num_embeds <= 0 or > 2^28, table_total < 0.
+ * label_nc outside 1..DEI2I_EMBED_MAX_LABEL_NC, num_embeds <= 0 or > 2^28, table_total < 0.
  *
  * dei2i_embed_gather: out[r][:] = bank[index[r]][:] for r < rows (rows = N * num_embeds), zeros for an index outside
  * [0, bank_rows) -- no address is formed from such an index.  float4 copies when embed_nc % 4 == 0 and bank and out are 16-byte

@@ -13,7 +13,7 @@ from test_diffaug_dev_gpu import draw_reference
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SEED = 0x5DEECE66D1234567
-BAD_ARG = -2
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
 MIXED = "flip,color,rot90"          # runs [flip] [color] [rot90]: blit runs at index 0 and 2
 
 

@@ -13,7 +13,7 @@ import blit_reference as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-BAD_ARG = -2                       # include/dei2i_hip.h: DEI2I_ERR_BAD_ARG
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
 GUARD = 64
 SENTINEL = -12345.0
 _P = ctypes.c_void_p

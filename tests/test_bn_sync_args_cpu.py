@@ -4,7 +4,8 @@ import ctypes
 
 import pytest
 
-BAD_ARG = -2
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
+
 P = ctypes.c_void_p(64)            # any non-null address: the checks below fail before a pointer is used
 
 

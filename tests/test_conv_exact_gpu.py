@@ -40,7 +40,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SENTINEL = 12288.0             # exact in bf16 and fp32; no integer sum of a case reaches it
-BAD_ARG = -2                   # DEI2I_ERR_BAD_ARG (include/dei2i_hip.h)
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
 OPTION_DEFAULTS = {"halo16": 1, "halo16_fold": 1, "dgrad_s2_ring": 1}      # the library's defaults (include/dei2i_hip.h; it has no getter)
 
 

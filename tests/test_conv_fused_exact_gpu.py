@@ -70,7 +70,7 @@ from test_conv_exact_gpu import (BAD_ARG, DEV, _counts, act_ref, cdiv, guarded, 
                                  ternary, where_report)
 
 gpu = pytest.mark.gpu
-WORKSPACE = -3                 # DEI2I_ERR_WORKSPACE (include/dei2i_hip.h)
+from de_i2i_gan_amd._lib import ERR_WORKSPACE as WORKSPACE
 LIMIT = float(2 ** 24)
 
 

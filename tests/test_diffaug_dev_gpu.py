@@ -19,7 +19,7 @@ from helpers import make_opt
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
 SEED = 0x5DEECE66D1234567          # (checked below: at 8x8, N = 4096 every translation and cutout value occurs)
-BAD_ARG = -2                       # include/dei2i_hip.h: DEI2I_ERR_BAD_ARG
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
 POLICIES = ["color", "translation", "cutout", "color,translation,cutout", "translation,color", "color,color"]
 CANONICAL = ("color", "translation", "cutout")
 

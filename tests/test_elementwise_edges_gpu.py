@@ -27,7 +27,7 @@ gpu = pytest.mark.gpu
 pytestmark = gpu
 DEV = "cuda:0"
 GUARD = 64
-BAD_ARG = -2                                                          # DEI2I_ERR_BAD_ARG (include/dei2i_hip.h)
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
 SENTINEL = {"bf16": 0x7FC1, "f32": 0x7FC0ABCD}                        # quiet NaNs with a payload
 
 

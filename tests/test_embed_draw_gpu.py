@@ -15,7 +15,7 @@ import embed_reference as R
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SEED = 0x5DEECE66D1234567
-BAD_ARG = -2                       # include/dei2i_hip.h: DEI2I_ERR_BAD_ARG
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
 LABEL_NC = 6
 NS, EMBEDS, WIDTHS = (1, 2, 300), (1, 3, 4, 5, 9), (1, 5, 768)
 

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-BAD_ARG = -2                     # include/dei2i_hip.h: DEI2I_ERR_BAD_ARG
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
 SENT = 4096.0                    # exact in bf16 and fp32, and no result of the integer cases reaches it
 GUARD = 64                       # elements on either side of a guarded buffer (a multiple of 8: the payload stays 16-byte aligned)
 

@@ -18,7 +18,7 @@ from helpers import make_opt
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SEED = 0x5DEECE66D1234567
-BAD_ARG = -2                       # include/dei2i_hip.h: DEI2I_ERR_BAD_ARG
+from de_i2i_gan_amd._lib import ERR_BAD_ARG as BAD_ARG
 M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 LOW = np.uint64(0xFFFFFFFF)
 
