@@ -19,6 +19,7 @@
 #include "common.h"
 #include "geom.h"
 #include "launch.h"
+#include "tile_prims.h"
 
 namespace dei2i {
 
@@ -42,13 +43,6 @@ template <> struct Mma<float> {
 
 DEI2I_D u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p); }
 DEI2I_D u32x4 zero16() { u32x4 z = {0u, 0u, 0u, 0u}; return z; }
-
-// bijective XCD-aware remap of the linear workgroup id (cdna_hip_programming.md T1)
-DEI2I_D int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
 
 // ------------------------------------------------------------------------------------------------
 // gather GEMM:  out[m][n] = act( sum_k  gather(src)[m][k] * wgt[n][k] + bias[n] )
@@ -160,13 +154,13 @@ __global__ __launch_bounds__(256) void gather_gemm_kernel(const DescPack pack, c
 #pragma unroll
     for (int i = 0; i < RA; ++i) {
       const int row = r0 + 32 * i;
-      *reinterpret_cast<u32x4*>(base + row * 128 + ((kv ^ ((row >> 1) & 7)) << 4)) = areg[i];
+      *reinterpret_cast<u32x4*>(base + row * 128 + ((kv ^ chunk_swz128(row)) << 4)) = areg[i];
     }
     unsigned char* bb = base + BM * 128;
 #pragma unroll
     for (int j = 0; j < RB; ++j) {
       const int row = r0 + 32 * j;
-      *reinterpret_cast<u32x4*>(bb + row * 128 + ((kv ^ ((row >> 1) & 7)) << 4)) = breg[j];
+      *reinterpret_cast<u32x4*>(bb + row * 128 + ((kv ^ chunk_swz128(row)) << 4)) = breg[j];
     }
   };
 
@@ -190,12 +184,12 @@ __global__ __launch_bounds__(256) void gather_gemm_kernel(const DescPack pack, c
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int row = wm * WTM + i * 32 + lr;
-        a[i] = *reinterpret_cast<const u32x4*>(ab + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
+        a[i] = *reinterpret_cast<const u32x4*>(ab + row * 128 + ((chunk ^ chunk_swz128(row)) << 4));
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int row = wn * WTN + j * 32 + lr;
-        b[j] = *reinterpret_cast<const u32x4*>(bb + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
+        b[j] = *reinterpret_cast<const u32x4*>(bb + row * 128 + ((chunk ^ chunk_swz128(row)) << 4));
       }
     };
     load_frags(0, af[0], bf[0]);
@@ -330,13 +324,6 @@ __global__ void splitk_finalize_kernel(const DescPack pack, const float* __restr
   }
 }
 
-// LDS swizzle for the pixel-major wgrad tiles read with ds_read_b64_tr_b16: a 32-lane half reads 4 consecutive
-// rows x 64 bytes; spread the 4 rows over the four 64-byte quarters of the 256-byte bank row.
-template <int ROWB> DEI2I_D int tr_swz(int row) {
-  if constexpr (ROWB % 256 == 0) return (row & 3) << 6;
-  else return ((row >> 1) & 1) << 6;    // 128-byte rows: rows r and r+2 alias, flip the 64-byte half
-}
-
 // ------------------------------------------------------------------------------------------------
 // wgrad:  dw[co][k] = sum_m dy[m][co] * gather(src)[m][k]
 // The pixel range is split over gridDim.z; split z stores its partial to slab z (dw + z*slab_elems, plain stores) and
@@ -457,20 +444,14 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const GatherDesc g, const T*
           const int colb = (wm * WTM + i * 32 + 16 * tr_cohalf + 4 * tr_p) * 2;
           const int o0 = row_lo * ROWB_A + (colb ^ tr_swz<ROWB_A>(row_lo));
           const int o1 = (row_lo + 4) * ROWB_A + (colb ^ tr_swz<ROWB_A>(row_lo + 4));
-          s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ab + o0));
-          s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ab + o1));
-          u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-          a[i].x = l2.x; a[i].y = l2.y; a[i].z = h2.x; a[i].w = h2.y;
+          a[i] = tr_read(ab, o0, o1);
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           const int colb = (wn * WTN + j * 32 + 16 * tr_cohalf + 4 * tr_p) * 2;
           const int o0 = row_lo * ROWB_B + (colb ^ tr_swz<ROWB_B>(row_lo));
           const int o1 = (row_lo + 4) * ROWB_B + (colb ^ tr_swz<ROWB_B>(row_lo + 4));
-          s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(bb + o0));
-          s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(bb + o1));
-          u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-          b[j].x = l2.x; b[j].y = l2.y; b[j].z = h2.x; b[j].w = h2.y;
+          b[j] = tr_read(bb, o0, o1);
         }
       };
 #pragma unroll

@@ -11,8 +11,10 @@
 // multiple of 64 (every 64-element k-step then lies inside one tap: tap / channel offset are wave-uniform scalars).
 //
 // LDS image: [row][128 B] with the 16-byte chunk c of row r stored at slot c ^ ((r>>1)&7) (conflict-free
-// ds_read_b128 fragments).  LDS-DMA writes lane l of a wave-instruction at base + 16*l, i.e. row (l>>3), slot (l&7) of
-// an 8-row group, so each lane FETCHES chunk (l&7) ^ ((r>>1)&7) of its row: the swizzle lives on the source address.
+// ds_read_b128 fragments) -- the chunk_swz128 of tile_prims.h, written out below: as calls, hipcc allocates this
+// kernel's registers differently.  LDS-DMA (glds16, the builtin form) writes lane l of a wave-instruction at
+// base + 16*l, i.e. row (l>>3), slot (l&7) of an 8-row group, so each lane FETCHES chunk (l&7) ^ ((r>>1)&7) of its
+// row: the swizzle lives on the source address.
 // Rows that contribute zeros (M / N edge, zero padding) fetch from a zero page.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,23 +23,9 @@
 #include "common.h"
 #include "geom.h"
 #include "launch.h"
+#include "tile_prims.h"
 
 namespace dei2i {
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];   // zero-initialised device memory
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-DEI2I_D void glds16(const void* gptr, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_t*)gptr, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
-
-DEI2I_D int xcd_remap2(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
 
 template <int BM, int BN, int WM, int WN, int STAGES>
 __global__ __launch_bounds__(512) void gather_gemm_v2_kernel(const DescPack pack, const bf16_t* __restrict__ src,
@@ -62,7 +50,7 @@ __global__ __launch_bounds__(512) void gather_gemm_v2_kernel(const DescPack pack
 
   const GatherDesc& g = pack.d[blockIdx.y];
   const bf16_t* __restrict__ wgt = wgt_base + pack.woff[blockIdx.y];
-  const int bid = xcd_remap2(blockIdx.x, gridDim.x);
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_n = bid % tiles_n, tile_m = bid / tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   if (m0 >= g.M) return;
@@ -197,11 +185,7 @@ __global__ __launch_bounds__(512) void gather_gemm_v2_kernel(const DescPack pack
   issue(0, 0);
   if (AHEAD > 1 && nk > 1) issue(1, 1);
   for (int it = 0; it < nk; ++it) {
-    if (AHEAD > 1 && it + 1 < nk) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LA + LB) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (AHEAD > 1 && it + 1 < nk) wait_vm<LA + LB>(); else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     if (it + AHEAD < nk) issue((it + AHEAD) % STAGES, it + AHEAD);
     compute(it % STAGES);

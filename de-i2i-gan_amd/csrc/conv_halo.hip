@@ -10,8 +10,10 @@
 //
 //   k-step order : 64-channel slice outer, tap inner (weights are packed [Cout][tap][Cs]: k = tap*Cs + slice*64)
 //   LDS          : halo[2] (2 x 44,032 B) | weight ring STAGES x BN x 128 B | halo source-offset table
-//   LDS image    : 128-byte rows, 16-byte chunk c of row r at slot c ^ ((r>>1)&7) (conflict-free ds_read_b128);
-//                  LDS-DMA lands lane-linear, so the swizzle is applied to the SOURCE chunk each lane fetches
+//   LDS image    : 128-byte rows, 16-byte chunk c of row r at slot c ^ ((r>>1)&7) (conflict-free ds_read_b128) -- the
+//                  chunk_swz128 of tile_prims.h, written out below: as calls, hipcc allocates this kernel's registers
+//                  differently; LDS-DMA (glds16, the builtin form) lands lane-linear, so the swizzle is applied to the
+//                  SOURCE chunk each lane fetches
 //   waves        : 8 (4 x 2): wave (wm, wn) owns tile rows 2wm, 2wm+1 (64 pixels) x BN/2 output channels
 //   halo pixel   : output (py, px), tap (ty, tx) reads halo pixel (py + dy(ty), px + dx(tx)), dy = ty for ys = +1 and
 //                  th-1-ty for ys = -1 (dgrad: the tap sign flip is the kernel flip, geom.h)
@@ -22,31 +24,15 @@
 #include "common.h"
 #include "geom.h"
 #include "launch.h"
+#include "tile_prims.h"
 
 namespace dei2i {
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page_halo[256];
-
-typedef __attribute__((address_space(3))) void lds_void_h;
-typedef __attribute__((address_space(1))) const void gbl_void_h;
-
-DEI2I_D void glds16h(const void* gptr, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_h*)gptr, (lds_void_h*)lds_wave_base, 16, 0, 0);
-}
-
-DEI2I_D int xcd_remap_h(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
 
 constexpr int HALO_TH = 8, HALO_TW = 32;
 constexpr int HALO_GROUPS = 43;                       // 8-pixel LDS-DMA groups per halo slice (344 >= 10*34 pixels)
 constexpr int HALO_BYTES = HALO_GROUPS * 8 * 128;     // 44,032
 constexpr int HALO_HL = 6;                            // halo LDS-DMA instructions per wave per slice (48 >= 43 groups)
 constexpr int HALO_STAGES = 4;                        // weight-ring depth
-
-template <int N> DEI2I_D void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // FP8: the operands are e4m3 bytes and the descriptor / pointers describe them as PAIRS (a "bf16" tensor with half the
 // channels), so every address, LDS image and DMA pattern is unchanged; a 16-byte fragment then holds 16 k-values and
@@ -88,7 +74,7 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
 
-  const int bid = xcd_remap_h(blockIdx.x, gridDim.x);
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_n = bid % tiles_n, tile_m = bid / tiles_n;
   const int tiles_x = g.Wo / HALO_TW, tiles_y = g.Ho / HALO_TH;
   const int img = tile_m / (tiles_x * tiles_y);
@@ -129,7 +115,7 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
 
   // ---- per-lane LDS-DMA roles ----
   const int lrow = lane >> 3, lslot = lane & 7;
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page_halo);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
   int h_off[HALO_HL], h_group[HALO_HL];
 #pragma unroll
   for (int j = 0; j < HALO_HL; ++j) {
@@ -162,7 +148,7 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
       if constexpr (PRO) {
         if (h_off[j] < -1) p = pro.ring + ((size_t)(unsigned)(-2 - h_off[j]) + (unsigned)ci0);
       }
-      glds16h(p, hb + h_group[j] * 1024);
+      glds16(p, hb + h_group[j] * 1024);
     }
   };
   // PRO: in-place normalisation of a landed halo slice.  Vector v = tid + 512 j is LDS slot (tid & 7) of halo pixel
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
 #pragma unroll
     for (int j = 0; j < LB; ++j) {
       const bf16_t* p = b_ptr[j] != nullptr ? b_ptr[j] + kb : zero;
-      glds16h(p, sb + (j * 64 + wave * 8) * 128);
+      glds16(p, sb + (j * 64 + wave * 8) * 128);
     }
     if (++is_tap == ntaps) { is_tap = 0; ++is_slice; }
   };
@@ -329,7 +315,7 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
     if (j + 1 >= nk) wait_vm<0>();
     else if (j + 2 < nk) { if (halo_young) wait_vm<LB + HALO_HL>(); else wait_vm<LB>(); }
     else { if (halo_young) wait_vm<HALO_HL>(); else wait_vm<0>(); }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
   };
   // C(j): the 16 MFMAs, with this wave's LDS-DMA issue in the gaps (an MFMA holds the vector issue 8 of its 32 cycles;
@@ -360,7 +346,7 @@ __global__ __launch_bounds__(512) void halo_conv_kernel(const GatherDesc g, cons
   __builtin_amdgcn_s_barrier();                          // halo 0 and weights(0) complete for every wave
   if constexpr (PRO) {
     transform(0, 0, 6);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();                        // slice 0 normalised for every wave
   }
   if (grp == 1) __builtin_amdgcn_s_barrier();            // group 1 starts one phase late

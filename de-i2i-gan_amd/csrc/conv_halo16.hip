@@ -11,7 +11,7 @@
 //   LDS       : halo[2] of (16+2) x (32+2) pixels x 32 channels (2 x 39 KB) | weight ring STAGES x BN x 64 B | offset table
 //   DMA       : 8 KB of weights + 4.3 KB of halo per k-step = 12.3 instructions ~ 790 cycles: under the MFMA issue time
 //   fragments : 8 pixel blocks + 4 channel blocks per wave and k-step (12 KB of LDS reads per 32 MFMAs; 16 KB before)
-//   LDS image : 64-byte rows; 16-byte chunk c of row r sits at slot c ^ (((r >> 2) & 1) << 1) -- every ds_read_b128 of 16
+//   LDS image : 64-byte rows; 16-byte chunk c of row r sits at slot c ^ chunk_swz64(r) (tile_prims.h) -- every ds_read_b128 of 16
 //               consecutive rows x 4 k-groups is conflict-free at ANY starting row (all lane groups of the instruction
 //               see 16 distinct (row & 3, slot) pairs), so the tap-shifted pixel fragments never conflict (the 128-byte
 //               rows of conv_halo.hip lose 5.9 % of their cycles there)
@@ -28,32 +28,16 @@
 #include "common.h"
 #include "geom.h"
 #include "launch.h"
+#include "tile_prims.h"
 
 namespace dei2i {
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page_h16[256];
-
-typedef __attribute__((address_space(3))) void lds_void_h16;
-typedef __attribute__((address_space(1))) const void gbl_void_h16;
-
-DEI2I_D void glds16x(const void* gptr, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_h16*)gptr, (lds_void_h16*)lds_wave_base, 16, 0, 0);
-}
-
-DEI2I_D int xcd_remap_h16(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
 
 constexpr int H16_TH = 16, H16_TW = 32;
 constexpr int H16_GROUPS = 39;                        // 16-pixel LDS-DMA groups per halo slice (624 >= 18*34 pixels)
 constexpr int H16_HBYTES = H16_GROUPS * 1024;         // 39,936
 constexpr int H16_HL = 5;                             // halo LDS-DMA instructions per wave per slice (40 >= 39 groups)
 
-template <int N> DEI2I_D void wait_vm16() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> DEI2I_D void lgkm_wait() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-// LDS reads the compiler does not track (no automatic s_waitcnt: every use needs a hand-placed lgkm_wait)
+// LDS reads the compiler does not track (no automatic s_waitcnt: every use needs a hand-placed wait_lgkm)
 template <int OFF> DEI2I_D u32x4 lds_read128_asm(int addr) {
   u32x4 v;
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
@@ -64,8 +48,6 @@ DEI2I_D int lds_read32_asm(int addr) {
   asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr) : "memory");
   return v;
 }
-DEI2I_D int sw16(int row) { return ((row >> 2) & 1) << 1; }
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 DEI2I_D f32x2 bf16x2_unpack(uint32_t u) { return f32x2{__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; }
 
@@ -149,7 +131,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
 
-  const int bid = xcd_remap_h16(blockIdx.x, gridDim.x);
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_n = bid % tiles_n, tile_m = bid / tiles_n;
   const int tiles_x = g.Wo / H16_TW, tiles_y = g.Ho / H16_TH;
   const int img = tile_m / (tiles_x * tiles_y);
@@ -186,7 +168,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
 
   // ---- per-lane LDS-DMA roles: one instruction = 16 rows x 64 B; lane l -> row (l >> 2), slot (l & 3) ----
   const int lrow = lane >> 2, lslot = lane & 3;
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page_h16);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
   int h_off[H16_HL], h_group[H16_HL];
 #pragma unroll
   for (int j = 0; j < H16_HL; ++j) {
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
     const int pix = grp * 16 + lrow;
     const int o = htab[pix];
     h_group[j] = grp;
-    const int so = (lslot ^ sw16(pix)) << 3;
+    const int so = (lslot ^ chunk_swz64(pix)) << 3;
     h_off[j] = o >= 0 ? o + so : (o == -1 ? -1 : o - so);
   }
   const int rg = BN == 128 ? wave : (wave & 3);        // 16-row group of the weight stage this wave fetches
@@ -203,7 +185,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
   {
     const int r = rg * 16 + lrow;
     const int n = n0 + r;
-    b_ptr = n < wrows ? wgt + (size_t)n * g.K + ((lslot ^ sw16(r)) << 3) : nullptr;
+    b_ptr = n < wrows ? wgt + (size_t)n * g.K + ((lslot ^ chunk_swz64(r)) << 3) : nullptr;
   }
 
   const int ntaps = __builtin_amdgcn_readfirstlane(lth * ltw);
@@ -219,8 +201,8 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       for (int j = 0; j < H16_HL; ++j) {
         const int pix = h_group[j] * 16 + lrow;
         const int o = htab[par * HTAB + pix];
-        const bf16_t* p = o >= 0 ? src + ((size_t)(unsigned)(o + ((lslot ^ sw16(pix)) << 3)) + (unsigned)ci0) : zero;
-        glds16x(p, hb + h_group[j] * 1024);
+        const bf16_t* p = o >= 0 ? src + ((size_t)(unsigned)(o + ((lslot ^ chunk_swz64(pix)) << 3)) + (unsigned)ci0) : zero;
+        glds16(p, hb + h_group[j] * 1024);
       }
     } else {
       const int ci0 = slice << 5;
@@ -228,7 +210,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       for (int j = 0; j < H16_HL; ++j) {
         const bf16_t* p = h_off[j] >= 0 ? src + ((size_t)(unsigned)h_off[j] + (unsigned)ci0) : zero;
         if (h_off[j] < -1) p = zring + ((size_t)(unsigned)(-2 - h_off[j]) + (unsigned)ci0);
-        glds16x(p, hb + h_group[j] * 1024);
+        glds16(p, hb + h_group[j] * 1024);
       }
     }
   };
@@ -242,7 +224,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       kb = is_tap * g.Cs + (is_slice << 5);
     }
     const bf16_t* p = b_ptr != nullptr ? b_ptr + kb : zero;
-    glds16x(p, ring + stage * B_STAGE + rg * 1024);
+    glds16(p, ring + stage * B_STAGE + rg * 1024);
     if (++is_tap == ntaps) { is_tap = 0; ++is_slice; }
   };
 
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
 #pragma unroll
   for (int j = 0; j < CB; ++j) {
     const int row = wn * WTN + j * 16 + l16;
-    b_addr[j] = row * 64 + ((kg ^ sw16(row)) << 4);
+    b_addr[j] = row * 64 + ((kg ^ chunk_swz64(row)) << 4);
   }
   // FOLD: this wave's ring block (wave-uniform kind: 0 none, 1 top row, 2 bottom row, 3 left column, 4 right column)
   int ring_kind = 0, ring_pix0 = 0;
@@ -311,7 +293,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       ring_live = ring_kind == 1 ? ld_ty == 0 : (ring_kind == 2 ? ld_ty == 2 : (ring_kind == 3 ? ld_tx == 0 : (ring_kind == 4 && ld_tx == 2)));
       if (ring_live) {
         const int pix = ring_pix0 + ld_toff;
-        ring_frag = *reinterpret_cast<const u32x4*>(hb + pix * 64 + ((kg ^ sw16(pix)) << 4));
+        ring_frag = *reinterpret_cast<const u32x4*>(hb + pix * 64 + ((kg ^ chunk_swz64(pix)) << 4));
       }
     }
 #pragma unroll
@@ -377,7 +359,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
         const int ty = t / 3, tx = t % 3;
         ring_live = (ring_kind == 1 && ty == 0) || (ring_kind == 2 && ty == 2) || (ring_kind == 3 && tx == 0) || (ring_kind == 4 && tx == 2);
         const int pix = ring_live ? ring_pix0 + (tap_off(t) >> 6) : 0;
-        ring_frag = lds_read128_asm<0>(par + pix * 64 + ((kg ^ sw16(pix)) << 4));
+        ring_frag = lds_read128_asm<0>(par + pix * 64 + ((kg ^ chunk_swz64(pix)) << 4));
       }
     };
     // (the opaque asm statements below keep per-tap copies of loop-invariant addresses -- 9 weight pointers, 5 table
@@ -389,13 +371,13 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       const bf16_t* bp = b_src;
       asm volatile("" : "+v"(bp));
       const int kb = (tapw * g.Cs + (slicew << 5)) * b_live;
-      glds16x(bp + kb, ring + stage * B_STAGE + rg * 1024);
+      glds16(bp + kb, ring + stage * B_STAGE + rg * 1024);
     };
     // a wave's halo piece jp = 16-pixel group 8 * jp + wave (mod 39): the pixel's source offset is read back from the offset
     // table when the piece is issued (five per-lane offsets -- or the 64-bit pointers the compiler makes of them -- would
     // not fit beside the accumulators and two fragment sets)
     const int hl_addr = (int)(reinterpret_cast<unsigned char*>(htab) - smem) + lrow * 4;
-    const int so_lane = (lslot ^ sw16(lrow)) << 3;      // (group bases are multiples of 16 pixels: the swizzle bit is the lane's)
+    const int so_lane = (lslot ^ chunk_swz64(lrow)) << 3;      // (group bases are multiples of 16 pixels: the swizzle bit is the lane's)
     auto piece_group = [&](int jp) -> int {
       int gq = jp * 8 + wave;
       if (gq >= H16_GROUPS) gq -= H16_GROUPS;
@@ -410,7 +392,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       const int ci0 = slicew << 5;
       const bf16_t* p = o >= 0 ? src + ((size_t)(unsigned)(o + so_lane) + (unsigned)ci0) : zero;
       if (o < -1) p = zring + ((size_t)(unsigned)(-2 - o + so_lane) + (unsigned)ci0);
-      glds16x(p, halo + (slicew & 1) * H16_HBYTES + piece_group(jp) * 1024);
+      glds16(p, halo + (slicew & 1) * H16_HBYTES + piece_group(jp) * 1024);
     };
     // 4 MFMAs: pixel blocks a[0..3] (accumulators i0..i0+3) x channel block jj
     auto mfma4 = [&](const u32x4* a, int i0, int jj) {
@@ -426,13 +408,13 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       int po[H16_HL];
 #pragma unroll
       for (int jp = 0; jp < H16_HL; ++jp) po[jp] = read_piece_off(jp);
-      lgkm_wait<0>();
+      wait_lgkm<0>();
 #pragma unroll
       for (int jp = 0; jp < H16_HL; ++jp) issue_halo_piece(0, jp, po[jp]);
     }
 #pragma unroll
     for (int s2 = 0; s2 < STAGES - 1; ++s2) issue_w(s2, 0, s2);
-    wait_vm16<STAGES - 3>();
+    wait_vm<STAGES - 3>();
     __builtin_amdgcn_s_barrier();
     read_a(al, 0, tap_off(0));
     read_ring(0, 0);
@@ -459,10 +441,10 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       // ---- H0(j): rows 0,1 multiply (groups by channel block jj), rows 2,3 of this k-step are fetched
       read_a1(ah, 2, 0, soff);
       __builtin_amdgcn_sched_barrier(0);
-      lgkm_wait<2>();                                     // all of al', ring' and bc'[0..2] are in; bc'[3] and ah0 may be in flight
+      wait_lgkm<2>();                                     // all of al', ring' and bc'[0..2] are in; bc'[3] and ah0 may be in flight
 #pragma unroll
       for (int jj = 0; jj < CB; ++jj) {
-        if (jj == CB - 1) lgkm_wait<4>();                 // bc'[3] is in (ah0..3 may be in flight)
+        if (jj == CB - 1) wait_lgkm<4>();                 // bc'[3] is in (ah0..3 may be in flight)
         __builtin_amdgcn_sched_barrier(0);
         mfma4(al, 0, jj);
         if constexpr (FOLD) {
@@ -476,11 +458,11 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       }
       if (grp == 0) {
         constexpr int NH = T == 7 ? 3 : 4 + (T == 0 ? 0 : T == 1 ? 1 : T == 2 ? 2 : T == 3 ? 3 : T == 4 ? 4 : T == 5 ? 4 : T == 6 ? 3 : 1);
-        if (j + STAGES - 2 >= nk) wait_vm16<0>();
-        else if (has_halo) wait_vm16<NH>();
-        else wait_vm16<4>();
+        if (j + STAGES - 2 >= nk) wait_vm<0>();
+        else if (has_halo) wait_vm<NH>();
+        else wait_vm<4>();
         // (tap 8: these were the last reads of this slice's halo buffer, which the DMA refills after the next barrier)
-        if constexpr (T == 8) lgkm_wait<0>();
+        if constexpr (T == 8) wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -496,7 +478,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       read_a1(al, 0, 0, soff_n);
       read_a1(al, 0, 1, soff_n);
       __builtin_amdgcn_sched_barrier(0);
-      lgkm_wait<NP + 2>();                                // ah0..3 are in
+      wait_lgkm<NP + 2>();                                // ah0..3 are in
 #pragma unroll
       for (int jj = 0; jj < CB; ++jj) {
         __builtin_amdgcn_sched_barrier(0);
@@ -509,7 +491,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
         __builtin_amdgcn_sched_barrier(0);
         if (jj == 0) {
           if constexpr (NP) {
-            lgkm_wait<4>();                               // the piece offset (oldest of this half's reads) is in
+            wait_lgkm<4>();                               // the piece offset (oldest of this half's reads) is in
             if (has_halo) issue_halo_piece(sl + 1, T, piece_off);
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -520,9 +502,9 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       }
       if (grp == 1) {
         constexpr int NH = T == 7 ? 4 : 5 + (T == 0 ? 1 : T == 1 ? 2 : T == 2 ? 3 : T == 3 ? 4 : T == 4 ? 5 : T == 5 ? 4 : T == 6 ? 3 : 1);
-        if (j + STAGES - 1 >= nk) wait_vm16<0>();
-        else if (has_halo) wait_vm16<NH>();
-        else wait_vm16<5>();
+        if (j + STAGES - 1 >= nk) wait_vm<0>();
+        else if (has_halo) wait_vm<NH>();
+        else wait_vm<5>();
         __builtin_amdgcn_s_barrier();
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -542,7 +524,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       kstep(std::integral_constant<int, 7>{}, sl);
       kstep(std::integral_constant<int, 8>{}, sl);
       // (register copies at the loop's back-edge must not meet a fragment register whose read is still in flight)
-      lgkm_wait<0>();
+      wait_lgkm<0>();
       __builtin_amdgcn_sched_barrier(0);
     }
   } else {
@@ -574,10 +556,10 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
       // the next slice's halo went out in C(tap 1): while it is younger than weights(j+1) it may stay in flight -- but not at the
       // slice's last tap, whose barrier is the last one before M(next slice, tap 0) reads it (short tap grids: S2)
       const bool halo_young = tap >= 2 && tap <= STAGES - 1 && tap <= ntaps - 2 && slice + 1 < nslices;
-      if (j + STAGES - 2 >= nk) wait_vm16<0>();
-      else if (halo_young) wait_vm16<(STAGES - 3) * LB + H16_HL>();
-      else wait_vm16<(STAGES - 3) * LB>();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (j + STAGES - 2 >= nk) wait_vm<0>();
+      else if (halo_young) wait_vm<(STAGES - 3) * LB + H16_HL>();
+      else wait_vm<(STAGES - 3) * LB>();
+      wait_lgkm<0>();
       __builtin_amdgcn_s_barrier();
     };
     auto phase_c = [&](int j) {
@@ -615,7 +597,7 @@ __global__ __launch_bounds__(512) void halo16_conv_kernel(const GatherDesc g, co
     issue_halo(0);
     for (int s2 = 0; s2 < STAGES - 2; ++s2) issue_b(s2);
     issue_b(STAGES - 2);                                  // (the slot of k-step 0 would sit in "C(-1)")
-    wait_vm16<(STAGES - 2) * LB>();                       // everything older than weights(1): halo 0 and weights(0)
+    wait_vm<(STAGES - 2) * LB>();                       // everything older than weights(1): halo 0 and weights(0)
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();           // group 1 starts one phase late
   #pragma unroll 1

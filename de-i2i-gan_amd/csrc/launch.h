@@ -95,6 +95,24 @@ hipError_t gather_gemm_multi(int dtype, const GatherDesc* descs, const long long
 // One wgrad slab: the packed [Cout][K] gradient with the row count rounded up to 8, so the kernels' 8-row store
 // groups need no per-row guard (the rows beyond Cout are never read).
 static inline long long wgrad_slab_elems(int co_rows, int K) { return (long long)((co_rows + 7) & ~7) * K; }
+// The split plan of the slab-writing wgrad launchers (wgrad_v2, wgrad_halo, wgrad_thin): `want` splits of `units` work units
+// (pixel chunks / half-tiles), clamped to the slabs that fit in capacity_elems; every split takes `per` units, which leaves
+// `zs` non-empty splits (the grid's split extent and *nsplit_out).  false: not even one slab fits.  How many splits a kernel
+// wants is its launcher's own policy.
+struct WgradSplitPlan {
+  long long slab_elems;
+  int splits;             // `want` after the clamp
+  int per, zs;
+};
+static inline bool wgrad_split_plan(int co_rows, int K, size_t capacity_elems, int want, int units, WgradSplitPlan& p) {
+  p.slab_elems = wgrad_slab_elems(co_rows, K);
+  p.splits = want;
+  if ((size_t)p.slab_elems * p.splits > capacity_elems) p.splits = (int)(capacity_elems / (size_t)p.slab_elems);
+  if (p.splits < 1) return false;
+  p.per = (units + p.splits - 1) / p.splits;
+  p.zs = (units + p.per - 1) / p.per;
+  return true;
+}
 // dw holds up to capacity_elems floats; split z writes slab z, *nsplit_out slabs to be summed by wgrad_reduce_unpack
 // (deterministic).
 hipError_t wgrad_gemm(int dtype, const GatherDesc& g, const void* src, const void* dy, int co_rows, int ldy, float* dw,

@@ -18,17 +18,12 @@
 #include "common.h"
 #include "geom.h"
 #include "launch.h"
+#include "tile_prims.h"
 
 namespace dei2i {
 
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page_thin[256];
-
-typedef __attribute__((address_space(3))) void lds_void_tc;
-typedef __attribute__((address_space(1))) const void gbl_void_tc;
-
-DEI2I_D void glds16tc(const void* gptr, unsigned char* lds_wave_base) {
-  glds16_asm(gptr, lds_wave_base);      // (common.h: hipcc must not see the LDS write, or it drains the ring)
-}
+// (both kernels issue their LDS-DMA through glds16_asm / glds16_asm_s, tile_prims.h: hipcc must not see the LDS write, or it
+// drains the halo prefetch -- the counted wait_vm and the barrier at the top of each tile are what orders it)
 
 constexpr int TC_TH = 8, TC_TW = 32, TC_N = 64;
 constexpr int TC_PAD_TAP = (int)0x80000000;      // tap-table sentinel (real offsets can be negative: dgrad walks taps backwards)
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(512) void thin_cin_conv_kernel(const GatherDesc g, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cb = wave & 1, rp = wave >> 1;
   const int lr = lane & 31, lh = lane >> 5;
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page_thin);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
   const int ntaps = g.th * g.tw;
 
   const int hwd = (TC_TW - 1) * g.sw + g.tw, hht = (TC_TH - 1) * g.sh + g.th;
@@ -75,7 +70,7 @@ __global__ __launch_bounds__(512) void thin_cin_conv_kernel(const GatherDesc g, 
         const int x = bound_coord(hx0 + hx, g.Wl, g.pad_mode);
         if ((y | x) >= 0) ptr = src + ((size_t)((img * g.Hs + (y >> g.up)) * g.Ws + (x >> g.up))) * 8;
       }
-      glds16tc(ptr, halo + buf * halo_bytes + grp * 1024);
+      glds16_asm(ptr, halo + buf * halo_bytes + grp * 1024);
     }
   };
 
@@ -117,8 +112,8 @@ __global__ __launch_bounds__(512) void thin_cin_conv_kernel(const GatherDesc g, 
     // my share of this tile's halo has landed.  vmcnt counts stores too, in issue order: the four output stores of the
     // previous tile are younger than the halo loads and stay in flight (waiting for them would serialise every tile
     // behind its own HBM write latency)
-    if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    if (it == 0) wait_vm<0>();
+    else wait_vm<4>();
     __syncthreads();                                                 // ... everyone's; the other buffer is free
     const int tn = t + gridDim.x;
     if (tn < ntiles) issue_halo((it + 1) & 1, tn);
@@ -158,7 +153,7 @@ __global__ __launch_bounds__(512) void thin_cin_conv_kernel(const GatherDesc g, 
         pk.y = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
         *reinterpret_cast<u32x2*>(wst + (i * 32 + lr) * TC_SROW + (8 * q + 4 * lh) * 2) = pk;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     {
       const int img = t / tiles_img;
       const int rem = t - img * tiles_img;
@@ -218,16 +213,14 @@ hipError_t thin_cin_conv(const GatherDesc& g, const void* src, const void* wgt, 
 constexpr int TO_MAXCO = 8;
 constexpr int TO_MAXG = 9;                         // LDS-DMA pieces per wave and tile (7x7: 34 groups x 2 planes = 68 -> 9 per wave)
 
-DEI2I_D int sw_to(int row) { return ((row >> 2) & 1) << 1; }
-
 // Round 3 form: 16x16x32 MFMAs (A = 16 weight rows of which <= 8 are live, B = 16 pixels x 32 channels).  The 32x32x16 form this
 // replaces spent a 32-row A operand on 8 live rows (75 % of the matrix work wasted: the 7x7 input gradient of the stem ran 196
 // MFMAs of 32 cycles per 32 pixels) and re-read the weight fragment from LDS for every MFMA in every wave -- the 3x3 heads were
 // LDS-bound at twice their MFMA time.  Here a tap of a 32-pixel tile row is 4 MFMAs of 16 cycles on 4 fragment reads, the <= 9-tap
 // weights (18 fragments) live in registers for the whole launch (WREG), the 49-tap ones stream one fragment per (tap, k-block).
-//   halo in LDS : two PLANES (channels 0..31 | 32..63) of [pixel][64 B] rows, 16-byte chunk c of row r at slot c ^ (((r >> 2) & 1)
-//                 << 1) -- conv_halo16.hip's image: a ds_read_b128 of 16 consecutive pixels x 4 k-groups is conflict-free at any
-//                 tap shift; one LDS-DMA piece = 16 pixels of one plane
+//   halo in LDS : two PLANES (channels 0..31 | 32..63) of [pixel][64 B] rows, 16-byte chunk c of row r at slot c ^ chunk_swz64(r)
+//                 (tile_prims.h) -- conv_halo16.hip's image: a ds_read_b128 of 16 consecutive pixels x 4 k-groups is conflict-free
+//                 at any tap shift; one LDS-DMA piece = 16 pixels of one plane
 //   D           : lane (px = l16, kg) holds channels 4kg .. 4kg+3 of its pixel: lanes kg < 2 store 8 bytes each
 template <bool WREG>
 __global__ __launch_bounds__(512) void thin_cout_conv_kernel(const GatherDesc g, const bf16_t* __restrict__ src,
@@ -242,7 +235,7 @@ __global__ __launch_bounds__(512) void thin_cout_conv_kernel(const GatherDesc g,
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // tile row of this wave
   const int l16 = lane & 15, kg = lane >> 4;
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page_thin);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
   const int ntaps = g.th * g.tw;
   const int wrow_bytes = g.K * 2;
   const int plane_bytes = halo_bytes >> 1;
@@ -272,7 +265,7 @@ __global__ __launch_bounds__(512) void thin_cout_conv_kernel(const GatherDesc g,
     const int grp = q >> 1, p = grp * 16 + (lane >> 2);
     const int hy = p / hwd, hx = p - hy * hwd;
     hyx[i] = (q < npieces && p < npix) ? ((hy << 16) | hx) : -1;
-    coff[i] = (q & 1) * 32 + (((lane & 3) ^ sw_to(p)) << 3);           // channel offset of this lane's 16-byte chunk
+    coff[i] = (q & 1) * 32 + (((lane & 3) ^ chunk_swz64(p)) << 3);           // channel offset of this lane's 16-byte chunk
     asm volatile("" : "+v"(hyx[i]), "+v"(coff[i]));
   }
   const bool fast = g.pad_mode == PAD_REFLECT;
@@ -302,7 +295,7 @@ __global__ __launch_bounds__(512) void thin_cout_conv_kernel(const GatherDesc g,
           const int x = bound_coord(hx0 + (hyx[i] & 0xffff), g.Wl, g.pad_mode);
           if ((y | x) >= 0) ptr = ibase + (unsigned)((((y >> g.up) * g.Ws + (x >> g.up)) << 6) + coff[i]);
         }
-        glds16tc(ptr, halo + dst);
+        glds16_asm(ptr, halo + dst);
       }
     }
   };
@@ -334,22 +327,22 @@ __global__ __launch_bounds__(512) void thin_cout_conv_kernel(const GatherDesc g,
     const int tn = t + gridDim.x;
     const unsigned char* hb = halo;
     if (nbuf == 2) {                                                 // halo of tile t+1 streams in under tile t
-      if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (two output stores per tile stay in flight)
-      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      if (it == 0) wait_vm<0>();                                     // (two output stores per tile stay in flight)
+      else wait_vm<2>();
       __syncthreads();
       if (tn < ntiles) issue_halo((it + 1) & 1, tn);
       hb = halo + (it & 1) * halo_bytes;
     } else {                                                         // 7x7: one 68 KB halo buffer next to 50 KB of weights
       __syncthreads();                                               // everyone is done with the previous tile
       issue_halo(0, t);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
       __syncthreads();
     }
 
     typedef __attribute__((ext_vector_type(4))) float acc4_t;
     acc4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     auto tap_mfma = [&](int pix, const u32x4& w0, const u32x4& w1) {
-      const int ad = pix * 64 + ((kg ^ sw_to(pix)) << 4);             // columns 0..15 of the tile row; 16..31 at +1024 (pix + 16: same swizzle bit)
+      const int ad = pix * 64 + ((kg ^ chunk_swz64(pix)) << 4);             // columns 0..15 of the tile row; 16..31 at +1024 (pix + 16: same swizzle bit)
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb) {
         const u32x4 a0 = *reinterpret_cast<const u32x4*>(hb + ad + pb * 1024);

@@ -25,15 +25,9 @@
 #include "common.h"
 #include "geom.h"
 #include "launch.h"
+#include "tile_prims.h"
 
 namespace dei2i {
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page_hw[256];
-
-typedef __attribute__((address_space(3))) void lds_void_hw;
-typedef __attribute__((address_space(1))) const void gbl_void_hw;
-
-DEI2I_D void glds16hw(const void* gptr, unsigned char* lds_wave_base) { glds16_asm(gptr, lds_wave_base); }      // (common.h)
 
 constexpr int HW_TH = 4, HW_TW = 32;                  // half-tile: 128 pixels
 constexpr int HW_HH = HW_TH + 2, HW_HWD = HW_TW + 2;  // 6 x 34 halo
@@ -41,20 +35,12 @@ constexpr int HW_HPIX = HW_HH * HW_HWD;               // 204
 constexpr int HW_HGROUPS = 26;                        // 8-pixel DMA groups (208 >= 204)
 constexpr int HW_HPAD = HW_HGROUPS * 8;                // 208 halo pixel rows per stage
 
-// 256-byte rows: spread 4 consecutive rows over the four 64-byte quarters; 128-byte rows: rows r and r+2 alias, flip
-// the 64-byte half (the tr-read swizzles of conv_gemm.hip)
-template <int ROWB> DEI2I_D int hw_swz(int row) {
-  if constexpr (ROWB == 256) return (row & 3) << 6;
-  else return ((row >> 1) & 1) << 6;
-}
-
 // BCO x BCI = 128 x 64 (Cout >= 96) or 64 x 128 (Cout <= 64): 8 waves = (BCO/32) x (BCI/32) blocks, 9 taps each;
 // 64 x 64 with the taps split over NTG = 2 wave groups for 64-channel inputs (the 64 -> 4 heads: one live co block)
 // PRO: the conv's input was normalised + activated on the operand path in the forward pass (ConvPro, geom.h; the
 // normalised tensor z was never written), so the same transform is applied here to every landed input halo, in place in
 // LDS, before its nine taps are read: one extra pass over 26 KB and one extra barrier per half-tile.
-template <int N> DEI2I_D void hw_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
+// LDS-DMA through glds16_asm / glds16_asm_s (tile_prims.h): the wait_vm and barriers of the ring below are all that orders it.
 template <int BCO, int BCI, int NTG, bool PRO = false>
 __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, const bf16_t* __restrict__ src,
                                                          const bf16_t* __restrict__ dy, const int co_rows, const int ldy,
@@ -85,7 +71,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
   const int ntiles = g.N * tiles_img;
   const int tbeg = split * tiles_per_split;
   const int tend = min(ntiles, tbeg + tiles_per_split);
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page_hw);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
 
   // ---- LDS-DMA roles ----
   // dy: one instruction = 4 pixel rows x 256 B: lane l -> row (l>>4), 16-byte slot (l&15); 32 instructions per tile
@@ -118,7 +104,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
   for (int j = 0; j < NA; ++j) {
     const int rgrp = (j * 8 + wave) * RPI_A;
     const int r = rgrp + lane / SPR_A;                                    // pixel of the half-tile: (r>>5, r&31)
-    const int off = ((lane % SPR_A) * 16) ^ hw_swz<ROWB_A>(r);            // source byte offset that belongs at this slot
+    const int off = ((lane % SPR_A) * 16) ^ tr_swz<ROWB_A>(r);            // source byte offset that belongs at this slot
     const int c = c0 + (off >> 1);
     a_off[j] = c < ldy ? ((r >> 5) * g.Wo + (r & 31)) * ldy + c : -1;
     asm volatile("" : "+v"(a_off[j]));
@@ -130,7 +116,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
     const int hp = grp * RPI_B + lane / SPR_B;
     const int hy = hp / HW_HWD, hx = hp - hy * HW_HWD;
     b_hyx[j] = hp < HW_HPIX ? ((hy << 16) | hx) : -1;
-    b_c[j] = ci0 + ((((lane % SPR_B) * 16) ^ hw_swz<ROWB_B>(hp)) >> 1);
+    b_c[j] = ci0 + ((((lane % SPR_B) * 16) ^ tr_swz<ROWB_B>(hp)) >> 1);
     asm volatile("" : "+v"(b_hyx[j]), "+v"(b_c[j]));
   }
   // FAST path (reflect padding, the whole co tile inside dy, no operand-path transform: every conv of the generator): a wave-
@@ -171,7 +157,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
     const int rgrp = (j * 8 + wave) * RPI_A;
     const long long base = (long long)((q.img * g.Ho + q.y0) * g.Wo + q.x0) * ldy;      // wave-uniform
     const bf16_t* p = a_off[j] >= 0 ? dy + base + a_off[j] : zero;
-    glds16hw(p, sa + rgrp * ROWB_A);
+    glds16_asm(p, sa + rgrp * ROWB_A);
   };
   auto issue_b = [&](int stage, const TileAt& q, int j) {
     unsigned char* sb = smem + stage * HW_STAGE + HW_A_BYTES;
@@ -188,7 +174,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
           p = src + (unsigned)(((q.img * g.Hs + (y >> g.up)) * g.Ws + (x >> g.up)) * g.Cs + b_c[j]);   // < 2^31 elements (checked at launch)
       }
     }
-    glds16hw(p, sb + grp * 1024);
+    glds16_asm(p, sb + grp * 1024);
   };
   auto issue = [&](int stage, const TileAt& q) {                          // the whole half-tile in one burst
     if (fast) {
@@ -219,7 +205,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
       const int x = bound_coord(x0 + g.bx0 + hx, g.Wl, g.pad_mode);
       if ((y | x) < 0) continue;
       if (pro.ring != nullptr && !(ring_interior(y, g.Hl) && ring_interior(x, g.Wl))) continue;
-      const int cofs = ((sl * 16) ^ hw_swz<ROWB_B>(hp)) >> 1;
+      const int cofs = ((sl * 16) ^ tr_swz<ROWB_B>(hp)) >> 1;
       float A8[8], B8[8], f[8];
       ldcoef<8>(pcoef + cofs, A8);
       ldcoef<8>(pcoef + BCI + cofs, B8);
@@ -246,24 +232,6 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
   const int a_colb = (cb * 32 + 16 * tr_half + 4 * tr_p) * 2;           // byte column in a dy row
   const int b_colb = (ib * 32 + 16 * tr_half + 4 * tr_p) * 2;           // byte column in a halo row
 
-  auto tr_read = [&](const unsigned char* base, int o0, int o1) {
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + o0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + o1));
-    u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-    u32x4 r;
-    r.x = l2.x; r.y = l2.y; r.z = h2.x; r.w = h2.y;
-    return r;
-  };
-
-  typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-  auto tr_read_lds = [&](unsigned a0, unsigned a1) {                      // two 32-bit LDS addresses -> one 8 x bf16 fragment
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(uintptr_t)a0);
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(uintptr_t)a1);
-    u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-    u32x4 r;
-    r.x = l2.x; r.y = l2.y; r.z = h2.x; r.w = h2.y;
-    return r;
-  };
   // NTG == 1 (a wave owns all nine taps): the half-tile is walked by HALO row.  The halo fragment of (hy, half, tx) serves
   // tap row ty of tile row py = hy - ty for every ty, so it is read once and multiplied with the (up to three) live dy
   // fragments: 36 halo + 8 dy fragments per half-tile instead of 72 + 8.  For a fixed tap the (py, half) products still
@@ -272,10 +240,10 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
   // five per-lane bases (dy; halo by (constant & 3)) plus an immediate offset (< 64 KB).  The bases are made opaque per call:
   // left to itself the compiler materialises all 88 addresses in registers and spills.
   const int lq = 8 * lh + tr_q;
-  const int a_lane = lq * ROWB_A + (a_colb ^ hw_swz<ROWB_A>(lq));
+  const int a_lane = lq * ROWB_A + (a_colb ^ tr_swz<ROWB_A>(lq));
   int b_lane[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) b_lane[k] = lq * ROWB_B + (b_colb ^ hw_swz<ROWB_B>(k + lq));
+  for (int k = 0; k < 4; ++k) b_lane[k] = lq * ROWB_B + (b_colb ^ tr_swz<ROWB_B>(k + lq));
   auto compute_rows = [&](int stage) {
     if constexpr (NTG == 1) {
       unsigned ab = smem_lds + stage * HW_STAGE + a_lane;                 // 32-bit LDS addresses
@@ -322,7 +290,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
 #pragma unroll 2
       for (int kb = 0; kb < 8; ++kb) {                                    // 16-pixel reduction blocks of the half-tile
         const int ra = kb * 16 + 8 * lh + tr_q;                           // dy rows ra, ra+4
-        const u32x4 af = tr_read(ab, ra * ROWB_A + (a_colb ^ hw_swz<ROWB_A>(ra)), (ra + 4) * ROWB_A + (a_colb ^ hw_swz<ROWB_A>(ra + 4)));
+        const u32x4 af = tr_read(ab, ra * ROWB_A + (a_colb ^ tr_swz<ROWB_A>(ra)), (ra + 4) * ROWB_A + (a_colb ^ tr_swz<ROWB_A>(ra + 4)));
         const int py = kb >> 1, px0 = (kb & 1) * 16;
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
@@ -330,7 +298,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
           if (tap >= 9) break;
           const int ty = tap / 3, tx = tap - ty * 3;
           const int rb = (py + ty) * HW_HWD + px0 + tx + 8 * lh + tr_q;   // halo pixels rb, rb+4
-          const u32x4 bf = tr_read(bb, rb * ROWB_B + (b_colb ^ hw_swz<ROWB_B>(rb)), (rb + 4) * ROWB_B + (b_colb ^ hw_swz<ROWB_B>(rb + 4)));
+          const u32x4 bf = tr_read(bb, rb * ROWB_B + (b_colb ^ tr_swz<ROWB_B>(rb)), (rb + 4) * ROWB_B + (b_colb ^ tr_swz<ROWB_B>(rb + 4)));
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bf), acc[t], 0, 0, 0);
         }
       }
@@ -347,7 +315,7 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
 #pragma unroll 1
   for (int it = -1; it < nt; ++it) {
     if (it >= 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // my share of stage `it` has landed
+      wait_vm<0>();                                                       // my share of stage `it` has landed
       __builtin_amdgcn_s_barrier();                                       // ... everyone's; compute(it-1) is done everywhere
     }
     bool reload = false;
@@ -365,12 +333,12 @@ __global__ __launch_bounds__(512) void wgrad_halo_kernel(const GatherDesc g, con
     if constexpr (PRO) {
       if (it >= 0 && pro.A != nullptr) {
         if (reload) {
-          if (it + 1 < nt) hw_wait_vm<NA + NB>(); else hw_wait_vm<0>();   // the coefficient load is older than the DMA just issued
+          if (it + 1 < nt) wait_vm<NA + NB>(); else wait_vm<0>();   // the coefficient load is older than the DMA just issued
           if (tid < 2 * BCI) pcoef[tid] = cval;
           __syncthreads();
         }
         transform(it & 1, tbeg + it);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();                                     // the halo is normalised for every wave
       }
     }
@@ -409,18 +377,15 @@ static hipError_t launch_wgrad_halo(const GatherDesc& g, const void* src, const 
   int splits = std::max(1, num_cu / combos);                  // one workgroup per CU, a single round
   if (splits > 8) splits -= splits % 8;                       // the combos of a split land on one XCD (linear id % 8)
   if (splits > ntiles / 4) splits = std::max(1, ntiles / 4);
-  const long long slab_elems = wgrad_slab_elems(co_rows, g.K);
-  if ((size_t)slab_elems * splits > slab_capacity_elems) splits = (int)(slab_capacity_elems / (size_t)slab_elems);
-  if (splits < 1) return hipErrorNotSupported;
-  if (!force && combos * splits < (num_cu * 3) / 4) return hipErrorNotSupported;   // too little parallelism: wgrad_v2 / v1 fill the chip better
-  const int tps = (ntiles + splits - 1) / splits;
-  const int zs = (ntiles + tps - 1) / tps;
+  WgradSplitPlan sp;
+  if (!wgrad_split_plan(co_rows, g.K, slab_capacity_elems, splits, ntiles, sp)) return hipErrorNotSupported;
+  if (!force && combos * sp.splits < (num_cu * 3) / 4) return hipErrorNotSupported;   // too little parallelism: wgrad_v2 / v1 fill the chip better
   const size_t lds = 2 * (size_t)(128 * BCO * 2 + HW_HPAD * BCI * 2) + (pro != nullptr ? 2 * BCI * sizeof(float) : 0);
   auto kern = pro != nullptr ? wgrad_halo_kernel<BCO, BCI, NTG, true> : wgrad_halo_kernel<BCO, BCI, NTG, false>;
   const ConvPro pv = pro != nullptr ? *pro : ConvPro{nullptr, nullptr, 0, 0.f, nullptr, 0};
-  *nsplit_out = zs;
-  return launch_counted(K_WGRAD_HALO, PROF_WGRAD, conv_flops(g, co_rows), kern, dim3(zs, combos), dim3(512), lds, st, g,
-                        (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, nslices, tps, slab_elems, pv);
+  *nsplit_out = sp.zs;
+  return launch_counted(K_WGRAD_HALO, PROF_WGRAD, conv_flops(g, co_rows), kern, dim3(sp.zs, combos), dim3(512), lds, st, g,
+                        (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, nslices, sp.per, sp.slab_elems, pv);
 }
 
 // the shape gate and tile selection of the kernel (pro_ring: operand-path normalisation with a ring tensor)

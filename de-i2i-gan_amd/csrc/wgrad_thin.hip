@@ -22,17 +22,9 @@
 #include "common.h"
 #include "geom.h"
 #include "launch.h"
+#include "tile_prims.h"
 
 namespace dei2i {
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page_wt[256];
-
-typedef __attribute__((address_space(3))) void lds_void_wt;
-typedef __attribute__((address_space(1))) const void gbl_void_wt;
-
-DEI2I_D void glds16wt(const void* gptr, unsigned char* lds_wave_base) {
-  glds16_asm(gptr, lds_wave_base);      // (common.h: hipcc must not see the LDS write, or it drains the ring)
-}
 
 constexpr int WT_TH = 4, WT_TW = 32;                 // half-tile: 128 pixels
 constexpr int WT_BCO = 64;                           // output channels per workgroup
@@ -63,11 +55,12 @@ __global__ __launch_bounds__(512) void wgrad_thin_kernel(const GatherDesc g, con
   const int ntiles = g.N * tiles_img;
   const int tbeg = split * tiles_per_split;
   const int tend = min(ntiles, tbeg + tiles_per_split);
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page_wt);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
 
   // dy: one instruction = 8 pixel rows x 128 B: lane l -> row (l>>3), 16-byte slot (l&7), rows swizzled for the
-  //     transposed reads (rows r and r+2 alias: flip the 64-byte half); 16 instructions per half-tile, 2 per wave
+  //     transposed reads (tr_swz: rows r and r+2 alias, flip the 64-byte half); 16 instructions per half-tile, 2 per wave
   // x : one instruction = 64 halo pixels x 16 B, no swizzle (the windows overlap); waves 0 .. HGROUPS-1 issue one each
+  // (glds16_asm, tile_prims.h: hipcc must not see the LDS write, or it drains the ring)
   auto issue = [&](int stage, int t) {
     unsigned char* sa = smem + stage * STAGE;
     unsigned char* sb = sa + WT_A_BYTES;
@@ -79,11 +72,11 @@ __global__ __launch_bounds__(512) void wgrad_thin_kernel(const GatherDesc g, con
     for (int j = 0; j < 2; ++j) {
       const int rgrp = (j * 8 + wave) * 8;
       const int r = rgrp + (lane >> 3);                                   // pixel of the half-tile: (r>>5, r&31)
-      const int off = ((lane & 7) * 16) ^ (((r >> 1) & 1) << 6);
+      const int off = ((lane & 7) * 16) ^ tr_swz<WT_ROWB_A>(r);
       const int c = off >> 1;
       const size_t pix = ((size_t)img * g.Ho + y0 + (r >> 5)) * g.Wo + x0 + (r & 31);
       const bf16_t* p = c < ldy ? dy + pix * ldy + c : zero;
-      glds16wt(p, sa + rgrp * WT_ROWB_A);
+      glds16_asm(p, sa + rgrp * WT_ROWB_A);
     }
     if (wave < HGROUPS) {
       const int hp = wave * 64 + lane;
@@ -94,7 +87,7 @@ __global__ __launch_bounds__(512) void wgrad_thin_kernel(const GatherDesc g, con
         const int x = bound_coord(x0 + g.bx0 + hx, g.Wl, g.pad_mode);
         if ((y | x) >= 0) p = src + ((size_t)((img * g.Hs + y) * g.Ws + x)) * 8;
       }
-      glds16wt(p, sb + wave * 1024);
+      glds16_asm(p, sb + wave * 1024);
     }
   };
 
@@ -110,23 +103,14 @@ __global__ __launch_bounds__(512) void wgrad_thin_kernel(const GatherDesc g, con
   const int a_colb = (cb * 32 + 16 * tr_half + 4 * tr_p) * 2;           // byte column in a dy row
   const int b_colb = (16 * tr_half + 4 * tr_p) * 2;                     // byte offset in the 64-byte tap window
 
-  auto tr_read = [&](const unsigned char* base, int o0, int o1) {
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + o0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + o1));
-    u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-    u32x4 r;
-    r.x = l2.x; r.y = l2.y; r.z = h2.x; r.w = h2.y;
-    return r;
-  };
-
   auto compute = [&](int stage) {
     const unsigned char* ab = smem + stage * STAGE;
     const unsigned char* bb = ab + WT_A_BYTES;
 #pragma unroll 2
     for (int kb = 0; kb < 8; ++kb) {                                      // 16-pixel reduction blocks of the half-tile
       const int ra = kb * 16 + 8 * lh + tr_q;                             // dy rows ra, ra+4
-      const u32x4 af = tr_read(ab, ra * WT_ROWB_A + (a_colb ^ (((ra >> 1) & 1) << 6)),
-                               (ra + 4) * WT_ROWB_A + (a_colb ^ ((((ra + 4) >> 1) & 1) << 6)));
+      const u32x4 af = tr_read(ab, ra * WT_ROWB_A + (a_colb ^ tr_swz<WT_ROWB_A>(ra)),
+                               (ra + 4) * WT_ROWB_A + (a_colb ^ tr_swz<WT_ROWB_A>(ra + 4)));
       const int py = kb >> 1, px0 = (kb & 1) * 16;
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(512) void wgrad_thin_kernel(const GatherDesc g, con
 #pragma unroll 1
   for (int it = -1; it < nt; ++it) {
     if (it >= 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
       __builtin_amdgcn_s_barrier();
     }
     if (it + 1 < nt) issue((it + 1) & 1, tbeg + it + 1);
@@ -181,17 +165,14 @@ hipError_t wgrad_thin(const GatherDesc& g, const void* src, const void* dy, int 
   if ((long long)g.N * g.Hs * g.Ws * g.Cs >= (1ll << 31)) return hipErrorNotSupported;
   const int ntiles = g.N * (g.Ho / WT_TH) * (g.Wo / WT_TW);
   if (ntiles < 64) return hipErrorNotSupported;
-  int splits = std::min(2 * num_cu(), ntiles / 4);   // 44 KB of LDS per workgroup
-  const long long slab_elems = wgrad_slab_elems(co_rows, g.K);
-  if ((size_t)slab_elems * splits > slab_capacity_elems) splits = (int)(slab_capacity_elems / (size_t)slab_elems);
-  if (splits < 1) return hipErrorNotSupported;
-  const int tps = (ntiles + splits - 1) / splits;
-  const int zs = (ntiles + tps - 1) / tps;
+  const int splits = std::min(2 * num_cu(), ntiles / 4);   // 44 KB of LDS per workgroup
+  WgradSplitPlan sp;
+  if (!wgrad_split_plan(co_rows, g.K, slab_capacity_elems, splits, ntiles, sp)) return hipErrorNotSupported;
   constexpr int HPIX = (WT_TH + 6) * (WT_TW + 6);
   const size_t lds = 2 * (size_t)(WT_A_BYTES + ((HPIX + 4 + 63) / 64) * 1024);
-  *nsplit_out = zs;
-  return launch_counted(K_WGRAD_THIN, PROF_WGRAD, conv_flops(g, co_rows), wgrad_thin_kernel<7, 7>, dim3(zs), dim3(512), lds, st, g,
-                        (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, tps, slab_elems);
+  *nsplit_out = sp.zs;
+  return launch_counted(K_WGRAD_THIN, PROF_WGRAD, conv_flops(g, co_rows), wgrad_thin_kernel<7, 7>, dim3(sp.zs), dim3(512), lds, st, g,
+                        (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, sp.per, sp.slab_elems);
 }
 
 }  // namespace dei2i

@@ -16,26 +16,13 @@
 #include "common.h"
 #include "geom.h"
 #include "launch.h"
+#include "tile_prims.h"
 
 namespace dei2i {
 
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page_w[256];   // zero-initialised device memory
-
-typedef __attribute__((address_space(3))) void lds_void_t2;
-typedef __attribute__((address_space(1))) const void gbl_void_t2;
-
-DEI2I_D void glds16w(const void* gptr, unsigned char* lds_wave_base) {
-  glds16_asm(gptr, lds_wave_base);      // (common.h: hipcc must not see the LDS write, or it drains the ring)
-}
-
-DEI2I_D int xcd_remap3(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
-
 // LDS image per stage: A = dy tile [64 px][512 B] (256 co), B = x tile [64 px][256 B] (128 k columns).
-// tr-read swizzle: byte offset within the row ^= (row & 3) << 6 (both row lengths are multiples of 256 B).
+// tr-read swizzle: byte offset within the row ^= tr_swz (both row lengths are multiples of 256 B: (row & 3) << 6).
+// LDS-DMA through glds16_asm (tile_prims.h): hipcc must not see the LDS write, or it drains the ring.
 template <int BM>
 __global__ __launch_bounds__(512) void wgrad_v2_kernel(const GatherDesc g, const bf16_t* __restrict__ src,
                                                        const bf16_t* __restrict__ dy, const int co_rows, const int ldy,
@@ -43,6 +30,7 @@ __global__ __launch_bounds__(512) void wgrad_v2_kernel(const GatherDesc g, const
                                                        const int chunks_per_split, const long long slab_elems) {
   constexpr int BN = 128, BR = 64, STAGES = 3;
   constexpr int ROWB_A = BM * 2, ROWB_B = BN * 2;
+  static_assert(ROWB_A % 256 == 0 && ROWB_B % 256 == 0, "one tr_swz form for both tiles");
   constexpr int RPI_A = 1024 / ROWB_A, SPR_A = ROWB_A / 16;      // rows per DMA instruction, 16-byte slots per row
   constexpr int A_BYTES = BR * ROWB_A, B_BYTES = BR * ROWB_B, STAGE_BYTES = A_BYTES + B_BYTES;   // 32 KB + 16 KB
   constexpr int LA = A_BYTES / 1024 / 8, LB = B_BYTES / 1024 / 8;                                  // 4, 2 DMA per wave
@@ -52,7 +40,7 @@ __global__ __launch_bounds__(512) void wgrad_v2_kernel(const GatherDesc g, const
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int bid = xcd_remap3(blockIdx.x, gridDim.x);
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int tile_k = bid % tiles_k, tile_c = bid / tiles_k;
   const int c0 = tile_c * BM, k0 = tile_k * BN;
 
@@ -67,7 +55,7 @@ __global__ __launch_bounds__(512) void wgrad_v2_kernel(const GatherDesc g, const
   const int ty = (int)fd_div((uint32_t)tap, g.fd_tw);
   const int dyy = ty * g.ys, dxx = (tap - ty * g.tw) * g.xs;
   const bool k_ok = k0 < g.K;
-  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page_w);
+  const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_zero_page);
 
   // DMA roles.  A: one instruction = RPI_A rows x ROWB_A bytes (2 x 512 B or 4 x 256 B).
   //             B: one instruction = 4 rows x 256 B -> lane l: row (l>>4), slot (l&15).
@@ -78,17 +66,17 @@ __global__ __launch_bounds__(512) void wgrad_v2_kernel(const GatherDesc g, const
     for (int j = 0; j < LA; ++j) {
       const int rgrp = (j * 8 + wave) * RPI_A;               // first row of this instruction's row group
       const int r = rgrp + lane / SPR_A;
-      const int off = ((lane % SPR_A) * 16) ^ ((r & 3) << 6);  // source byte offset that belongs at this LDS slot
+      const int off = ((lane % SPR_A) * 16) ^ tr_swz<ROWB_A>(r);  // source byte offset that belongs at this LDS slot
       const int m = mb + r;
       const int c = c0 + (off >> 1);
       const bf16_t* p = (m < g.M && c < ldy) ? dy + (size_t)m * ldy + c : zero;
-      glds16w(p, sbase + rgrp * ROWB_A);
+      glds16_asm(p, sbase + rgrp * ROWB_A);
     }
 #pragma unroll
     for (int j = 0; j < LB; ++j) {
       const int rgrp = j * 32 + wave * 4;
       const int r = rgrp + (lane >> 4);
-      const int off = ((lane & 15) * 16) ^ ((r & 3) << 6);
+      const int off = ((lane & 15) * 16) ^ tr_swz<ROWB_B>(r);
       const int m = mb + r;
       const bf16_t* p = zero;
       if (k_ok && m < g.M) {
@@ -98,7 +86,7 @@ __global__ __launch_bounds__(512) void wgrad_v2_kernel(const GatherDesc g, const
         const int x = bound_coord(ox * g.sw + g.bx0 + dxx, g.Wl, g.pad_mode);
         if ((y | x) >= 0) p = src + ((size_t)((n * g.Hs + (y >> g.up)) * g.Ws + (x >> g.up))) * g.Cs + ci0 + (off >> 1);
       }
-      glds16w(p, sbase + A_BYTES + rgrp * ROWB_B);
+      glds16_asm(p, sbase + A_BYTES + rgrp * ROWB_B);
     }
   };
 
@@ -119,7 +107,8 @@ __global__ __launch_bounds__(512) void wgrad_v2_kernel(const GatherDesc g, const
     u32x4 af[2][TM], bf[2][TN];
     auto load_frags = [&](int kk, u32x4 (&a)[TM], u32x4 (&b)[TN]) {
       const int row_lo = kk * 16 + 8 * lh + tr_q;
-      const int s0 = (row_lo & 3) << 6, s1 = ((row_lo + 4) & 3) << 6;
+      const int s0 = tr_swz<ROWB_A>(row_lo), s1 = tr_swz<ROWB_A>(row_lo + 4);   // (the same for ROWB_B)
+      // (tr_read of tile_prims.h, written out: as calls, hipcc allocates this kernel's registers differently)
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int colb = (wm * WTM + i * 32 + 16 * tr_cohalf + 4 * tr_p) * 2;
@@ -156,11 +145,7 @@ __global__ __launch_bounds__(512) void wgrad_v2_kernel(const GatherDesc g, const
     issue(0, cbeg);
     if (nc > 1) issue(1, cbeg + 1);
     for (int it = 0; it < nc; ++it) {
-      if (it + 1 < nc) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LA + LB) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      if (it + 1 < nc) wait_vm<LA + LB>(); else wait_vm<0>();
       __builtin_amdgcn_s_barrier();
       if (it + 2 < nc) issue((it + 2) % STAGES, cbeg + it + 2);
       compute(it % STAGES);
@@ -231,16 +216,13 @@ hipError_t wgrad_v2(const GatherDesc& g, const void* src, const void* dy, int co
   const int nchunks = (g.M + BR - 1) / BR;
   int splits = std::max(1, num_cu() / tiles);                  // one workgroup per CU (144 KB LDS), a single round
   if (splits > nchunks / 8) splits = std::max(1, nchunks / 8);
-  const long long slab_elems = wgrad_slab_elems(co_rows, g.K);
-  if ((size_t)slab_elems * splits > slab_capacity_elems) splits = (int)(slab_capacity_elems / (size_t)slab_elems);
-  if (splits < 1) return hipErrorNotSupported;
-  const int cps = (nchunks + splits - 1) / splits;
-  const int zs = (nchunks + cps - 1) / cps;
-  *nsplit_out = zs;
+  WgradSplitPlan sp;
+  if (!wgrad_split_plan(co_rows, g.K, slab_capacity_elems, splits, nchunks, sp)) return hipErrorNotSupported;
+  *nsplit_out = sp.zs;
   const size_t lds = 3 * (size_t)(64 * 2 * BM + 64 * 256);
   return launch_counted(K_WGRAD_V2, PROF_WGRAD, conv_flops(g, co_rows), BM == 256 ? wgrad_v2_kernel<256> : wgrad_v2_kernel<128>,
-                        dim3(tiles, 1, zs), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, tiles_k,
-                        cps, slab_elems);
+                        dim3(tiles, 1, sp.zs), dim3(512), lds, st, g, (const bf16_t*)src, (const bf16_t*)dy, co_rows, ldy, slabs, tiles_k,
+                        sp.per, sp.slab_elems);
 }
 
 // first level of a two-level slab sum, used when the (co, channel-block) grid alone cannot fill the chip (thin layers

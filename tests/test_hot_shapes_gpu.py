@@ -426,7 +426,7 @@ def _place(arena, want_bit31, tensors):
 
 def test_operand_addresses_on_both_sides_of_the_2gib_line():
     """Regression test for a GPU memory-access fault on record (round 2, development build of wgrad_halo's lean LDS-DMA issue
-    path): ``glds16_asm_s`` (csrc/common.h) hands ``global_load_lds_dwordx4`` a wave-uniform 64-bit base in an SGPR pair, built
+    path): ``glds16_asm_s`` (csrc/tile_prims.h) hands ``global_load_lds_dwordx4`` a wave-uniform 64-bit base in an SGPR pair, built
     from two ``readfirstlane``s of the pointer's halves -- the builtin returns *int*, and widening the low half as a signed value
     put 0xffffffff into the high half whenever the operand's low address word had bit 31 set (fault address 0xffff_b1400000).
     Whether a run hit it depended on where the allocator put the operand.  Here the operands of the kernels that use the helper
