@@ -2638,3 +2638,111 @@ def cce_logits(x, target):
     if not isinstance(target, torch.Tensor):
         raise ValueError("cce_logits: the target is a tensor of class weights, one row per sample")
     return _CceLogits.apply(x, target)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Validation metrics (csrc/metrics.hip; trainer.validate()): per image the sums PSNR, L1 and SSIM are made of in ONE pass over the
+# two image batches, and the classifier's confusion counts -- float64 / int64 device tensors that add up over a loader, read by
+# the host once (``metrics_summary`` / ``clf_scores``).  No autograd.
+# --------------------------------------------------------------------------------------------------------------
+SSIM_WINDOW = 11
+IMAGE_SUMS = ("sse", "sae", "sse_masked", "sae_masked", "count_masked", "ssim_sum")
+CLF_KINDS = {"bce": L.CLF_MULTI, "mse": L.CLF_MULTI, "cce": L.CLF_ARGMAX}
+
+
+def image_metrics(x, y, mask=None, data_range=2.0):
+    """-> float64 (N, 6) device tensor, per image (``IMAGE_SUMS``): the sums of (x-y)^2 and |x-y| over its C*H*W elements; the same
+    two over the elements of the pixels where ``mask`` (N,1,H,W) is not 0, and their count (zeros without a mask); the sum of SSIM
+    (Wang et al. 2004: 11 x 11 Gaussian window, sigma 1.5, no padding, C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = ``data_range``) over the
+    C*(H-10)*(W-10) window positions.  ``x``, ``y``: NCHW image batches of one shape; other dtypes or layouts than contiguous fp32
+    are converted.  Two launches on the current stream, no atomics, nothing read on the host: bit-reproducible, capturable."""
+    if x.dim() != 4 or tuple(x.shape) != tuple(y.shape):
+        raise ValueError(f"image_metrics: x of shape {tuple(x.shape)}, y of shape {tuple(y.shape)}; expected two NCHW batches of one shape")
+    n, c, h, w = x.shape
+    if n == 0 or c == 0 or h < SSIM_WINDOW or w < SSIM_WINDOW:
+        raise ValueError(f"image_metrics: {n} x {c} x {h} x {w} images; the {SSIM_WINDOW} x {SSIM_WINDOW} SSIM window needs H, W >= "
+                         f"{SSIM_WINDOW} (and N, C > 0)")
+    if mask is not None and tuple(mask.shape) != (n, 1, h, w):
+        raise ValueError(f"image_metrics: mask of shape {tuple(mask.shape)}; expected {(n, 1, h, w)}")
+    if not float(data_range) > 0.0:
+        raise ValueError(f"image_metrics: |data_range {data_range}| is invalid (> 0)")
+    _require_gpu(x, "image_metrics")
+    if y.device != x.device or (mask is not None and mask.device != x.device):
+        raise ValueError(f"image_metrics: x is on {x.device}, y on {y.device}" + (f", the mask on {mask.device}" if mask is not None else ""))
+    x, y = _f32c(x.detach()), _f32c(y.detach())
+    mask = None if mask is None else _f32c(mask.detach())
+    lib = _lib_for(x)
+    words = lib.dei2i_image_metrics_ws_doubles(n, c, h, w)
+    if words <= 0:
+        raise ValueError(f"image_metrics: a batch of shape {(n, c, h, w)} is too large (N*C*H*W < 2^40, C*H*W < 2^31)")
+    ws = torch.empty(words, dtype=torch.float64, device=x.device)
+    out = torch.empty((n, len(IMAGE_SUMS)), dtype=torch.float64, device=x.device)
+    L.check(lib.dei2i_image_metrics(n, c, h, w, _p(x), _p(y), _p(mask), float(data_range), _p(ws), _p(out), _stream()), "image_metrics")
+    return out
+
+
+def clf_counts(logits, targets, kind, out=None):
+    """Confusion counts of a classifier head: ``logits`` (N, K) or (N, K, 1, ..., 1) against ``targets`` of as many elements.
+    ``kind`` "bce" / "mse" (multi-label): class k of a row is predicted when its logit is > 0 (a logit of 0 is a negative), wanted
+    when its target is > 0.5; "cce": the row's argmax against the targets' argmax.  -> int64 (4K + 1,) device tensor TP[K] | FP[K] |
+    FN[K] | TN[K] | rows right in every class: ``out`` (the caller's, ADDED to: a loader sums without a host read) or a fresh one."""
+    if kind not in CLF_KINDS:
+        raise ValueError(f"clf_counts: |kind {kind}| is invalid ({' | '.join(CLF_KINDS)})")
+    if logits.dim() < 2 or any(d != 1 for d in logits.shape[2:]) or logits.numel() == 0:
+        raise ValueError(f"clf_counts: logits of shape {tuple(logits.shape)}; expected (N, K) or (N, K, 1, ..., 1)")
+    if targets.numel() != logits.numel():
+        raise ValueError("clf_counts: target size mismatch")
+    n, k = logits.shape[0], logits.shape[1]
+    _require_gpu(logits, "clf_counts")
+    if targets.device != logits.device:
+        raise ValueError(f"clf_counts: the logits are on {logits.device}, the targets on {targets.device}")
+    if out is None:
+        out = torch.zeros(4 * k + 1, dtype=torch.int64, device=logits.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (4 * k + 1,) or out.device != logits.device or not out.is_contiguous():
+        raise ValueError(f"clf_counts: out must be a contiguous int64 ({4 * k + 1},) tensor on {logits.device}")
+    logits, targets = _f32c(logits.detach().reshape(n, k)), _f32c(targets.detach().reshape(n, k))
+    L.check(_lib_for(logits).dei2i_clf_counts(n, k, _p(logits), _p(targets), CLF_KINDS[kind], _p(out), _stream()), "clf_counts")
+    return out
+
+
+IMAGE_SCORES = ("psnr", "ssim", "l1", "psnr_masked")
+CLF_SCORES = ("acc", "f1")
+
+
+def image_scores(sums, chw, data_range=2.0):
+    """``image_metrics`` rows (M, 6) of images of shape ``chw`` = (C, H, W) -> float64 (4,) device tensor (``IMAGE_SCORES``), torch ops
+    on M numbers: the mean over the images of 10 log10(L^2 / max(mse, 1e-10 L^2)) (an exact reconstruction scores 100 dB), of the mean
+    SSIM and of the mean |x-y|, and the PSNR over the masked elements, averaged over the images that have any (NaN when none has)."""
+    c, h, w = (int(v) for v in chw)
+    sums = sums.reshape(-1, len(IMAGE_SUMS)).double()
+    peak = float(data_range) ** 2
+
+    def psnr(mse):
+        return 10.0 * torch.log10(peak / mse.clamp_min(1e-10 * peak))
+
+    count = sums[:, 4]
+    masked = torch.where(count > 0, psnr(sums[:, 2] / count.clamp_min(1.0)), torch.full_like(count, float("nan")))
+    return torch.stack([psnr(sums[:, 0] / (c * h * w)).mean(),
+                        (sums[:, 5] / (c * (h - SSIM_WINDOW + 1) * (w - SSIM_WINDOW + 1))).mean(),
+                        (sums[:, 1] / (c * h * w)).mean(), torch.nanmean(masked)])
+
+
+def clf_scores_dev(counts):
+    """``clf_counts`` words -> float64 (2,) device tensor (``CLF_SCORES``): the share of rows right in every class, and the macro F1
+    = mean of 2 TP / (2 TP + FP + FN) over the classes with any positive target (NaN when there is none)"""
+    k = (counts.numel() - 1) // 4
+    tp, fp, fn, tn = counts[:4 * k].double().reshape(4, k)
+    rows = tp[0] + fp[0] + fn[0] + tn[0]
+    f1 = torch.where(tp + fn > 0, 2 * tp / (2 * tp + fp + fn).clamp_min(1.0), torch.full_like(tp, float("nan")))
+    return torch.stack([counts[4 * k].double() / rows, torch.nanmean(f1)])
+
+
+def metrics_summary(sums, chw, data_range=2.0):
+    """Accumulated ``image_metrics`` rows (the batches' outputs concatenated) of images of shape ``chw`` = (C, H, W) -> {"psnr",
+    "ssim", "l1", "psnr_masked"} as Python floats (``image_scores``), with ONE device read."""
+    return dict(zip(IMAGE_SCORES, image_scores(sums, chw, data_range).tolist()))
+
+
+def clf_scores(counts):
+    """Accumulated ``clf_counts`` words -> {"acc", "f1"} as Python floats (``clf_scores_dev``), with one device read"""
+    return dict(zip(CLF_SCORES, clf_scores_dev(counts).tolist()))

@@ -428,6 +428,31 @@ def clip_options(opt):
     return float(c)
 
 
+def validation_options(opt, metric_names=()):
+    """-> {"val_freq": epochs between two validation passes of ``train()`` (absent, None or 0: 0 = never), "val_max_batches" (None:
+    the whole loader), "val_seed" (default 0: the seed of validation's own draws), "save_best": the metric of ``metric_names`` whose
+    best value keeps a "best" checkpoint, or None}.  ``metric_names``: what the asking trainer's ``validate()`` returns."""
+    freq = getattr(opt, "val_freq", None)
+    freq = 0 if freq is None else freq
+    if isinstance(freq, bool) or int(freq) != freq or freq < 0:
+        raise ValueError(f"|val_freq {freq}| is invalid (a whole number of epochs >= 0; None or 0 turns validation off)")
+    batches = getattr(opt, "val_max_batches", None)
+    if batches is not None and (isinstance(batches, bool) or int(batches) != batches or batches <= 0):
+        raise ValueError(f"|val_max_batches {batches}| is invalid (a whole number of batches > 0; None: the whole loader)")
+    seed = getattr(opt, "val_seed", None)
+    seed = 0 if seed is None else seed
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < 2 ** 63:
+        raise ValueError(f"|val_seed {seed}| is invalid (a whole number in [0, 2^63))")
+    best = getattr(opt, "save_best", None) or None
+    if best is not None and best not in metric_names:
+        raise ValueError(f"|save_best {best}| is invalid (the metrics of this stage: {' | '.join(metric_names)})")
+    return {"val_freq": int(freq), "val_max_batches": None if batches is None else int(batches), "val_seed": int(seed),
+            "save_best": best}
+
+
+LOWER_IS_BETTER = ("l1",)          # (every other validation metric: higher is better)
+
+
 def ada_options(opt, diffaug_stage=True):
     """-> None (``opt.diff_aug_p`` absent or None and ``opt.ada_target`` absent, None or 0: DiffAugment as it was), or the dict
     {"p": the initial (or, without a target, the fixed) probability, "target": r_t's target or None (no controller), "interval"

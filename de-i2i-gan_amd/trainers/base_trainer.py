@@ -11,7 +11,8 @@ from .. import ops
 from .. import train_state as TS
 from ..models import create_model
 from ..networks import tensors_dropped_on_load
-from ..optim import FusedAdam, FusedRMSprop, FusedSGD, ada_options, clip_options, ema_options
+from ..optim import (LOWER_IS_BETTER, FusedAdam, FusedRMSprop, FusedSGD, ada_options, clip_options, ema_options,
+                     validation_options)
 
 
 # opt.optimizer -> keyword arguments of the fused optimizer (the reference builds torch.optim.Adam(betas=(0.5, 0.999)) /
@@ -29,6 +30,7 @@ class BaseTrainer:
     ``optimizers`` / ``schedulers`` keyed by network name; the schedulers are stepped ``first_epoch`` times at construction
     like the reference does."""
     diff_augments = False        # whether the trainer's stage applies opt.diff_aug (optim.ada_options)
+    metric_names = ()            # what the stage's validate() returns (optim.validation_options: opt.save_best names one of them)
 
     def __init__(self, opt):
         self.opt = opt
@@ -42,13 +44,20 @@ class BaseTrainer:
         # opt.diff_aug_p / opt.ada_target: gated DiffAugment and its controller (the defectGAN stage; refused elsewhere, and an
         # invalid combination before anything is built)
         self.ada_opts = ada_options(opt, diffaug_stage=self.diff_augments)
+        # opt.val_freq / val_max_batches / val_seed / save_best: the validation pass (validate()), its hook in train() and the "best"
+        # checkpoint -- an invalid value or a metric this stage does not have is refused before anything is built
+        self.val_opts = validation_options(opt, self.metric_names)
+        self.best = None                  # (epoch, iters, value) of the "best" checkpoint
         self.model = create_model(opt)
         # opt.ema_beta > 0: the EMA copies of what the G optimizer trains start from the weights just initialised or restored
         self.model.create_ema(self._restore_or_init_weights(opt))
         self.losses, self.dis_outputs = defaultdict(list), defaultdict(list)
-        if opt.phase == "val":
-            self.metrics = {}
+        self.metrics = defaultdict(list)  # {metric name: one value per validate() call}
         self._resume_progress(opt)
+        best_path = opt.ckpt_dir / opt.name / "best.txt"
+        if opt.continue_training and self.val_opts["save_best"] and best_path.exists():      # (a continued run keeps its best so far)
+            epoch, iters, value = best_path.read_text().strip().split(",")
+            self.best = (int(epoch), int(iters), float(value))
         self._init_lr(opt)
         self._create_optimizer(opt)
         self._create_scheduler(opt)
@@ -195,6 +204,90 @@ class BaseTrainer:
         """Drop the captured graphs of ``graph_step`` (the next step() warms up and captures again)."""
         if self._graphs is not None:
             self._graphs.release()
+
+    # ---- validation: a pass that leaves training exactly where it was ------------------------------------------------------------
+    def _generators(self):
+        """the generator and its EMA copy: every module validation may run that memoizes SPADE tables"""
+        nets = [self.model.netG] + [net for label, net in self.model.ema.items() if label == "G"]
+        return [net for net in nets if hasattr(net, "clear_spade_cache")]
+
+    @contextlib.contextmanager
+    def _validation_scope(self):
+        """What ``validate()`` runs in: no grad, every draw from generators of validation's own, seeded by ``opt.val_seed`` -- the
+        torch CPU and device RNGs inside ``torch.random.fork_rng``, Python's ``random`` saved and put back, and a fresh
+        ``ops.DeviceRng(val_seed)`` swapped in for the model's ``mask_rng`` / ``embed_rng``, whose counters therefore never move
+        (``diffaug_rng`` is not drawn from: no inference mode augments).  On exit every module has the ``training`` flag it had
+        (the inference modes put the networks in eval mode, so BatchNorm's running statistics and ``num_batches_tracked`` are only
+        read), the generator has the table marks it had, and the SPADE tables and the label-set memo are dropped: the next train
+        pass on the same label tensor re-primes.  Nothing inside touches ``iters``, an optimizer or a captured graph."""
+        import random
+        model, seed = self.model, self.val_opts["val_seed"]
+        device = torch.device(self.opt.device)
+        modules = [m for net in list(model.networks.values()) + list(self._extra_modules().values()) for m in net.modules()]
+        flags = [m.training for m in modules]
+        marks = model.netG.table_marks() if hasattr(model.netG, "table_marks") else None
+        swapped = {}
+        if getattr(model, "mask_rng", None) is not None:
+            swapped["mask_rng"], model.mask_rng = model.mask_rng, ops.DeviceRng(seed, device)
+        bank = getattr(model, "embed_bank", None)
+        if bank is not None:
+            swapped["embed_rng"], bank.rng = bank.rng, ops.DeviceRng(seed, device)
+            model.embed_rng = bank.rng
+        py_state = random.getstate()
+        try:
+            with torch.no_grad(), torch.random.fork_rng(devices=[device] if device.type == "cuda" else []):
+                torch.manual_seed(seed)
+                random.seed(seed)
+                yield
+        finally:
+            random.setstate(py_state)
+            if "mask_rng" in swapped:
+                model.mask_rng = swapped["mask_rng"]
+            if "embed_rng" in swapped:
+                bank.rng = model.embed_rng = swapped["embed_rng"]
+            for m, flag in zip(modules, flags):
+                m.__dict__["training"] = flag
+            for net in self._generators():
+                net.clear_spade_cache()
+            if marks is None and hasattr(model.netG, "table_marks") and model.netG.table_marks() is not None:
+                for m in model.netG._table_modules():        # (a pass before the first step: that step still finds an unmarked tree)
+                    m.__dict__.pop("_ran_class_mode", None)
+                model.netG.__dict__.pop("_marked_table_modules", None)
+            if hasattr(model, "_label_sets"):
+                model._label_sets = None
+
+    def _classify(self, images, labels, counts):
+        """D's classifier on ``images`` against ``labels``: its confusion counts added to ``counts`` (None: a fresh buffer) -> counts"""
+        _, logits = self.model.netD(images)
+        return ops.clf_counts(logits, labels.to(logits.device).reshape(logits.shape[0], -1), self.model.clf_loss_type, out=counts)
+
+    def _finish_validation(self, names, scores):
+        """``scores``: float64 device tensors whose concatenation holds one value per name -> {name: float}, with the ONE host read
+        of the pass; each value is appended to ``self.metrics[name]``"""
+        values = torch.cat([s.reshape(-1) for s in scores]).tolist()
+        assert len(values) == len(names)
+        out = dict(zip(names, values))
+        for name, v in out.items():
+            self.metrics[name].append(v)
+        return out
+
+    def maybe_save_best(self, epoch):
+        """With ``opt.save_best = "<metric>"``, after a ``validate()``: when the metric's newest value beats the best one so far (higher
+        is better, lower for ``l1``; NaN never does), ``save_checkpoint("best", epoch)`` -- ``best_net_*.pth``, with ``opt.train_state``
+        ``best_train_state.pth`` -- and ``best.txt`` = (epoch, iters, value) next to them.  -> whether it saved."""
+        name = self.val_opts["save_best"]
+        if name is None or not self.metrics[name]:
+            return False
+        value = self.metrics[name][-1]
+        sign = -1.0 if name in LOWER_IS_BETTER else 1.0
+        if math.isnan(value) or (self.best is not None and not sign * value > sign * self.best[2]):
+            return False
+        self.best = (int(epoch), int(self.iters), float(value))
+        self.save_checkpoint("best", epoch)
+        path = self.opt.ckpt_dir / self.opt.name / "best.txt"
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(f"{self.best[0]},{self.best[1]},{self.best[2]!r}\n")
+        return True
 
     # ---- checkpoints: weights as the reference writes them; with opt.train_state one more file, written last --------------------
     def save_checkpoint(self, label, epoch, latest=False):

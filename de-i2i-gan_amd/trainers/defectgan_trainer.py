@@ -6,11 +6,15 @@ epoch).
 
 TensorBoard logging, progress bars, image grids and FID/IS/LPIPS validation are host-side tooling outside the hot path
  and are not part of this package."""
+import torch
+
+from .. import ops
 from .base_trainer import BaseTrainer
 
 
 class DefectGanTrainer(BaseTrainer):
     diff_augments = True
+    metric_names = ("cyc_psnr", "cyc_ssim", "cyc_df_psnr", "cyc_df_ssim", "clf_acc_real", "clf_f1_real", "clf_acc_fake", "clf_f1_fake")
 
     def __init__(self, opt):
         super().__init__(opt)
@@ -79,13 +83,60 @@ class DefectGanTrainer(BaseTrainer):
     def train(self, train_loaders, val_loaders=None):
         """Epochs ``first_epoch .. num_epochs`` (1-based, like the reference): ``train_loaders['defects']`` is iterated once
         per epoch, ``train_loaders['background']`` is an (infinite) iterator drawn with ``next`` -- both yield
-        ``(images, labels, _)``.  ``val_loaders`` is accepted for signature compatibility (metrics are out of scope)."""
+        ``(images, labels, _)``.  ``opt.val_freq = E`` (> 0): after every E-th epoch ``validate(val_loaders, opt.val_max_batches)``
+        runs (``val_loaders``: the same two keys; required then) and, with ``opt.save_best``, ``maybe_save_best(epoch)``; without it
+        ``val_loaders`` is not read."""
+        val_freq = self.val_opts["val_freq"]
+        if val_freq > 0 and val_loaders is None:
+            raise ValueError(f"val_freq={val_freq} validates every {val_freq} epoch(s): train() needs val_loaders")
         for epoch in range(self.first_epoch, self.opt.num_epochs + 1):
             self._init_losses()
             self._train_epoch(train_loaders, epoch)
             if epoch % getattr(self.opt, "save_ckpt_freq", 10 ** 9) == 0:
                 self.save_checkpoint(epoch, epoch)
+            if val_freq > 0 and epoch % val_freq == 0:
+                self.validate(val_loaders, self.val_opts["val_max_batches"])
+                self.maybe_save_best(epoch)
             self._update_per_epoch(epoch)
+
+    # ---- validation ---------------------------------------------------------------------------------------------------------
+    def validate(self, loaders, max_batches=None):
+        """One pass over ``loaders`` (the ``defects`` / ``background`` shape of ``train_loaders``; at most ``max_batches`` batches) ->
+        {name: float}, each value also appended to ``self.metrics[name]``.  Per batch ``(bg, df, df_labels)``, every generator pass
+        through ``model("inference", ...)`` (the EMA copies under ``opt.ema_inference``; SPADE, AdaIN and SEAN alike):
+          ``fake_df = G(bg, df_labels)``, ``restored = G(fake_df, normal_labels)``: ``cyc_psnr`` / ``cyc_ssim`` of restored vs bg;
+          the mirror image df -> normal -> df_labels against df: ``cyc_df_psnr`` / ``cyc_df_ssim`` (ops.image_metrics);
+          ``clf_acc_real`` / ``clf_f1_real``: D's classifier on df against df_labels (exact-match rate; macro F1 over the classes with
+          any positive); ``clf_acc_fake`` / ``clf_f1_fake``: the same on fake_df -- does it find the defect that was asked for?
+        Every draw (NoiseInjection, SEAN's ``random.choices`` or its device draws) comes from validation's own generators seeded by
+        ``opt.val_seed`` (``_validation_scope``), so scores compare across epochs.  Everything accumulates on the device; ONE host
+        read at the end.  Runs eagerly, keeps captured graphs, and leaves training exactly where it was (``state_digest()``, every
+        RNG state and counter, BatchNorm statistics, ``training`` flags, ``iters``).  Under ``attach_ddp`` this is a local call on
+        whatever loaders the rank passes: no collective."""
+        model, device = self.model, self.opt.device
+        cyc, cyc_df, real, fake, chw = [], [], None, None, None
+        with self._validation_scope():
+            for i, (df, df_labels, *_) in enumerate(loaders["defects"]):
+                if max_batches is not None and i >= max_batches:
+                    break
+                bg = next(loaders["background"])[0][:df.size(0)]
+                bg, df, df_labels = (t.to(device, non_blocking=True) for t in (bg, df, df_labels))
+                nm_labels = torch.zeros_like(df_labels)
+                nm_labels[:, 0] = 1
+                fake_df = model("inference", bg, df_labels)[0]
+                restored = model("inference", fake_df, nm_labels)[0]
+                fake_nm = model("inference", df, nm_labels)[0]
+                recovered = model("inference", fake_nm, df_labels)[0]
+                cyc.append(ops.image_metrics(restored, bg))
+                cyc_df.append(ops.image_metrics(recovered, df))
+                real = self._classify(df, df_labels, real)
+                fake = self._classify(fake_df, df_labels, fake)
+                chw = tuple(bg.shape[1:])
+            if not cyc:
+                raise ValueError("validate: the loaders yielded no batch")
+            scores = [ops.image_scores(torch.cat(cyc), chw)[:2], ops.image_scores(torch.cat(cyc_df), chw)[:2],
+                      ops.clf_scores_dev(real), ops.clf_scores_dev(fake)]
+            return self._finish_validation(self.metric_names, scores)
 
     def _train_epoch(self, data_loaders, epoch):
         for df_data, df_labels, _ in data_loaders["defects"]:

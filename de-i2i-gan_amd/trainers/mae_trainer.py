@@ -18,11 +18,13 @@ TensorBoard logging, image grids and FID validation are host-side tooling outsid
 package."""
 import torch
 
+from .. import ops
 from .base_trainer import BaseTrainer
 
 
 class MAETrainer(BaseTrainer):
     draws_masks = True           # every update draws a patch mask (graph_step captures it only when opt.mask_rng = "device")
+    metric_names = ("psnr", "ssim", "l1", "psnr_masked", "clf_acc", "clf_f1")      # (ops.IMAGE_SCORES, then clf_ + ops.CLF_SCORES)
 
     def __init__(self, opt, data_types=("fusion",)):
         super().__init__(opt)
@@ -75,6 +77,36 @@ class MAETrainer(BaseTrainer):
         self._scaled_update(d_loss, "D")
         norm_keys, norms = self._grad_norm_records("D")
         self._record([("gan", "D"), ("clf", "D")] + norm_keys, [gan_loss, clf_loss] + norms)
+
+    # ---- validation ---------------------------------------------------------------------------------------------------------
+    def validate(self, loader, max_batches=None):
+        """One pass over ``loader`` (it yields ``(images, labels, _)``; at most ``max_batches`` batches) -> {name: float}, each value
+        also appended to ``self.metrics[name]``: ``l1``, ``psnr``, ``ssim`` of the repaired image against the original over the whole
+        image, ``psnr_masked`` over the pixels the generator had to invent (ops.image_metrics: one fused pass per batch), and
+        ``clf_acc`` / ``clf_f1`` of D's classifier on the real images (exact-match rate; macro F1 over the classes with any positive).
+        Per batch one no-grad eval pass ``_repair_mask`` of what ``mae_inference`` runs (the EMA copies under ``opt.ema_inference``),
+        on masks drawn from validation's own generators seeded by ``opt.val_seed`` (``_validation_scope``): every call sees the same
+        masks on the same loader order, so scores compare across epochs.  Everything accumulates on the device; ONE host read at
+        the end.  Runs eagerly, keeps captured graphs, and leaves training exactly where it was (``state_digest()``, every RNG state
+        and counter, BatchNorm statistics, ``training`` flags, ``iters``).  Under ``attach_ddp`` this is a local call on whatever
+        loader the rank passes: no collective."""
+        model, device = self.model, self.opt.device
+        sums, counts, chw = [], None, None
+        with self._validation_scope():
+            model.netD.eval()
+            model.netG.eval()
+            with model._ema_scope():
+                for i, (imgs, labels, *_) in enumerate(loader):
+                    if max_batches is not None and i >= max_batches:
+                        break
+                    imgs, labels = imgs.to(device, non_blocking=True), labels.to(device, non_blocking=True)
+                    predicted, masks = model._repair_mask(imgs, labels)
+                    sums.append(ops.image_metrics(predicted, imgs, mask=1.0 - masks))       # (masks: 1 = kept, 0 = the token's)
+                    counts = self._classify(imgs, labels, counts)
+                    chw = tuple(imgs.shape[1:])
+            if not sums:
+                raise ValueError("validate: the loader yielded no batch")
+            return self._finish_validation(self.metric_names, [ops.image_scores(torch.cat(sums), chw), ops.clf_scores_dev(counts)])
 
     def step(self, data, labels):
         """One iteration of the reference's loop (mae_trainer.py:92-99).  ``opt.graph_step``: replayed from a captured graph after

@@ -464,6 +464,29 @@ int dei2i_embed_draw(uint64_t seed, uint64_t* counter_dev, int N, int row0, int 
                      const int* table, int64_t table_total, int* index_out, uint64_t* invalid_dev, dei2i_stream s);
 int dei2i_embed_gather(int64_t rows, int embed_nc, const int* index, const float* bank, int64_t bank_rows, float* out, dei2i_stream s);
 
+/* ---- validation metrics (csrc/metrics.hip): the sums PSNR, L1 and SSIM are made of, and the classifier's confusion counts ----
+ * dei2i_image_metrics: x, y contiguous fp32 NCHW, H, W >= 11; mask (nullable) fp32 (N,1,H,W), a pixel is masked when its word is
+ * not 0.  out[n][0..5] (float64) = sum of (x-y)^2, sum of |x-y| over the image's C*H*W elements; the same two over the masked
+ * pixels' elements and their count (all 0 without a mask); the sum of SSIM over the C*(H-10)*(W-10) window positions -- Wang et al.
+ * 2004: 11 x 11 Gaussian window, sigma 1.5, weights normalised to 1, no padding, C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range,
+ * SSIM = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx^2 + sy^2 + C2)) from the window means of x, y, x^2, y^2, xy.  One
+ * workgroup per 32 x 32 tile of window positions and plane stores six float64 partials to ws (dei2i_image_metrics_ws_doubles
+ * words, no clearing); a second launch sums them per image in a fixed order: no atomics, bit-reproducible, nothing read on the
+ * host.  BAD_ARG: null x, y, ws or out, N, C <= 0, H or W < 11, N*C*H*W >= 2^40, C*H*W >= 2^31, data_range <= 0.
+ *
+ * dei2i_clf_counts: logits and targets contiguous fp32 (N, K).  DEI2I_CLF_MULTI (bce / mse, multi-label): class k of a row is
+ * predicted when logit > 0 (a logit of exactly 0 is a negative) and wanted when target > 0.5.  DEI2I_CLF_ARGMAX (cce): the row
+ * predicts the first argmax of its logits and wants the first argmax of its targets.  counts: 4*K + 1 int64 words, TP[K] | FP[K] |
+ * FN[K] | TN[K] | the number of rows right in every class; the launch ADDS to them (the caller zeroes them once, a whole loader
+ * sums without a host read).  One workgroup, a class's words written by one thread: no atomics.  BAD_ARG: null pointers, N, K <= 0,
+ * N*K >= 2^31, another kind. */
+#define DEI2I_CLF_MULTI 0
+#define DEI2I_CLF_ARGMAX 1
+int64_t dei2i_image_metrics_ws_doubles(int N, int C, int H, int W);
+int dei2i_image_metrics(int N, int C, int H, int W, const float* x, const float* y, const float* mask, double data_range, double* ws,
+                        double* out, dei2i_stream s);
+int dei2i_clf_counts(int N, int K, const float* logits, const float* targets, int kind, int64_t* counts, dei2i_stream s);
+
 /* ---- spectral normalisation of a conv weight (--use_spectral; torch.nn.utils.spectral_norm semantics, one power
  * iteration per training-mode forward) ----  W = weight_orig as a (Cout, K) fp32 matrix, u (Cout) / v (K) the module's
  * buffers (updated in place when iterate != 0); u_used / v_used receive the vectors sigma was computed with (the backward
