@@ -86,7 +86,7 @@ if not os.path.exists(HEADER_PATH):
     raise RuntimeError(f"the C ABI header {HEADER_PATH} is missing: the ctypes binding is derived from it")
 with open(HEADER_PATH) as _f:
     CONSTANTS, STRUCTS, SIGNATURES = parse_header(_f.read())
-globals().update(CONSTANTS)          # BF16, ACT_*, PAD_*, ERR_*, DIFFAUG_*, BLIT_*, PROF_*, EMBED_MAX_LABEL_NC, DIGEST_MAX_ROWS
+globals().update(CONSTANTS)          # BF16, ACT_*, PAD_*, ERR_*, DIFFAUG_*, BLIT_*, WARP_*, PROF_*, EMBED_MAX_LABEL_NC, DIGEST_MAX_ROWS
 ConvDesc, ProDesc, EpiNormDesc, LabelMod, AdamRec, DiffAugRec = (
     STRUCTS["dei2i_" + n] for n in ("conv", "pro", "epi_norm", "label_mod", "adam_rec", "diffaug_rec"))
 ADAM_REC_WORDS = ctypes.sizeof(AdamRec) // 8          # int64 words in one row of a device table of dei2i_adam_rec

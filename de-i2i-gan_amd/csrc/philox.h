@@ -1,5 +1,5 @@
 // The counter-based generator of the device-drawn random parameters (diffaug.hip dei2i_diffaug_draw, mask.hip dei2i_mask_draw,
-// embed.hip dei2i_embed_draw, blit.hip dei2i_blit_draw): key = a seed, counter words = (call low, call high, stream word, row) -- include/dei2i_hip.h gives each user's word layout.
+// embed.hip dei2i_embed_draw, blit.hip dei2i_blit_draw, warp.hip dei2i_warp_draw): key = a seed, counter words = (call low, call high, stream word, row) -- include/dei2i_hip.h gives each user's word layout.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

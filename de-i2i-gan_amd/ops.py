@@ -2001,6 +2001,45 @@ class _BlitInverse(torch.autograd.Function):
         return _Blit.apply(gg, ctx.codes, None), None
 
 
+# The warp runs (scale -> rotate -> aniso, csrc/warp.hip): one bilinear resampling per sample, a linear map whose input gradient is
+# its transpose applied to the output gradient -- a gather with the forward's own weights, no atomics -- and whose own gradient is the
+# forward again: differentiable to any order and bit-reproducible.  Nothing is saved but the record table.
+def _warp_run(x, tab, adjoint: int):
+    x = x.contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    n, c, h, w = x.shape
+    out = torch.empty_like(x)
+    L.check(_lib_for(x).dei2i_warp(n, c, h, w, _p(tab), adjoint, _p(x), _p(out), _stream()), "warp")
+    return out
+
+
+class _Warp(torch.autograd.Function):
+    """y = W x, W the sample's bilinear resampling matrix"""
+
+    @staticmethod
+    def forward(ctx, x, tab, host):
+        ctx.tab, ctx.host = tab, host                      # (host: the pinned source of the table's upload, alive while the graph is)
+        return _warp_run(x, tab, 0)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _WarpAdjoint.apply(g, ctx.tab), None, None
+
+
+class _WarpAdjoint(torch.autograd.Function):
+    """W^T g; its transpose is the forward"""
+
+    @staticmethod
+    def forward(ctx, g, tab):
+        ctx.tab = tab
+        return _warp_run(g, tab, 1)
+
+    @staticmethod
+    def backward(ctx, gg):
+        return _Warp.apply(gg, ctx.tab, None), None
+
+
 # Data-parallel stargan-v2 (stargan.Solver under parallel.attach_ddp): each rank holds rows [rank * n, (rank + 1) * n) of the global
 # batch, and the reference augments the whole global batch with one draw per function.  Inside ``diffaug_sharded(rank, world)`` the
 # draws are those of the global batch (utils.diffaug.draw_params(shard=...)) and only the rank's rows are uploaded and applied.
@@ -2055,19 +2094,26 @@ def _gate_word(p, device, what):
     return p
 
 
+def _run_kind(names):
+    """utils.diffaug.BLIT / WARP for a run of those kinds, None for a color / translation / cutout run"""
+    from .utils.diffaug import BLIT, WARP, is_blit_run, is_warp_run
+    return BLIT if is_blit_run(names) else WARP if is_warp_run(names) else None
+
+
 def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0, p=None):
     """One dei2i_diffaug_draw launch on the current stream: -> (tab, runs), ``tab`` a device int32 (len(runs), n, 8) table of struct
     dei2i_diffaug_rec for global rows [row0, row0 + n), ``runs`` the (has_color, cut_h, cut_w) list of utils.diffaug.draw_params.
     Nothing is read from the host RNG and nothing is uploaded.  ``p`` (a one-element fp32 device tensor in [0, 1]): the gated
     draw dei2i_diffaug_draw_p instead -- each policy applies to a row with probability ``p``, read on the device by the launch.
     A policy with blit runs (flip -> rot90): ``runs`` holds ``utils.diffaug.BLIT`` at their places and ``tab`` the records of the
-    other runs in order (``None``, and no launch, when there is none); ``blit_draw`` draws the codes, after this call."""
-    from .utils.diffaug import BLIT, REC_FIELDS, check_policy, is_blit_run, policy_runs
+    other runs in order (``None``, and no launch, when there is none); ``blit_draw`` draws the codes, after this call.  Warp runs
+    (scale -> rotate -> aniso) alike: ``utils.diffaug.WARP`` at their places, their records drawn by ``warp_draw``, after both."""
+    from .utils.diffaug import REC_FIELDS, check_policy, policy_runs
     check_policy(policy, h, w)
     whole = policy_runs(policy)
     if not 0 < len(whole) <= L.DIFFAUG_MAX_RUNS:
         raise ValueError(f"diff_augment with a device RNG takes 1..{L.DIFFAUG_MAX_RUNS} canonical-order runs; {policy!r} has {len(whole)}")
-    names = [run for run in whole if not is_blit_run(run)]
+    names = [run for run in whole if _run_kind(run) is None]
     bit = {"color": L.DIFFAUG_COLOR, "translation": L.DIFFAUG_TRANSLATION, "cutout": L.DIFFAUG_CUTOUT}
     flags, runs = 0, []
     for r, run in enumerate(names):
@@ -2075,7 +2121,7 @@ def diffaug_draw(rng: DiffAugRng, policy, n, h, w, row0=0, p=None):
         cut = "cutout" in run
         runs.append(("color" in run, int(h * 0.5 + 0.5) if cut else 0, int(w * 0.5 + 0.5) if cut else 0))
     affine = iter(runs)
-    runs = [BLIT if is_blit_run(run) else next(affine) for run in whole]
+    runs = [_run_kind(run) or next(affine) for run in whole]
     if not names:
         return None, runs
     tab = torch.empty((len(names), n, REC_FIELDS), dtype=torch.int32, device=rng.device)
@@ -2112,6 +2158,33 @@ def blit_draw(rng: DiffAugRng, policy, n, row0=0, p=None):
         L.check(lib.dei2i_blit_draw_p(rng.seed, _p(rng.counter), len(whole), flags, n, int(row0),
                                       _p(_gate_word(p, rng.device, "blit_draw")), _p(codes), _stream()), "blit_draw_p")
     return codes
+
+
+def warp_draw(rng: DiffAugRng, policy, n, row0=0, p=None):
+    """One dei2i_warp_draw launch on the current stream: -> a device int32 (warp runs, n, 8) table, row b the records (the 8-word rows
+    of dei2i_warp, the floats stored bitwise) of the b-th warp run of ``policy`` for global rows [row0, row0 + n) (the counter-word
+    layout: include/dei2i_hip.h -- the run word is the run's index in the whole list).  ``p``: the gated draw dei2i_warp_draw_p.
+    A policy without a warp run raises ValueError."""
+    from .utils.diffaug import REC_FIELDS, is_warp_run, policy_runs
+    whole = policy_runs(policy)
+    if not 0 < len(whole) <= L.DIFFAUG_MAX_RUNS:
+        raise ValueError(f"diff_augment with a device RNG takes 1..{L.DIFFAUG_MAX_RUNS} canonical-order runs; {policy!r} has {len(whole)}")
+    bit = {"scale": L.WARP_SCALE, "rotate": L.WARP_ROTATE, "aniso": L.WARP_ANISO}
+    flags = count = 0
+    for r, run in enumerate(whole):
+        if is_warp_run(run):
+            flags |= sum(bit[name] for name in run) << (3 * r)
+            count += 1
+    if not count:
+        raise ValueError(f"warp_draw: {policy!r} holds no scale, rotate or aniso")
+    tab = torch.empty((count, n, REC_FIELDS), dtype=torch.int32, device=rng.device)
+    lib = _lib_for(tab)
+    if p is None:
+        L.check(lib.dei2i_warp_draw(rng.seed, _p(rng.counter), len(whole), flags, n, int(row0), _p(tab), _stream()), "warp_draw")
+    else:
+        L.check(lib.dei2i_warp_draw_p(rng.seed, _p(rng.counter), len(whole), flags, n, int(row0),
+                                      _p(_gate_word(p, rng.device, "warp_draw")), _p(tab), _stream()), "warp_draw_p")
+    return tab
 
 
 class AdaState:
@@ -2226,9 +2299,11 @@ def state_digest(tensors, rows_per_launch=None):
 
 def diff_augment(x, policy="", rng=None, p=None):
     """DiffAugment(x, policy) of utils/diffaug.py on an NCHW fp32 GPU image batch, one or two launches per canonical-order policy
-    run (one per blit run: flip -> rot90, csrc/blit.hip).  ``policy == ""`` returns ``x`` itself.  ``rng=None``: the same draws from
+    run (one per blit run: flip -> rot90, csrc/blit.hip; one per warp run: scale -> rotate -> aniso, csrc/warp.hip).
+    ``policy == ""`` returns ``x`` itself.  ``rng=None``: the same draws from
     the global CPU RNG as utils/diffaug.py, one upload of the parameter table per call.  ``rng`` a ``DiffAugRng``: the table is drawn
-    on the device by one more launch (``diffaug_draw``), and the codes of the blit runs by one more (``blit_draw``, after it) -- the
+    on the device by one more launch (``diffaug_draw``), the codes of the blit runs by one more (``blit_draw``, after it) and the
+    matrices of the warp runs by one more (``warp_draw``, last) -- the
     CPU RNG is not touched, nothing is uploaded, and the call can be captured into a graph.
     Inside ``diffaug_sharded`` ``x`` is one rank's rows of the global batch (above).  ``p`` (needs ``rng``): a one-element fp32 device
     tensor, the probability with which each policy applies to a row (``diffaug_draw``); the apply launches are the same.
@@ -2240,7 +2315,7 @@ def diff_augment(x, policy="", rng=None, p=None):
     _require_gpu(x, "diff_augment")
     if x.dim() != 4 or x.dtype != torch.float32:
         raise TypeError("diff_augment expects an NCHW fp32 image batch")
-    from .utils.diffaug import BLIT, check_policy, draw_params
+    from .utils.diffaug import BLIT, WARP, check_policy, draw_params
     n, _, h, w = x.shape
     check_policy(policy, h, w)
     if rng is not None:
@@ -2249,24 +2324,30 @@ def diff_augment(x, policy="", rng=None, p=None):
         row0 = diffaug_shard[0] * n if diffaug_shard is not None else 0
         tab, runs = diffaug_draw(rng, policy, n, h, w, row0=row0, p=p)
         codes = blit_draw(rng, policy, n, row0=row0, p=p) if BLIT in runs else None
+        mats = warp_draw(rng, policy, n, row0=row0, p=p) if WARP in runs else None
         host = None
     else:
         rec, runs = draw_params(policy, n, h, w, shard=diffaug_shard)
         blits = [r for r, run in enumerate(runs) if run == BLIT]
-        if blits:                                            # (the other runs' records, then one code word per sample: one upload)
+        warps = [r for r, run in enumerate(runs) if run == WARP]
+        if blits or warps:               # (the affine runs' records, the warp runs' records, then one code word per sample: one upload)
             import numpy as np
-            others = [r for r in range(len(runs)) if r not in blits]
-            rec = np.concatenate([rec[others].reshape(-1), rec[blits, :, 0].reshape(-1)])
+            others = [r for r in range(len(runs)) if r not in blits and r not in warps]
+            rec = np.concatenate([rec[others].reshape(-1), rec[warps].reshape(-1), rec[blits, :, 0].reshape(-1)])
         host = torch.empty(rec.shape, dtype=torch.int32, pin_memory=True)
         host.copy_(torch.from_numpy(rec))
         tab = host.to(x.device, non_blocking=True)
-        if blits:
-            tab, codes = tab[:len(others) * n * 8].view(len(others), n, 8), tab[len(others) * n * 8:].view(len(blits), n)
-    affine = blit = 0
+        if blits or warps:
+            a, b = len(others) * n * 8, (len(others) + len(warps)) * n * 8
+            tab, mats, codes = tab[:a].view(len(others), n, 8), tab[a:b].view(len(warps), n, 8), tab[b:].view(len(blits), n)
+    affine = blit = warp = 0
     for run in runs:
         if run == BLIT:
             x = _Blit.apply(x, codes[blit], host)
             blit += 1
+        elif run == WARP:
+            x = _Warp.apply(x, mats[warp], host)
+            warp += 1
         else:
             x = _DiffAug.apply(x, tab[affine], run, 0, host)
             affine += 1

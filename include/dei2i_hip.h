@@ -400,6 +400,55 @@ int dei2i_blit_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run
 int dei2i_blit_draw_p(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, const float* p_dev,
                       int* codes, dei2i_stream s);
 
+/* ---- the geometric policies (utils/diffaug.py: scale -> rotate -> aniso; csrc/warp.hip) on fp32 NCHW images: per sample ONE bilinear
+ * resampling with a 2x2 matrix about the image centre.  With cx = (W - 1) / 2, cy = (H - 1) / 2, dx = j - cx, dy = i - cy, output
+ * pixel (i, j) samples the input at
+ *   u = (m00 dx + m01 dy) + (cx + tu),   v = (m10 dx + m11 dy) + (cy + tv)
+ * in fp32, in exactly this association, without contraction; u0 = floor(u), fu = u - u0 (v alike) and
+ *   dst[i][j] = ((t0 + t1) + t2) + t3,  t = weight * tap over (v0, u0), (v0, u0 + 1), (v0 + 1, u0), (v0 + 1, u0 + 1) with the weights
+ *   (1 - fv)(1 - fu), (1 - fv) fu, fv (1 - fu), fv fu; a tap outside the image gives t = 0 (zero fill) and nothing is read for it.
+ * The pixel is 0 when u or v is not finite or lies outside [-1, W) x [-1, H), tested in floating point before any conversion.
+ * adjoint != 0 is the exact transpose with the forward's own weights: dst[y][x] = sum of weight(i, j -> y, x) * src[i][j] over the
+ * output pixels (i, j) in ascending row-major order, starting from 0, the weight recomputed from (i, j) by the forward's function.
+ * One thread owns one input pixel and searches a box of at most 19 x 19 output pixels: a gather, no atomics, one launch,
+ * deterministic in both directions.
+ * USABLE records: the six floats are finite, |m| <= 4 for each of the four matrix entries, and with det = m00 m11 - m01 m10 (in
+ * double: both products exact, one rounding) det != 0 and |m| <= 4 |det| for each entry, i.e. every entry of the inverse is at most
+ * 4 in magnitude -- that bounds the box.  A record that is not usable is applied as the IDENTITY (1, 0, 0, 1, 0, 0) in both
+ * directions.  Drawn matrices have entries and inverse entries of at most 2 and never meet the gate.  No table, whatever it holds,
+ * moves a read or a write outside the two N*C*H*W buffers, and every loop ends within the box bound.  tab_dev: N records of device
+ * memory, each DEI2I_WARP_REC_WORDS = 8 32-bit words (32 bytes, the size of a dei2i_diffaug_rec: one upload carries both kinds):
+ * the fp32 words m00, m01, m10, m11, tu, tv, then two pad words that the launch does not read.  BAD_ARG: null pointers,
+ * N, C, H, W <= 0, N*C*H*W >= 2^40, C*H*W >= 2^31 (the limits of dei2i_diffaug), H or W > 2^16 (the size up to which the box
+ * provably holds every contributing pixel: csrc/warp.hip), and src and dst that overlap. */
+#define DEI2I_WARP_REC_WORDS 8
+int dei2i_warp(int N, int C, int H, int W, const float* tab_dev, int adjoint, const float* src, float* dst, dei2i_stream s);
+/* Fill tab[b][n] (warp runs x N records, b counting the warp runs of the list in order, n in [0, N)) on the device from Philox4x32-10:
+ * key = seed, counter words = (call low 32, call high 32, run | 4 << 16, row0 + n), run the run's index in the WHOLE run list of the
+ * policy (blocks 0..2 of that word belong to dei2i_diffaug_draw, block 3 to dei2i_blit_draw): x0 -> r_s, x1 -> r_t, x2 -> r_l, each
+ * (x >> 8) * 2^-24.  In fp32 without contraction, with the accurate exp2f, sinf, cosf (not the fast forms):
+ *   s = exp2f(r_s - 0.5);  t = (2 r_t - 1) * (float)pi, c = cosf(t), sn = sinf(t);  l = exp2f(r_l - 0.5)
+ *   m00 = l * (c * s);  m01 = l * (-(sn * s));  m10 = (sn * s) / l;  m11 = (c * s) / l;  tu = tv = 0, pad0 = pad1 = 0
+ * -- M = diag(l, 1/l) . R(t) . s I, both singular values in [1/2, 2].  run_flags: 3 bits per run of the whole list, run r at bits
+ * [3r, 3r + 3): the warp policies the run holds, 0 for a run of another kind (no row in the table); a policy that is absent
+ * contributes its identity exactly (s = 1; c = 1, sn = 0; l = 1).  One launch of one workgroup, no atomics; it leaves *counter_dev
+ * greater by exactly 1 under the ordering rule of dei2i_diffaug_draw, whose counter it shares: a diff_augment call launches
+ * dei2i_diffaug_draw FIRST, dei2i_blit_draw SECOND and dei2i_warp_draw THIRD, only those it has runs for, and each sees the count
+ * the one before it left.  A pure function of (seed, call, run, row0 + n): rows [row0, row0 + N) are that slice of the whole-batch
+ * call.  BAD_ARG: null pointers, runs outside 1..DEI2I_DIFFAUG_MAX_RUNS, flag bits beyond the runs, no warp run, N <= 0, row0 < 0,
+ * row0 + N > 2^31, runs * N >= 2^24. */
+#define DEI2I_WARP_SCALE 1
+#define DEI2I_WARP_ROTATE 2
+#define DEI2I_WARP_ANISO 4
+int dei2i_warp_draw(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, float* tab, dei2i_stream s);
+/* The same table with a gate per row and policy: block 5 (counter word run | 5 << 16) gives x0 for scale, x1 for rotate, x2 for
+ * aniso, and a policy of the run applies to the row iff (x >> 8) * 2^-24 < *p_dev (one fp32 word of device memory); one that does
+ * not apply contributes its identity exactly.  Block 4 is drawn as without gates: p = 1 gives the table of dei2i_warp_draw bit for
+ * bit, p = 0 identity records only, and a row's parameters do not depend on its gates.  BAD_ARG: as dei2i_warp_draw, and a null
+ * p_dev. */
+int dei2i_warp_draw_p(uint64_t seed, uint64_t* counter_dev, int runs, uint64_t run_flags, int N, int row0, const float* p_dev,
+                      float* tab, dei2i_stream s);
+
 /* ---- the controller of p (csrc/ada.hip; Karras et al. 2020: r_t = E[sign(D(real))] held at a target) ----
  * dei2i_ada_measure: one workgroup over n fp32 logits; pair_dev[0] = sum of (x > 0) - (x < 0), pair_dev[1] = n, two int64 words,
  * written, or added to when accumulate != 0.  NaN and +-0 count 0 towards the sum and 1 towards n.  Integer sums: exact and
